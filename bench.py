@@ -70,7 +70,12 @@ def main():
     ap.add_argument("--workload", choices=["denoise", "train"], default="denoise",
                     help="denoise: the BASELINE metric (default).  train: BASELINE configs[3] -- multi-speaker naive GAN "
                          "training step (G+D), global batch 8*N sharded over N ranks, gradients all-reduced over RCCL")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline leg's last timed step returned as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB in all, larger outputs as a fixed seeded sample of their elements)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)                 # the parent never touches the GPU
@@ -114,6 +119,9 @@ def main():
     from mixgan_tts_amd import ops, _lib
     from helpers import hot_path_configs, write_stats
 
+    # torch's global generator supplies module init and the seed of the in-kernel noise (Denoiser.p_sample) and the
+    # training step's draws: pinned, so the same arguments give the same inputs and noise in every run
+    torch.manual_seed(1234)
     if args.workload == "train":
         return train_workload(args, mg, dev, dist, rank, world)
 
@@ -157,7 +165,9 @@ def main():
         return precision == "fp32" and not args.project_per_step and single_launch(precision) \
             and os.environ.get("MG_COND_PREPROJECT", "1") != "0"
 
-    def measure(precision, hoist=None):
+    outputs = {}
+
+    def measure(precision, hoist=None, keep_output=False):
         den.precision = precision
         pk = den.packed_weights()
         hoist = hoists(precision) if hoist is None else hoist
@@ -204,13 +214,15 @@ def main():
         ms = (ctypes.c_float * (args.steps * n_layers))()
         n_ev = Lh.mg_profile_end(ms, args.steps * n_layers)
         assert torch.isfinite(cur).all(), "non-finite output"
+        if keep_output:
+            outputs["x_prev"] = cur.cpu()          # x_{t-1} [B, 80, L] of the last timed step (the later legs reuse `bufs`)
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         if dist is not None:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         k_ms = float(np.mean(np.frombuffer(ms, dtype=np.float32)[:n_ev])) if n_ev > 0 else float("nan")
         return float(tmax.item()), k_ms, int(n_ev)
 
-    dt, k_ms, n_ev = measure(args.precision)
+    dt, k_ms, n_ev = measure(args.precision, keep_output=bool(args.dump_outputs))
     per_step = None
     if hoists(args.precision) and not args.no_alt:
         per_step = measure(args.precision, False)     # the same steps with the projection left inside every launch
@@ -296,10 +308,34 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(gd, B, L)
             line["speedup_vs_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each output as d/<name>.npy, float64 kept, anything else as float32.  When the whole would pass
+    DUMP_BYTES, an array over its even share of the budget is cut to a fixed sample of its elements (seeded, sorted
+    flat indices: the same in every run for the same shape), written beside it as <name>_index.npy (float64, exact)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(torch.as_tensor(v).numpy()) for k, v in arrays.items()}
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    budget = DUMP_BYTES - (64 << 10) * len(arrays)      # headroom for the .npy headers
+    share = budget // max(1, len(arrays))
+    squeeze = sum(a.nbytes for a in arrays.values()) > budget
+    for k, a in arrays.items():
+        if squeeze and a.nbytes > share:
+            n = share // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            np.save(os.path.join(d, k + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def launch_ranks(n):
@@ -381,6 +417,7 @@ def train_workload(args, mg, dev, dist, rank, world):
     dt, out = timed(args.warmup, args.steps)
     assert all(torch.isfinite(v).all() for v in out.values())
     trainer.check()                                     # a hand-off timeout would have poisoned the gradients
+    outputs = {k: torch.as_tensor(v).detach().cpu() for k, v in out.items()}   # the last timed step's loss dict
     comm = {}
     if dist is not None:
         # the exposed cost of the gradient exchange: the same steps with the collectives skipped (everything else --
@@ -395,6 +432,8 @@ def train_workload(args, mg, dev, dist, rank, world):
                                "G_early_chunk": (trainer._early[1] - trainer._early[0]) * 4 if trainer._early else 0},
                 "backend": dist.get_backend()}
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         # per step: 2 denoiser forwards + 1 backward (= 4 forward-equivalents), 4 D forwards + 2 backward passes
         flop = (4 * FLOP_PER_FRAME + 8 * 645504.0) * B * L * world
         print(json.dumps({

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -59,11 +60,32 @@ def test_both_legs_and_the_per_step_headline():
     assert "projection_in_every_step" not in q
 
 
-def test_train_workload_line():
-    d = _run(["--workload", "train", "--steps", "2", "--warmup", "1"])
+def test_dump_outputs_follow_the_timed_steps_and_repeat(tmp_path):
+    """--dump-outputs writes x_{t-1} of the headline leg's last timed step; the same arguments give the same inputs and
+    in-kernel noise, so a second run writes the same array, and one more timed step ends somewhere else."""
+    args = ["--steps", "5", "--warmup", "2", "--no-alt", "--no-cpu-baseline", "--batch", "2", "--frames", "96"]
+    out = {}
+    for name, steps in (("a", "5"), ("b", "5"), ("c", "6")):
+        d = _run(args[:1] + [steps] + args[2:] + ["--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == int(steps) and abs(d["value"] * d["ms_per_step"] - 1000.0) < 1.0
+        assert os.listdir(tmp_path / name) == ["x_prev.npy"]
+        out[name] = np.load(tmp_path / name / "x_prev.npy")
+    a = out["a"]
+    assert a.dtype == np.float32 and a.shape == (2, 80, 96) and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.array_equal(a, out["b"])
+    assert not np.array_equal(a, out["c"])
+
+
+def test_train_workload_line(tmp_path):
+    d = _run(["--workload", "train", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
     assert "configs[3]" in d["config"]["workload"] and d["n_gpus"] == 1 and d["steps"] == 2
     assert d["unit"] == "steps/s" and d["value"] > 10 and d["dtype"] == "f32"
     assert "comm_exposed_ms" not in d          # no process group at N=1 unless MG_BENCH_EXCHANGE=1
+    # the last timed step's loss dict, one scalar per loss
+    assert {"adv_loss.npy", "mel_loss.npy", "fm_loss.npy", "d_loss.npy"} <= set(os.listdir(tmp_path))
+    for f in os.listdir(tmp_path):
+        v = np.load(tmp_path / f)
+        assert v.dtype in (np.float32, np.float64) and v.size == 1 and np.isfinite(v).all(), f
 
 
 def test_two_ranks_started_by_bench_itself():

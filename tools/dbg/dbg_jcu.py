@@ -1,5 +1,6 @@
-import sys, torch
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mixgan_tts_amd as mg
 from mixgan_tts_amd import ops, autograd as A
 import torch.nn.functional as F
