@@ -524,6 +524,39 @@ int mg_mapping_mask(const int64_t *dur_w, const int64_t *wb, const int64_t *src_
 int mg_rel_coef(const int64_t *dur, const int64_t *dur_len, const uint8_t *mask, float *out, int B, int T,
                 int Lout, void *stream);
 
+/* ------------------------------------------------------------------ linguistic encoder, inference (lingenc.hip)
+ * Windowed relative-position self-attention (model/blocks.py:1016-1123, heads_share=True):
+ * qkv [B, 3*H*D, L] channel-major (q, k, v stacked), valid uint8 [B,L] (1 = valid), emb_k / emb_v
+ * [2*window+1, D] -> out [B, H*D, L] (before conv_o).  Scores masked with -1e4 where valid[i]*valid[j] == 0,
+ * so padded queries come out finite (the reference's uniform rows).  D must be 128, window <= 8, L <= 2900. */
+int mg_rel_attention_fwd(const float *qkv, const uint8_t *valid, const float *emb_k, const float *emb_v, float *out,
+                         int B, int L, int n_head, int d_head, int window, void *stream);
+/* Word-to-phoneme attention (model/blocks.py:695-768): q [B, H*D, Lq], kv [B, 2*H*D, Lk] (k then v) channel-major;
+ * key_valid [B,Lk], query_valid [B,Lq], mapping [B,Lq,Lk] uint8; prior [B,Lk,Lq] or NULL (helper_type "ctc").
+ * Writes out [B, H*D, Lq] and the head-major [H, B, Lq, Lk] tensors attn (= attn_raw * mapping), attn_raw
+ * (= softmax * query mask) and logprob (the scores, -inf at padded keys).  D must be 128, Lk <= 2900. */
+int mg_w2p_attention_fwd(const float *q, const float *kv, const uint8_t *key_valid, const uint8_t *query_valid,
+                         const uint8_t *mapping, const float *prior, float *out, float *attn, float *attn_raw,
+                         float *logprob, int B, int Lq, int Lk, int n_head, int d_head, void *stream);
+/* nn.Embedding into channel-major: out[b,c,l] = valid[b,l] ? table[ids[b,l], c] : 0 (table [n_rows, C]). */
+int mg_embed_cm(const int64_t *ids, const float *table, const uint8_t *valid, float *out, int B, int L, int C,
+                int n_rows, void *stream);
+/* VariancePredictor head (model/linguistic_encoder.py:163-183,473-478) on h [B,C,L] channel-major:
+ * pred[b,l] = (weight . h[b,:,l] + bias) * valid[b,l] (* control when target is NULL).  With emb [n_bounds+1, C]:
+ * x[b,:,l] += emb[bucketize(target or pred, bins[n_bounds])] at every frame, pads included. */
+int mg_variance_head(const float *h, const float *weight, const float *bias, const uint8_t *valid, float control,
+                     const float *target, const float *bins, int n_bounds, const float *emb, float *pred, float *x,
+                     int B, int C, int L, void *stream);
+/* Word-level duration (model/linguistic_encoder.py:294-316): logw [B,W] = log(word sum of exp(logp [B,Tp]))
+ * (-inf past src_w_len); dur [B,W] int64 = the word sum of target [B,Tp] (int64) when given, else
+ * max(rint(exp(logw) - 1) * d_control, 0) truncated. */
+int mg_duration_head(const float *logp, const int64_t *target, const int64_t *wb, const int64_t *src_w_len,
+                     float d_control, float *logw, int64_t *dur, int B, int Tp, int Tw, int W, void *stream);
+/* add_position_enc (model/linguistic_encoder.py:201-220): out [B,C,L] = x + coef[b,l] * table[l,c];
+ * x is [B,L,C] when x_rowmajor, else [B,C,L]; table [>=L, C]. */
+int mg_posenc_add(const float *x, int x_rowmajor, const float *coef, const float *table, float *out, int B, int C,
+                  int L, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

@@ -26,6 +26,8 @@ EXPORTS = (
     "mg_denoiser_psample", "mg_denoiser_cond_project", "mg_denoiser_step_vectors_floats", "mg_denoiser_step_vectors", "mg_denoiser_persist_status", "mg_persist_error", "mg_denoiser_fwd_pair",
     "mg_grad_norm_scratch_floats", "mg_grad_norm", "mg_adam_flat", "mg_adam_flat_dev",
     "mg_multi_loss_scratch_floats", "mg_multi_loss_fwd", "mg_multi_loss_bwd",
+    "mg_rel_attention_fwd", "mg_w2p_attention_fwd", "mg_embed_cm", "mg_variance_head", "mg_duration_head",
+    "mg_posenc_add",
 )
 
 
@@ -155,6 +157,12 @@ def _declare(L):
         "mg_word_pool_bwd": (i, [vp, vp, vp, vp, i, i, i, i, i, i, vp]),
         "mg_mapping_mask": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_rel_coef": (i, [vp, vp, vp, vp, i, i, i, vp]),
+        "mg_rel_attention_fwd": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "mg_w2p_attention_fwd": (i, [vp] * 10 + [i, i, i, i, i, vp]),
+        "mg_embed_cm": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
+        "mg_variance_head": (i, [vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, i, i, i, vp]),
+        "mg_duration_head": (i, [vp, vp, vp, vp, f, vp, vp, i, i, i, i, vp]),
+        "mg_posenc_add": (i, [vp, i, vp, vp, vp, i, i, i, vp]),
         "mg_resblock_fwd": (i, [vp] * 16 + [i, i, i, i, vp]),
         "mg_gate_bwd": (i, [vp, vp, vp, vp, i, i, i, vp]),
         "mg_mish_fwd": (i, [vp, vp, sz, vp]),

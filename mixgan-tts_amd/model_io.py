@@ -5,9 +5,10 @@ Checkpoint format (unchanged): `<train_config.path.ckpt_path>/<step>.pth.tar`, a
 `optG_fs2`, `optG`, `optD`, `sdlG`, `sdlD` (state dicts).  It is read with `torch.load(..., weights_only=True)`: the
 file only holds tensors and plain containers, and nothing in it is ever executed.
 
-The linguistic encoder is out of scope and injected (`linguistic_encoder=`): with it the generator's state dict has
-the reference's full key set and `G` loads strictly; without it only the keys of the modules on the HIP path are
-restored (and the call says which were skipped).
+The linguistic encoder is injected (`linguistic_encoder=` a module) or native (`linguistic_encoder="native"`, the
+inference-only HIP encoder of linguistic_encoder.py): with either the generator's state dict has the reference's full
+key set and `G` loads strictly; without one only the keys of the modules on the HIP path are restored (and the call
+says which were skipped).
 """
 import os
 
@@ -25,7 +26,8 @@ def checkpoint_path(train_config, step):
 
 
 def get_model(args, configs, device, train=False, linguistic_encoder=None):
-    """-> model (eval) or (model, discriminator, optG_fs2, optG, optD, sdlG, sdlD, epoch) when `train`."""
+    """-> model (eval) or (model, discriminator, optG_fs2, optG, optD, sdlG, sdlD, epoch) when `train`.
+    linguistic_encoder: None, a module, or "native" (synthesis from phoneme ids with no reference module present)."""
     preprocess_config, model_config, train_config = configs
     epoch = 1
     model = MixGANTTS(args, preprocess_config, model_config, train_config, linguistic_encoder=linguistic_encoder).to(device)
