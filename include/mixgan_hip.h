@@ -223,6 +223,27 @@ int mg_denoiser_fwd(const mg_denoiser_dims *d, const float *packed, const float 
                     const int64_t *t, const float *cond, const float *spk, float *out,
                     float *workspace, size_t workspace_floats, int B, int L, int mode, void *stream);
 
+/* Which kernel mg_denoiser_fwd / mg_denoiser_psample run for (B, L, mode): the same decision they make, environment
+ * pins (MG_DENOISER_PERSIST, MG_DENOISER_GENERIC, MG_PERSIST_NT / _SOLO / _TEAM) included.  cproj_mode: 0 none, 1 the
+ * launch stores its conditioner projections (mg_sampling_loop.cproj_out), 2 it reads them (.cproj).  cus: compute
+ * units to plan for, <= 0: the current device's.  No GPU work; the plan depends on no pointer. */
+#define MG_PLAN_PER_LAYER 0 /* path: one launch per residual layer */
+#define MG_PLAN_SINGLE 1    /* path: the whole forward as one launch */
+#define MG_PLAN_PERSIST 0   /* family: denoiser_persist_kernel (32- or 64-frame tiles) */
+#define MG_PLAN_PERSIST16 1 /* family: denoiser_persist16_kernel (16-frame tiles, one workgroup per tile) */
+#define MG_PLAN_TEAM16 2    /* family: denoiser_team16_kernel (16-frame tiles, `team` workgroups per tile) */
+typedef struct mg_fwd_plan {
+    int32_t path;       /* MG_PLAN_PER_LAYER / MG_PLAN_SINGLE; the fields below describe the single launch (else 0) */
+    int32_t family;     /* MG_PLAN_PERSIST / _PERSIST16 / _TEAM16 */
+    int32_t nt;         /* tile width in frames */
+    int32_t waves;      /* waves per workgroup */
+    int32_t solo;       /* 1: the build for one workgroup per CU, 0: two per CU */
+    int32_t team;       /* workgroups per tile (team16), else 0 */
+    int32_t cproj_mode; /* conditioner-projection mode of the launch (0 when saving) */
+    int32_t grid, block;
+} mg_fwd_plan;
+int mg_denoiser_fwd_plan(const mg_denoiser_dims *d, int B, int L, int mode, int cproj_mode, int cus, mg_fwd_plan *out);
+
 /* The workspace's first use must find its 64-float counter block zeroed (allocate it zero-filled once; the kernels
  * re-arm the counters themselves, also under hipGraph replay).
  *

@@ -24,6 +24,7 @@ EXPORTS = (
     "mg_length_regulate_fwd", "mg_length_regulate_bwd", "mg_word_pool_fwd", "mg_word_pool_bwd", "mg_mapping_mask",
     "mg_rel_coef", "mg_resblock_fwd", "mg_gate_bwd", "mg_mish_fwd", "mg_mish_bwd", "mg_step_embed",
     "mg_denoiser_psample", "mg_denoiser_cond_project", "mg_denoiser_step_vectors_floats", "mg_denoiser_step_vectors", "mg_denoiser_persist_status", "mg_persist_error", "mg_denoiser_fwd_pair",
+    "mg_denoiser_fwd_plan",
     "mg_grad_norm_scratch_floats", "mg_grad_norm", "mg_adam_flat", "mg_adam_flat_dev",
     "mg_multi_loss_scratch_floats", "mg_multi_loss_fwd", "mg_multi_loss_bwd",
     "mg_rel_attention_fwd", "mg_w2p_attention_fwd", "mg_embed_cm", "mg_variance_head", "mg_duration_head",
@@ -53,6 +54,12 @@ class SamplingLoop(ctypes.Structure):
     """mg_sampling_loop (include/mixgan_hip.h): what the steps of one sampling loop share."""
     _fields_ = [("cproj", ctypes.c_void_p), ("cproj_out", ctypes.c_void_p), ("step_vectors", ctypes.c_void_p),
                 ("step_index", ctypes.c_int32), ("step_count", ctypes.c_int32)]
+
+
+class FwdPlan(ctypes.Structure):
+    """mg_fwd_plan (include/mixgan_hip.h): which kernel the denoiser forward runs."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "family", "nt", "waves", "solo", "team", "cproj_mode", "grid",
+                                              "block")]
 
 
 def library_path():
@@ -130,6 +137,7 @@ def _declare(L):
         "mg_denoiser_workspace_floats": (sz, [dp, i, i, i]),
         "mg_denoiser_fwd": (i, [dp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, vp]),
         "mg_denoiser_fwd_pair": (i, [dp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, i, i, vp]),
+        "mg_denoiser_fwd_plan": (i, [dp, i, i, i, i, i, ctypes.POINTER(FwdPlan)]),
         "mg_transpose_bml_strided": (i, [vp] * 5 + [i, i, i, i, i, ctypes.c_long, vp]),
         "mg_act_bwd": (i, [vp, vp, vp, i, sz, vp]),
         "mg_upsample_zero": (i, [vp, vp, i, i, i, i, vp]),

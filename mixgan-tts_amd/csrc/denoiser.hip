@@ -713,33 +713,41 @@ static int psample_tail(const PostSample &ps, const float *x0, const float *x_t,
 extern "C" int mg_denoiser_cond_project(const mg_denoiser_dims *d, const float *packed, const float *cond, float *cproj, int B,
                                         int L, void *stream);
 
-static int denoiser_forward(const mg_denoiser_dims *d, const float *packed, const float *x_t, const int64_t *t,
-                            const float *cond, const float *spk, float *out, float *ws, size_t ws_floats, int B,
-                            int L, int mode, const PostSample *post, void *stream)
-{
-    const int save = mode & MG_FWD_SAVE;
-    const int split = mode & MG_FWD_SPLIT;
-    const int has_p16 = mode & MG_FWD_P16;
-    if (split && save) return MG_ERR_ARG;  // the backward consumes fp32 activations
-    MG_TRY(den_check(d));
-    if (!packed || !x_t || !t || !cond || !out || !ws) return MG_ERR_ARG;
-    if (d->multi_speaker && !spk) return MG_ERR_ARG;
-    if (B <= 0 || L <= 0) return MG_ERR_SHAPE;
-    const DenWs w = den_ws(d, B, L, save);
-    if (ws_floats < w.total) return MG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int C = d->channels, H = d->cond_channels, M = d->mel_bins, NL = d->n_layers;
-    const DenLayout o = den_layout(d, (split ? MG_DEN_SPLIT : 0) | (has_p16 ? MG_DEN_P16 : 0));
-    const float *lay0 = packed + o.layers;
+// ------------------------------------------------------------------------------------------ kernel choice
+// What the forward runs for (B, L, mode) on `cus` CUs: the public mg_fwd_plan and what the launch needs besides
+struct DenFwdPlan {
+    mg_fwd_plan k;       // path, family, tile width, waves, solo, team, CPM, grid, block
+    int tiles_per_b;
+    bool fused;          // C = H = 256 and no MG_DENOISER_GENERIC: the fused kernels (single launch or per layer)
+    bool own_vectors;    // the launch computes its step vectors (else it reads a sampling loop's in place)
+};
 
+// the tests' and tools' pins of the single-launch form (read per call: a test pins one form for one call)
+struct DenFwdPins {
+    int nt;     // MG_PERSIST_NT: 16, 32, 64, 328 = 32 frames x 8 waves, 864 = 64 frames x 8 waves (0: none)
+    int solo;   // MG_PERSIST_SOLO=0: never the one-workgroup-per-CU 32- and 16-frame builds
+    int team;   // MG_PERSIST_TEAM: 0 no teams, 2 / 4 pin a size (-1: none)
+};
+static DenFwdPins den_fwd_pins()
+{
+    const char *ne = std::getenv("MG_PERSIST_NT"), *se = std::getenv("MG_PERSIST_SOLO");
+    const char *te = std::getenv("MG_PERSIST_TEAM");
+    return DenFwdPins{ne ? std::atoi(ne) : 0, !(se && se[0] == '0'), te ? std::atoi(te) : -1};
+}
+
+// The one place the forward's kernel is chosen (mg_denoiser_fwd_plan reports it).  cproj_mode: 0, or the loop buffer
+// this launch stores (1) or reads (2) its conditioner projections in; loop_vectors: a sampling loop's step vectors are
+// given (mg_sampling_loop.step_vectors).
+static DenFwdPlan den_fwd_plan(const mg_denoiser_dims *d, int B, int L, int mode, int cproj_mode, bool loop_vectors,
+                               int cus)
+{
+    const bool save = mode & MG_FWD_SAVE, split = mode & MG_FWD_SPLIT, has_p16 = mode & MG_FWD_P16;
+    const int C = d->channels, H = d->cond_channels, M = d->mel_bins, NL = d->n_layers;
+    const DenFwdPins pin = den_fwd_pins();
     static const bool force_generic = std::getenv("MG_DENOISER_GENERIC") != nullptr;
-    const bool fused = !force_generic && C == RB_C && H == RB_C;
-    // ---- single-launch forward (denoiser_persist.h): inference in exact fp32; an utterance's chain of 32-frame tiles
-    // must fit in a quarter of the chip's 512 slots (forward progress with another process on the GPU), and the tag
-    // scheme needs >= 3 layers.  MG_DENOISER_PERSIST=0 keeps the launch-per-layer kernels.
-    const char *pe = std::getenv("MG_DENOISER_PERSIST");   // read per call: tests pin each path
-    const bool no_persist = pe && pe[0] == '0';
-    // tile width: 64 frames (8 waves, one workgroup per CU, weights streamed once per 64 frames) when that still gives
+    DenFwdPlan p{};
+    p.fused = !force_generic && C == RB_C && H == RB_C;
+    // tile width: 64 frames (4 waves, one workgroup per CU, weights streamed once per 64 frames) when that still gives
     // more than 128 workgroups, else 32 frames (4 waves, two per CU: twice the workgroups for small launches)
     // ... and 16 frames (v_mfma_f32_16x16x4_f32, denoiser_persist16.h) when even the 32-frame tiling leaves half the
     // CUs idle: single utterances, the configs[0] shape.  Inference only; needs the 16-row packs (MG_FWD_P16).
@@ -750,236 +758,244 @@ static int denoiser_forward(const mg_denoiser_dims *d, const float *packed, cons
     // the MFMAs of its SIMD partner (measured at that shape: -0.2 ms; the non-saving forward is 8 % SLOWER that way --
     // half the MFMAs per fragment read -- and keeps 4 waves)
     bool wide32 = nt == 32 && save && (long)mg_cdiv(L, 32) * B <= 256;
-    bool eight64 = false;
-    if (const char *ne = std::getenv("MG_PERSIST_NT")) {   // tests pin each width: 16, 32, 64, 328 = 32 frames x 8 waves
-        const int f = std::atoi(ne);
-        if (f == 32 || f == 64 || f == 328 || (f == 16 && has_p16 && !save)) {
-            nt = f == 328 ? 32 : f;
-            wide32 = f == 328;
-        }
-        if (f == 864) {   // 64-frame tiles as eight waves of 32 channels
-            nt = 64;
-            eight64 = true;
-        }
+    bool eight64 = false;   // 64-frame tiles as eight waves of 32 channels (the form up to round 3; A/B and tests)
+    if (pin.nt == 32 || pin.nt == 64 || pin.nt == 328 || (pin.nt == 16 && has_p16 && !save)) {
+        nt = pin.nt == 328 ? 32 : pin.nt;
+        wide32 = pin.nt == 328;
+    }
+    if (pin.nt == 864) {
+        nt = 64;
+        eight64 = true;
     }
     if (nt == 16 && mg_cdiv(L, 16) > 128) nt = 32;
     if (nt != 32) wide32 = false;
     // 32-frame tiles, not saving, at most one per CU: the one-workgroup-per-CU build (MG_PERSIST_SOLO=0: the two-per-CU one)
     // (and an utterance's chain within a quarter of the slots THAT build has: one per CU)
-    bool solo32 = nt == 32 && !wide32 && !save && (long)mg_cdiv(L, 32) * B <= mg_device_cus() &&
-                  mg_cdiv(L, 32) <= mg_device_cus() / 4;
-    if (const char *se = std::getenv("MG_PERSIST_SOLO")) solo32 = solo32 && se[0] != '0';
+    const bool solo32 = pin.solo && nt == 32 && !wide32 && !save && (long)mg_cdiv(L, 32) * B <= cus &&
+                        mg_cdiv(L, 32) <= cus / 4;
     // ... and when even the 16-frame tiles number no more than a quarter of the CUs (one utterance of up to 1024 frames,
     // the configs[0] shape B=4, L<=256): four workgroups per tile, each owning 64 channels (denoiser_team16.h).  The
-    // whole grid must be co-resident, one workgroup per CU.  MG_PERSIST_TEAM=0 keeps one workgroup per tile.
-    // Teams of 4 while tiles x 4 <= CUs, else of 2 while tiles x 2 <= CUs.  MG_PERSIST_TEAM=0 / 2 / 4: none / pin a size.
+    // whole grid must be co-resident, one workgroup per CU.  Teams of 4 while tiles x 4 <= CUs, else of 2 while
+    // tiles x 2 <= CUs.  MG_PERSIST_TEAM=0 / 2 / 4: none / pin a size.
     int team = 0;
-    if (nt == 16 && !save && w.team != 0) {
-        const char *te = std::getenv("MG_PERSIST_TEAM");
+    if (nt == 16 && !save && den_ws(d, B, L, save).team != 0 && pin.team != 0) {
         const long tiles16 = (long)mg_cdiv(L, 16) * B;
-        const int pin = te ? std::atoi(te) : -1;
-        if (pin != 0) {
-            if (tiles16 * 4 <= mg_device_cus() && pin != 2) team = 4;
-            else if (tiles16 * 2 <= mg_device_cus() && pin != 4) team = 2;
-        }
+        if (tiles16 * 4 <= cus && pin.team != 2) team = 4;
+        else if (tiles16 * 2 <= cus && pin.team != 4) team = 2;
     }
     // 16-frame tiles, one workgroup per tile: the one-workgroup-per-CU build (512 registers per wave) when the launch has
     // at most one tile per CU and an utterance's chain fits in a quarter of THOSE slots, else the two-per-CU build
-    bool solo16 = nt == 16 && team == 0 && (long)mg_cdiv(L, 16) * B <= mg_device_cus() && mg_cdiv(L, 16) <= mg_device_cus() / 4;
-    if (const char *se = std::getenv("MG_PERSIST_SOLO")) solo16 = solo16 && se[0] != '0';
-    const int tiles_per_b = mg_cdiv(L, nt);
+    const bool solo16 = pin.solo && nt == 16 && team == 0 && (long)mg_cdiv(L, 16) * B <= cus && mg_cdiv(L, 16) <= cus / 4;
+    p.tiles_per_b = mg_cdiv(L, nt);
     // a quarter of the chip's workgroup slots: one per CU for the builds with one wave per SIMD (64-frame tiles, the
     // 8-wave 32-frame form, 16-frame tiles without teams, the one-per-CU 32-frame build), two for the 4-wave 32-frame form
-    const int chain_cap = (nt == 64 || wide32 || solo32 || solo16) ? mg_device_cus() / 4 : mg_device_cus() / 2;
-    const bool persist = fused && !no_persist && !split && M <= 96 && NL >= 3 && tiles_per_b <= chain_cap;
-    // the step-dependent vectors: this launch's own, unless the caller computed them for its whole sampling loop
-    // (mg_denoiser_step_vectors; read in place by the single-launch kernels only)
-    const bool own_vectors = !(persist && post && post->step_vectors);
-    if (own_vectors) MG_TRY(den_step_vectors(d, o, packed, t, spk, ws, w, B, st));
-    if (persist) {
-        PersistArgs a;
-        a.b_split = 0;
-        a.x_t2 = a.hvec2 = a.dvec2 = a.cond2 = nullptr;
-        a.out2 = nullptr;
-        a.x_t = x_t;
-        a.cond = cond;
-        a.cproj = post ? post->cproj : nullptr;
-        a.cproj_out = post ? post->cproj_out : nullptr;
-        a.in_w = packed + o.in_w;
-        a.in_b = packed + o.in_b;
-        a.layers = lay0;
-        a.layer_stride = o.layer_stride;
-        a.l_wc = o.l_wc;
-        a.l_w3 = o.l_w3;
-        a.l_wo = o.l_wo;
-        a.l_bc = o.l_bc;
-        a.l_b3 = o.l_b3;
-        a.l_bo = o.l_bo;
-        a.skip_w = packed + o.skip_w;
-        a.skip_b = packed + o.skip_b;
-        a.out_w = packed + o.out_w;
-        a.out_b = packed + o.out_b;
-        a.p16layers = packed + o.p16layers;
-        a.p16layer_stride = o.p16layer_stride;
-        a.p_wc = o.p_wc;
-        a.p_w3 = o.p_w3;
-        a.p_wo = o.p_wo;
-        if (nt == 16) {   // the 16x16x4 forms of the head / tail projections
-            a.in_w = packed + o.in_w16;
-            a.skip_w = packed + o.skip_w16;
-            a.out_w = packed + o.out_w16;
-        }
-        a.hvec = ws + w.hvec;
-        a.dvec = ws + w.dvec;
-        a.vec_rows = 0;
-        if (!own_vectors) {
-            const StepVecAt v = den_stepvec_layout(d, (size_t)post->step_count * B);
-            a.hvec = post->step_vectors + v.hvec + (size_t)post->step_index * B * C;
-            a.dvec = post->step_vectors + v.dvec + (size_t)post->step_index * B * C;
-            a.vec_rows = post->step_count * B;
-        }
-        a.out = out;
-        a.t = t;
-        a.coef1 = post ? post->coef1 : nullptr;
-        a.coef2 = post ? post->coef2 : nullptr;
-        a.logvar = post ? post->logvar : nullptr;
-        a.noise = post ? post->noise : nullptr;
-        a.seed = post ? post->seed : 0ull;
-        a.noise_stream = post ? post->noise_stream : 0ull;
-        a.x0_out = post ? post->x0_out : nullptr;
-        a.gran = reinterpret_cast<dp_u64 *>(ws + w.gran);
-        a.team = team ? reinterpret_cast<dp_u64 *>(ws + w.team) : nullptr;
-        a.sync = reinterpret_cast<unsigned *>(ws + w.sync);
-        a.host_err = mg_host_err_device_ptr();
-        a.spin_limit = mg_persist_spin_limit();
-        a.B = B;
-        a.L = L;
-        a.M = M;
-        a.NL = NL;
-        a.tiles_per_b = tiles_per_b;
-        a.post = post ? 1 : 0;
-        a.clip = post ? post->clip : 0;
-        a.n_steps = post ? post->n_steps : 1;
-        a.rsNL = 1.0f / sqrtf((float)NL);
-        a.dbg = g_persist_dbg;
-        {
-            const char *we = g_persist_dbg ? std::getenv("MG_PERSIST_DBG_WAVE") : nullptr;
-            a.dbg_wave = we ? std::atoi(we) & 7 : 0;
-            if (a.dbg_wave >= (nt == 32 && !wide32 ? 4 : 8)) a.dbg_wave = 0;
-        }
-        a.x0_save = save ? ws + w.x0 : nullptr;
-        a.y_save = save ? ws + w.y : nullptr;
-        a.skip_save = save ? ws + w.skip : nullptr;
-        a.h_save = save ? ws + w.h : nullptr;
-        a.g_save = save ? ws + w.g : nullptr;
-        a.sig_save = save ? ws + w.sig : nullptr;
-        a.tnh_save = save ? ws + w.tnh : nullptr;
-        a.act_stride = w.act_stride;
-        {
-            const char *fe = std::getenv("MG_PERSIST_FLAGS");
-            a.flags = fe ? std::atoi(fe) : DP_F_ROLES;
-        }
-        // (16-byte rows for the float4 staging of cond and for the LDS-direct fetches of its projections)
-        const bool vec4 = (L % 4 == 0) && (((uintptr_t)cond & 15) == 0) && (((uintptr_t)a.cproj & 15) == 0);
-        dim3 grid((unsigned)(tiles_per_b * B));
-        prof_mark(st, 0);
-#define MG_DP_LAUNCH(NT, V, T, S) hipLaunchKernelGGL((denoiser_persist_kernel<NT, V, T, S>), grid, dim3(NT * 8), 0, st, a)
-// a step that stores (CPM 1: a.cproj_out) or reads (CPM 2: a.cproj) its conditioner projections: own instantiations
-#define MG_DP_LAUNCH_C(NT, V, T, NWV, CPM) \
-    hipLaunchKernelGGL((denoiser_persist_kernel<NT, V, T, false, NWV, CPM>), grid, dim3(NWV * 64), 0, st, a)
-#define MG_DP_LAUNCH_R(NT, V, T, NWV)                  \
-    do {                                               \
-        if (a.cproj) MG_DP_LAUNCH_C(NT, V, T, NWV, 2); \
-        else MG_DP_LAUNCH_C(NT, V, T, NWV, 1);         \
-    } while (0)
-        const bool readp = (a.cproj != nullptr || a.cproj_out != nullptr) && !save;   // (the launch has a loop's buffer)
-        if (nt == 16 && team == 4) {
-            const dim3 tgrid((unsigned)(tiles_per_b * B * 4));
-            if (vec4) hipLaunchKernelGGL((denoiser_team16_kernel<true, 4>), tgrid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((denoiser_team16_kernel<false, 4>), tgrid, dim3(256), 0, st, a);
-        } else if (nt == 16 && team == 2) {
-            const dim3 tgrid((unsigned)(tiles_per_b * B * 2));
-            if (vec4) hipLaunchKernelGGL((denoiser_team16_kernel<true, 2>), tgrid, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((denoiser_team16_kernel<false, 2>), tgrid, dim3(512), 0, st, a);
-        } else if (nt == 16 && solo16) {
-            if (vec4) hipLaunchKernelGGL((denoiser_persist16_kernel<true, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((denoiser_persist16_kernel<false, true>), grid, dim3(256), 0, st, a);
-        } else if (nt == 16) {
-            if (vec4) hipLaunchKernelGGL((denoiser_persist16_kernel<true, false>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((denoiser_persist16_kernel<false, false>), grid, dim3(256), 0, st, a);
-        } else if (nt == 64 && !eight64) {
-            // 64-frame tiles as FOUR waves of 64 channels: one wave per SIMD with the whole 512-entry register file
-            // (nobody to share the matrix pipe with, nobody's operands queueing behind an older wave's)
-#define MG_DP_LAUNCH4(V, T, S, CPM) \
-    hipLaunchKernelGGL((denoiser_persist_kernel<64, V, T, S, 4, CPM>), grid, dim3(256), 0, st, a)
-#define MG_DP_LAUNCH4V(T, S, CPM)             \
-    do {                                      \
-        if (vec4) MG_DP_LAUNCH4(true, T, S, CPM); \
-        else MG_DP_LAUNCH4(false, T, S, CPM);     \
-    } while (0)
-            const bool stamps = g_persist_dbg && vec4;
-            if (save) MG_DP_LAUNCH4V(false, true, 0);
-            else if (a.cproj) {
-                if (stamps) MG_DP_LAUNCH4(true, true, false, 2);
-                else MG_DP_LAUNCH4V(false, false, 2);
-            } else if (a.cproj_out) MG_DP_LAUNCH4V(false, false, 1);
-            else if (stamps) MG_DP_LAUNCH4(true, true, false, 0);
-            else MG_DP_LAUNCH4V(false, false, 0);
-#undef MG_DP_LAUNCH4V
-#undef MG_DP_LAUNCH4
-        } else if (nt == 64) {   // MG_PERSIST_NT=864: eight waves of 32 channels (the form up to round 3; A/B and tests)
-            if (save) {
-                if (vec4) MG_DP_LAUNCH(64, true, false, true);
-                else MG_DP_LAUNCH(64, false, false, true);
-            } else if (readp) {
-                if (vec4) MG_DP_LAUNCH_R(64, true, false, 8);
-                else MG_DP_LAUNCH_R(64, false, false, 8);
-            } else if (g_persist_dbg && vec4) MG_DP_LAUNCH(64, true, true, false);
-            else if (vec4) MG_DP_LAUNCH(64, true, false, false);
-            else MG_DP_LAUNCH(64, false, false, false);
-        } else if (wide32) {
-#define MG_DP_LAUNCH8(V, S) hipLaunchKernelGGL((denoiser_persist_kernel<32, V, false, S, 8>), grid, dim3(512), 0, st, a)
-            if (save) {
-                if (vec4) MG_DP_LAUNCH8(true, true);
-                else MG_DP_LAUNCH8(false, true);
-            } else if (readp) {
-                if (vec4) MG_DP_LAUNCH_R(32, true, false, 8);
-                else MG_DP_LAUNCH_R(32, false, false, 8);
-            } else if (vec4) MG_DP_LAUNCH8(true, false);
-            else MG_DP_LAUNCH8(false, false);
-#undef MG_DP_LAUNCH8
-        } else if (solo32) {
-            // at most one 32-frame tile per CU: the 4-wave form built for one workgroup per CU (512 registers per wave)
-#define MG_DP_LAUNCH_S(V, CPM) \
-    hipLaunchKernelGGL((denoiser_persist_kernel<32, V, false, false, 4, CPM, true>), grid, dim3(256), 0, st, a)
-            if (a.cproj) {
-                if (vec4) MG_DP_LAUNCH_S(true, 2);
-                else MG_DP_LAUNCH_S(false, 2);
-            } else if (a.cproj_out) {
-                if (vec4) MG_DP_LAUNCH_S(true, 1);
-                else MG_DP_LAUNCH_S(false, 1);
-            } else if (vec4) MG_DP_LAUNCH_S(true, 0);
-            else MG_DP_LAUNCH_S(false, 0);
-#undef MG_DP_LAUNCH_S
-        } else {
-            if (save) {
-                if (vec4) MG_DP_LAUNCH(32, true, false, true);
-                else MG_DP_LAUNCH(32, false, false, true);
-            } else if (readp) {
-                if (vec4) MG_DP_LAUNCH_R(32, true, false, 4);
-                else MG_DP_LAUNCH_R(32, false, false, 4);
-            } else if (g_persist_dbg && vec4) MG_DP_LAUNCH(32, true, true, false);
-            else if (vec4) MG_DP_LAUNCH(32, true, false, false);
-            else MG_DP_LAUNCH(32, false, false, false);
-        }
-#undef MG_DP_LAUNCH_R
-#undef MG_DP_LAUNCH_C
-#undef MG_DP_LAUNCH
-        prof_mark(st, 1);
-        MG_LAUNCH_CHECK();
-        return MG_OK;
+    const int chain_cap = (nt == 64 || wide32 || solo32 || solo16) ? cus / 4 : cus / 2;
+    const bool persist = p.fused && !split && M <= 96 && den_persist_allowed(NL, p.tiles_per_b, chain_cap);
+    p.own_vectors = !(persist && loop_vectors);
+    if (!persist) return p;   // p.k: MG_PLAN_PER_LAYER
+    mg_fwd_plan &k = p.k;
+    k.path = MG_PLAN_SINGLE;
+    k.nt = nt;
+    k.team = team;
+    if (team) {
+        k.family = MG_PLAN_TEAM16;
+        k.waves = 16 / team;
+        k.solo = team == 4;
+    } else if (nt == 16) {
+        k.family = MG_PLAN_PERSIST16;
+        k.waves = 4;
+        k.solo = solo16;
+    } else {
+        k.family = MG_PLAN_PERSIST;
+        k.waves = eight64 || wide32 ? 8 : 4;
+        k.solo = (nt == 64 && !eight64) || solo32;
     }
-    // launch-per-layer path: x_0 first (into `out`), the posterior as one more elementwise launch at the end
+    // a step that stores (CPM 1) or reads (CPM 2) a sampling loop's conditioner projections
+    k.cproj_mode = save ? 0 : cproj_mode;
+    k.grid = p.tiles_per_b * B * (team ? team : 1);
+    k.block = k.waves * 64;
+    return p;
+}
+
+extern "C" int mg_denoiser_fwd_plan(const mg_denoiser_dims *d, int B, int L, int mode, int cproj_mode, int cus,
+                                    mg_fwd_plan *out)
+{
+    MG_TRY(den_check(d));
+    if (!out || cproj_mode < 0 || cproj_mode > 2 || ((mode & MG_FWD_SPLIT) && (mode & MG_FWD_SAVE))) return MG_ERR_ARG;
+    if (B <= 0 || L <= 0) return MG_ERR_SHAPE;
+    *out = den_fwd_plan(d, B, L, mode, cproj_mode, false, cus > 0 ? cus : mg_device_cus()).k;
+    return MG_OK;
+}
+
+// Every built instantiation of the single-launch kernels, by form; [vec4] = float4 staging of cond (and of its
+// projections).  nullptr: not built.
+typedef void (*DenFwdKernel)(PersistArgs);
+template <int NT, bool V, bool T, bool S, int NWV, int CPM = 0, bool SOLO = false>
+constexpr DenFwdKernel dpk = denoiser_persist_kernel<NT, V, T, S, NWV, CPM, SOLO>;
+struct DpForm {
+    DenFwdKernel save[2];     // the saving forward (training)
+    DenFwdKernel cpm[3][2];   // not saving, by conditioner-projection mode
+    DenFwdKernel timing[3];   // TIMING: cycle stamps into mg_debug_persist_stamps' buffer (float4 staging only), by CPM
+};
+static const DpForm dp_forms[5] = {
+    // 64 frames, 4 waves of 64 channels: one wave per SIMD with the whole 512-entry register file (nobody to share the
+    // matrix pipe with, nobody's operands queueing behind an older wave's)
+    {{dpk<64, false, false, true, 4>, dpk<64, true, false, true, 4>},
+     {{dpk<64, false, false, false, 4, 0>, dpk<64, true, false, false, 4, 0>},
+      {dpk<64, false, false, false, 4, 1>, dpk<64, true, false, false, 4, 1>},
+      {dpk<64, false, false, false, 4, 2>, dpk<64, true, false, false, 4, 2>}},
+     {dpk<64, true, true, false, 4, 0>, nullptr, dpk<64, true, true, false, 4, 2>}},
+    // 64 frames, 8 waves of 32 channels (MG_PERSIST_NT=864)
+    {{dpk<64, false, false, true, 8>, dpk<64, true, false, true, 8>},
+     {{dpk<64, false, false, false, 8, 0>, dpk<64, true, false, false, 8, 0>},
+      {dpk<64, false, false, false, 8, 1>, dpk<64, true, false, false, 8, 1>},
+      {dpk<64, false, false, false, 8, 2>, dpk<64, true, false, false, 8, 2>}},
+     {dpk<64, true, true, false, 8, 0>, nullptr, nullptr}},
+    // 32 frames, 8 waves of 32 channels (the saving forward at one tile per CU; MG_PERSIST_NT=328)
+    {{dpk<32, false, false, true, 8>, dpk<32, true, false, true, 8>},
+     {{dpk<32, false, false, false, 8, 0>, dpk<32, true, false, false, 8, 0>},
+      {dpk<32, false, false, false, 8, 1>, dpk<32, true, false, false, 8, 1>},
+      {dpk<32, false, false, false, 8, 2>, dpk<32, true, false, false, 8, 2>}},
+     {nullptr, nullptr, nullptr}},
+    // 32 frames, 4 waves, built for one workgroup per CU (512 registers per wave): not saving, at most one tile per CU
+    {{nullptr, nullptr},
+     {{dpk<32, false, false, false, 4, 0, true>, dpk<32, true, false, false, 4, 0, true>},
+      {dpk<32, false, false, false, 4, 1, true>, dpk<32, true, false, false, 4, 1, true>},
+      {dpk<32, false, false, false, 4, 2, true>, dpk<32, true, false, false, 4, 2, true>}},
+     {nullptr, nullptr, nullptr}},
+    // 32 frames, 4 waves, two workgroups per CU
+    {{dpk<32, false, false, true, 4>, dpk<32, true, false, true, 4>},
+     {{dpk<32, false, false, false, 4, 0>, dpk<32, true, false, false, 4, 0>},
+      {dpk<32, false, false, false, 4, 1>, dpk<32, true, false, false, 4, 1>},
+      {dpk<32, false, false, false, 4, 2>, dpk<32, true, false, false, 4, 2>}},
+     {dpk<32, true, true, false, 4, 0>, nullptr, nullptr}},
+};
+static const DenFwdKernel dp16_kernels[2][2] = {   // [solo][vec4]
+    {denoiser_persist16_kernel<false, false>, denoiser_persist16_kernel<true, false>},
+    {denoiser_persist16_kernel<false, true>, denoiser_persist16_kernel<true, true>}};
+static const DenFwdKernel team16_kernels[2][2] = {   // [team == 4][vec4]
+    {denoiser_team16_kernel<false, 2>, denoiser_team16_kernel<true, 2>},
+    {denoiser_team16_kernel<false, 4>, denoiser_team16_kernel<true, 4>}};
+
+// stamps: a stamp buffer is set (tools only): the TIMING build where the form has one
+static DenFwdKernel den_fwd_kernel(const mg_fwd_plan &k, bool save, bool stamps, bool vec4)
+{
+    if (k.family == MG_PLAN_TEAM16) return team16_kernels[k.team == 4][vec4];
+    if (k.family == MG_PLAN_PERSIST16) return dp16_kernels[k.solo != 0][vec4];
+    const DpForm &f = dp_forms[k.nt == 64 ? (k.waves == 8) : k.waves == 8 ? 2 : k.solo ? 3 : 4];
+    if (save) return f.save[vec4];
+    if (stamps && vec4 && f.timing[k.cproj_mode]) return f.timing[k.cproj_mode];
+    return f.cpm[k.cproj_mode][vec4];
+}
+
+// mg_denoiser_fwd_pair's second problem: utterances [b_split, B) of the launch, saved into (ws, w)
+struct DpPair {
+    int b_split;
+    const float *x_t, *cond;
+    float *out, *ws;
+    const DenWs *w;
+};
+
+// The single-launch kernels' arguments: a forward of B utterances over the workspace (ws, w), or with `pair` the two
+// problems of mg_denoiser_fwd_pair.  The posterior, the loop's buffers, the 16-row packs, the debug stamps and the wave
+// roles (with their test hook MG_PERSIST_FLAGS) are the forward's alone; the pair saves its second problem only.
+static PersistArgs den_persist_args(const mg_denoiser_dims *d, const float *packed, const DenLayout &o,
+                                    const DenFwdPlan &p, const float *x_t, const int64_t *t, const float *cond,
+                                    float *out, float *ws, const DenWs &w, int B, int L, bool save,
+                                    const PostSample *post, const DpPair *pair)
+{
+    const int C = d->channels, NL = d->n_layers;
+    const bool p16 = p.k.nt == 16;             // the 16x16x4 forms of the head / tail projections
+    float *const sws = pair ? pair->ws : save ? ws : nullptr;   // where the saves land
+    const DenWs &sw = pair ? *pair->w : w;
+    PersistArgs a;
+    a.x_t = x_t;
+    a.cond = cond;
+    a.cproj = post ? post->cproj : nullptr;
+    a.cproj_out = post ? post->cproj_out : nullptr;
+    a.in_w = packed + (p16 ? o.in_w16 : o.in_w);
+    a.in_b = packed + o.in_b;
+    a.layers = packed + o.layers;
+    a.layer_stride = o.layer_stride;
+    a.l_wc = o.l_wc;
+    a.l_w3 = o.l_w3;
+    a.l_wo = o.l_wo;
+    a.l_bc = o.l_bc;
+    a.l_b3 = o.l_b3;
+    a.l_bo = o.l_bo;
+    a.p16layers = pair ? nullptr : packed + o.p16layers;
+    a.p16layer_stride = pair ? 0 : o.p16layer_stride;
+    a.p_wc = pair ? 0 : o.p_wc;
+    a.p_w3 = pair ? 0 : o.p_w3;
+    a.p_wo = pair ? 0 : o.p_wo;
+    a.skip_w = packed + (p16 ? o.skip_w16 : o.skip_w);
+    a.skip_b = packed + o.skip_b;
+    a.out_w = packed + (p16 ? o.out_w16 : o.out_w);
+    a.out_b = packed + o.out_b;
+    a.hvec = ws + w.hvec;
+    a.dvec = ws + w.dvec;
+    a.vec_rows = 0;
+    if (!p.own_vectors) {
+        const StepVecAt v = den_stepvec_layout(d, (size_t)post->step_count * B);
+        a.hvec = post->step_vectors + v.hvec + (size_t)post->step_index * B * C;
+        a.dvec = post->step_vectors + v.dvec + (size_t)post->step_index * B * C;
+        a.vec_rows = post->step_count * B;
+    }
+    a.out = out;
+    a.t = t;
+    a.coef1 = post ? post->coef1 : nullptr;
+    a.coef2 = post ? post->coef2 : nullptr;
+    a.logvar = post ? post->logvar : nullptr;
+    a.noise = post ? post->noise : nullptr;
+    a.seed = post ? post->seed : 0ull;
+    a.noise_stream = post ? post->noise_stream : 0ull;
+    a.x0_out = post ? post->x0_out : nullptr;
+    a.gran = reinterpret_cast<dp_u64 *>(ws + w.gran);
+    a.team = p.k.team ? reinterpret_cast<dp_u64 *>(ws + w.team) : nullptr;
+    a.sync = reinterpret_cast<unsigned *>(ws + w.sync);
+    a.host_err = mg_host_err_device_ptr();
+    a.spin_limit = mg_persist_spin_limit();
+    a.B = B;
+    a.L = L;
+    a.M = d->mel_bins;
+    a.NL = NL;
+    a.tiles_per_b = p.tiles_per_b;
+    a.post = post ? 1 : 0;
+    a.clip = post ? post->clip : 0;
+    a.n_steps = post ? post->n_steps : 1;
+    a.rsNL = 1.0f / sqrtf((float)NL);
+    a.dbg = pair ? nullptr : g_persist_dbg;
+    const char *we = a.dbg ? std::getenv("MG_PERSIST_DBG_WAVE") : nullptr;
+    a.dbg_wave = we ? std::atoi(we) & 7 : 0;
+    if (a.dbg_wave >= p.k.waves) a.dbg_wave = 0;
+    a.x0_save = sws ? sws + sw.x0 : nullptr;
+    a.y_save = sws ? sws + sw.y : nullptr;
+    a.skip_save = sws ? sws + sw.skip : nullptr;
+    a.h_save = sws ? sws + sw.h : nullptr;
+    a.g_save = sws ? sws + sw.g : nullptr;
+    a.sig_save = sws ? sws + sw.sig : nullptr;
+    a.tnh_save = sws ? sws + sw.tnh : nullptr;
+    a.act_stride = sw.act_stride;
+    const char *fe = pair ? nullptr : std::getenv("MG_PERSIST_FLAGS");
+    a.flags = pair ? 0 : fe ? std::atoi(fe) : DP_F_ROLES;
+    a.b_split = pair ? pair->b_split : 0;
+    a.x_t2 = pair ? pair->x_t : nullptr;
+    a.cond2 = pair ? pair->cond : nullptr;
+    a.out2 = pair ? pair->out : nullptr;
+    a.hvec2 = pair ? pair->ws + pair->w->hvec : nullptr;
+    a.dvec2 = pair ? pair->ws + pair->w->dvec : nullptr;
+    return a;
+}
+
+// The launch-per-layer forward (split / fused / generic kernels): x_0 first (into `out`), the posterior as one more
+// elementwise launch at the end
+static int den_fwd_layers(const mg_denoiser_dims *d, const float *packed, const DenLayout &o, const float *x_t,
+                          const int64_t *t, const float *cond, float *out, float *ws, const DenWs &w, int B, int L,
+                          int save, int split, bool fused, const PostSample *post, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int C = d->channels, H = d->cond_channels, M = d->mel_bins, NL = d->n_layers;
+    const float *lay0 = packed + o.layers;
     if (post && post->cproj_out)   // its kernels project per layer: the projections a later launch may read come from the GEMM
         MG_TRY(mg_denoiser_cond_project(d, packed, cond, post->cproj_out, B, L, stream));
     float *const final_out = out;
@@ -1062,30 +1078,30 @@ static int denoiser_forward(const mg_denoiser_dims *d, const float *packed, cons
             xb = tmp;
         }
     } else {
-    if (w.x0 != w.x) MG_TRY(copy_d2d(ws + w.x, ws + w.x0, (size_t)B * C * L, st));
-    for (int l = 0; l < NL; ++l) {
-        const float *lp = lay0 + (size_t)l * o.layer_stride;
-        float *hbuf = ws + w.h + (size_t)l * w.act_stride;
-        float *gbuf = ws + w.g + (size_t)l * w.act_stride;
-        {
-            ConvShape s{B, H, L, L, 1, 1, 0, C, 0, 0};
-            EpiCond::Params ep{hbuf, lp + o.l_bc, ws + w.x, ws + w.hvec + (size_t)l * B * C, C};
-            MG_TRY(conv_launch<EpiCond>(s, cond, nullptr, lp + o.l_wc, ep, st));
+        if (w.x0 != w.x) MG_TRY(copy_d2d(ws + w.x, ws + w.x0, (size_t)B * C * L, st));
+        for (int l = 0; l < NL; ++l) {
+            const float *lp = lay0 + (size_t)l * o.layer_stride;
+            float *hbuf = ws + w.h + (size_t)l * w.act_stride;
+            float *gbuf = ws + w.g + (size_t)l * w.act_stride;
+            {
+                ConvShape s{B, H, L, L, 1, 1, 0, C, 0, 0};
+                EpiCond::Params ep{hbuf, lp + o.l_bc, ws + w.x, ws + w.hvec + (size_t)l * B * C, C};
+                MG_TRY(conv_launch<EpiCond>(s, cond, nullptr, lp + o.l_wc, ep, st));
+            }
+            {
+                ConvShape s{B, C, L, L, 3, 1, 1, 2 * C, 0, 0};
+                EpiGate::Params ep{gbuf, lp + o.l_b3, save ? ws + w.sig + (size_t)l * w.act_stride : nullptr,
+                                   save ? ws + w.tnh + (size_t)l * w.act_stride : nullptr, C};
+                prof_mark(st, 0);
+                MG_TRY(conv_launch<EpiGate>(s, hbuf, nullptr, lp + o.l_w3, ep, st));
+                prof_mark(st, 1);
+            }
+            {
+                ConvShape s{B, C, L, L, 1, 1, 0, 2 * C, 0, 0};
+                EpiResSkip::Params ep{ws + w.x, ws + w.skip, lp + o.l_bo, ws + w.dvec + (size_t)l * B * C, C, l == 0};
+                MG_TRY(conv_launch<EpiResSkip>(s, gbuf, nullptr, lp + o.l_wo, ep, st));
+            }
         }
-        {
-            ConvShape s{B, C, L, L, 3, 1, 1, 2 * C, 0, 0};
-            EpiGate::Params ep{gbuf, lp + o.l_b3, save ? ws + w.sig + (size_t)l * w.act_stride : nullptr,
-                               save ? ws + w.tnh + (size_t)l * w.act_stride : nullptr, C};
-            prof_mark(st, 0);
-            MG_TRY(conv_launch<EpiGate>(s, hbuf, nullptr, lp + o.l_w3, ep, st));
-            prof_mark(st, 1);
-        }
-        {
-            ConvShape s{B, C, L, L, 1, 1, 0, 2 * C, 0, 0};
-            EpiResSkip::Params ep{ws + w.x, ws + w.skip, lp + o.l_bo, ws + w.dvec + (size_t)l * B * C, C, l == 0};
-            MG_TRY(conv_launch<EpiResSkip>(s, gbuf, nullptr, lp + o.l_wo, ep, st));
-        }
-    }
     }
     // sum(skips)/sqrt(NL) -> skip_projection -> ReLU -> output_projection (model/modules.py:441-444)
     if (fused && M <= 128) {
@@ -1108,6 +1124,38 @@ static int denoiser_forward(const mg_denoiser_dims *d, const float *packed, cons
     return post ? psample_tail(*post, out, x_t, t, final_out, reinterpret_cast<unsigned *>(ws + w.sync), B, M, L, st) : MG_OK;
 }
 
+static int denoiser_forward(const mg_denoiser_dims *d, const float *packed, const float *x_t, const int64_t *t,
+                            const float *cond, const float *spk, float *out, float *ws, size_t ws_floats, int B,
+                            int L, int mode, const PostSample *post, void *stream)
+{
+    const int save = mode & MG_FWD_SAVE;
+    const int split = mode & MG_FWD_SPLIT;
+    if (split && save) return MG_ERR_ARG;  // the backward consumes fp32 activations
+    MG_TRY(den_check(d));
+    if (!packed || !x_t || !t || !cond || !out || !ws) return MG_ERR_ARG;
+    if (d->multi_speaker && !spk) return MG_ERR_ARG;
+    if (B <= 0 || L <= 0) return MG_ERR_SHAPE;
+    const DenWs w = den_ws(d, B, L, save);
+    if (ws_floats < w.total) return MG_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const DenLayout o = den_layout(d, (split ? MG_DEN_SPLIT : 0) | (mode & MG_FWD_P16 ? MG_DEN_P16 : 0));
+    const int cproj_mode = post && post->cproj ? 2 : post && post->cproj_out ? 1 : 0;
+    const DenFwdPlan p = den_fwd_plan(d, B, L, mode, cproj_mode, post && post->step_vectors, mg_device_cus());
+    if (p.own_vectors) MG_TRY(den_step_vectors(d, o, packed, t, spk, ws, w, B, st));
+    if (p.k.path == MG_PLAN_PER_LAYER)
+        return den_fwd_layers(d, packed, o, x_t, t, cond, out, ws, w, B, L, save, split, p.fused, post, stream);
+    const PersistArgs a = den_persist_args(d, packed, o, p, x_t, t, cond, out, ws, w, B, L, save, post, nullptr);
+    // (16-byte rows for the float4 staging of cond and for the LDS-direct fetches of its projections)
+    const bool vec4 = (L % 4 == 0) && (((uintptr_t)cond & 15) == 0) && (((uintptr_t)a.cproj & 15) == 0);
+    const DenFwdKernel kern = den_fwd_kernel(p.k, save, g_persist_dbg != nullptr, vec4);
+    if (!kern) return MG_ERR_ARG;
+    prof_mark(st, 0);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.k.grid), dim3((unsigned)p.k.block), 0, st, a);
+    prof_mark(st, 1);
+    MG_LAUNCH_CHECK();
+    return MG_OK;
+}
+
 // Both generator forwards of a GAN training step (train.py:133 and :153: same weights, different t / noise) as ONE
 // launch: problem A = the D phase's no-grad forward, problem B = the G phase's saving forward, Bh utterances each over
 // the same conditioner.  wsA: a workspace for (2 Bh, L, no save) -- tickets, halo granules, A's step vectors; wsB: one for
@@ -1126,84 +1174,23 @@ extern "C" int mg_denoiser_fwd_pair(const mg_denoiser_dims *d, const float *pack
     if (d->multi_speaker && !spk) return MG_ERR_ARG;
     if (Bh <= 0 || L <= 0) return MG_ERR_SHAPE;
     const int C = d->channels, H = d->cond_channels, M = d->mel_bins, NL = d->n_layers;
-    const int tiles_per_b = mg_cdiv(L, 64);
-    const char *pe = std::getenv("MG_DENOISER_PERSIST");
-    if ((pe && pe[0] == '0') || C != RB_C || H != RB_C || M > 96 || NL < 3 || tiles_per_b > mg_device_cus() / 4) return MG_ERR_SHAPE;
+    DenFwdPlan p{};
+    p.tiles_per_b = mg_cdiv(L, 64);
+    if (C != RB_C || H != RB_C || M > 96 || !den_persist_allowed(NL, p.tiles_per_b, mg_device_cus() / 4)) return MG_ERR_SHAPE;
     const DenWs wA = den_ws(d, 2 * Bh, L, 0), wB = den_ws(d, Bh, L, 1);
     if (wsA_floats < wA.total || wsB_floats < wB.total) return MG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const DenLayout o = den_layout(d, 0);
     MG_TRY(den_step_vectors(d, o, packed, tA, spk, wsA, wA, Bh, st));
     MG_TRY(den_step_vectors(d, o, packed, tB, spkB, wsB, wB, Bh, st));
-    PersistArgs a;
-    a.x_t = x_tA;
-    a.x_t2 = x_tB;
-    a.out = outA;
-    a.out2 = outB;
-    a.hvec = wsA + wA.hvec;
-    a.dvec = wsA + wA.dvec;
-    a.vec_rows = 0;
-    a.hvec2 = wsB + wB.hvec;
-    a.dvec2 = wsB + wB.dvec;
-    a.b_split = Bh;
-    a.cond = cond;
-    a.cproj = nullptr;
-    a.cproj_out = nullptr;
-    a.cond2 = condB;
-    a.in_w = packed + o.in_w;
-    a.in_b = packed + o.in_b;
-    a.layers = packed + o.layers;
-    a.layer_stride = o.layer_stride;
-    a.l_wc = o.l_wc;
-    a.l_w3 = o.l_w3;
-    a.l_wo = o.l_wo;
-    a.l_bc = o.l_bc;
-    a.l_b3 = o.l_b3;
-    a.l_bo = o.l_bo;
-    a.skip_w = packed + o.skip_w;
-    a.skip_b = packed + o.skip_b;
-    a.out_w = packed + o.out_w;
-    a.out_b = packed + o.out_b;
-    a.p16layers = nullptr;
-    a.p16layer_stride = 0;
-    a.p_wc = a.p_w3 = a.p_wo = 0;
-    a.t = nullptr;
-    a.coef1 = a.coef2 = a.logvar = a.noise = nullptr;
-    a.seed = a.noise_stream = 0ull;
-    a.x0_out = nullptr;
-    a.gran = reinterpret_cast<dp_u64 *>(wsA + wA.gran);
-    a.team = nullptr;
-    a.sync = reinterpret_cast<unsigned *>(wsA + wA.sync);
-    a.host_err = mg_host_err_device_ptr();
-    a.spin_limit = mg_persist_spin_limit();
-    a.B = 2 * Bh;
-    a.L = L;
-    a.M = M;
-    a.NL = NL;
-    a.tiles_per_b = tiles_per_b;
-    a.post = 0;
-    a.clip = 0;
-    a.n_steps = 1;
-    a.rsNL = 1.0f / sqrtf((float)NL);
-    a.dbg = nullptr;
-    a.dbg_wave = 0;
-    a.x0_save = wsB + wB.x0;
-    a.y_save = wsB + wB.y;
-    a.skip_save = wsB + wB.skip;
-    a.h_save = wsB + wB.h;
-    a.g_save = wsB + wB.g;
-    a.sig_save = wsB + wB.sig;
-    a.tnh_save = wsB + wB.tnh;
-    a.act_stride = wB.act_stride;
-    a.flags = 0;
+    // 64-frame tiles as four waves (one workgroup per CU), or as eight with MG_PERSIST_NT=864 (see den_fwd_plan)
+    const int waves = den_fwd_pins().nt == 864 ? 8 : 4;
+    p.k = mg_fwd_plan{MG_PLAN_SINGLE, MG_PLAN_PERSIST, 64, waves, waves == 4, 0, 0, p.tiles_per_b * 2 * Bh, waves * 64};
+    p.own_vectors = true;
+    const DpPair pb{Bh, x_tB, condB, outB, wsB, &wB};
+    const PersistArgs a = den_persist_args(d, packed, o, p, x_tA, nullptr, cond, outA, wsA, wA, 2 * Bh, L, false, nullptr, &pb);
     const bool vec4 = (L % 4 == 0) && (((uintptr_t)cond & 15) == 0) && (((uintptr_t)condB & 15) == 0);
-    dim3 grid((unsigned)(tiles_per_b * 2 * Bh));
-    const char *ne = std::getenv("MG_PERSIST_NT");
-    if (ne && std::atoi(ne) == 864) {   // eight waves of 32 channels (see denoiser_forward)
-        if (vec4) hipLaunchKernelGGL((denoiser_persist_kernel<64, true, false, true>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((denoiser_persist_kernel<64, false, false, true>), grid, dim3(512), 0, st, a);
-    } else if (vec4) hipLaunchKernelGGL((denoiser_persist_kernel<64, true, false, true, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((denoiser_persist_kernel<64, false, false, true, 4>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(den_fwd_kernel(p.k, true, false, vec4), dim3((unsigned)p.k.grid), dim3((unsigned)p.k.block), 0, st, a);
     MG_LAUNCH_CHECK();
     return MG_OK;
 }

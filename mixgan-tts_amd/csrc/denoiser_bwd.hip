@@ -256,9 +256,8 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
     // dout = [dx_l / sqrt2 ; dskip]; slot l+1 of dx_all holds the dx that ENTERS layer l, slot l the one it produces
     // One persistent launch (denoiser_bwd_persist.h) when the shapes allow; MG_DENOISER_PERSIST=0 keeps the two
     // generic conv launches per layer.
-    const char *pe = std::getenv("MG_DENOISER_PERSIST");
     const int tiles_per_b = mg_cdiv(L, 32);
-    const bool persist = !(pe && pe[0] == '0') && C == RB_C && NL >= 3 && tiles_per_b <= mg_device_cus() / 4;
+    const bool persist = C == RB_C && den_persist_allowed(NL, tiles_per_b, mg_device_cus() / 4);
     if (persist) {
         BwdPersistArgs pa;
         pa.dout = dout;

@@ -3,6 +3,7 @@
 // of the step-embedding MLP.
 #pragma once
 #include "conv_mfma.h"
+#include <cstdlib>
 
 // ------------------------------------------------------------------------------------------ single-launch kernels: host side
 // (defined in denoiser.hip; used by the forward and backward launchers)
@@ -14,6 +15,15 @@ int mg_device_cus();
 unsigned *mg_host_err_device_ptr();
 // polls a hand-off wait makes before it gives up: DP_SPIN_LIMIT, or MG_PERSIST_SPIN_LIMIT (tests)
 unsigned mg_persist_spin_limit();
+// May a single-launch kernel (forward or backward) run?  MG_DENOISER_PERSIST=0 keeps the launch-per-layer kernels
+// (read per call: tests pin each path); the tag scheme needs >= 3 layers; an utterance's chain of tiles must fit in
+// chain_cap workgroup slots (a quarter of the chip's: forward progress with another process on the GPU).  Shape
+// conditions of the kernel itself are the caller's.
+static inline bool den_persist_allowed(int NL, int tiles_per_b, int chain_cap)
+{
+    const char *pe = std::getenv("MG_DENOISER_PERSIST");
+    return !(pe && pe[0] == '0') && NL >= 3 && tiles_per_b <= chain_cap;
+}
 
 // ------------------------------------------------------------------------------------------ packed blob
 struct DenLayout {

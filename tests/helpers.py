@@ -199,3 +199,20 @@ def mixgantts_tapes(g):
     n = len([k for k in g if k.startswith("rng")])
     m = len([k for k in g if k.startswith("mask")])
     return [g["rng%d" % i] for i in range(n)], [g["mask%d" % i] for i in range(m)]
+
+
+def pin_width(monkeypatch, nt):
+    """MG_PERSIST_NT pins a tile width; 16: teams of workgroups per tile where they fit (denoiser_team16.h: 4 members,
+    else 2), 216: teams of 2 only, 116: 16-frame tiles with one workgroup per tile (denoiser_persist16.h) everywhere;
+    328: 32-frame tiles, 8 waves; 64: 64-frame tiles as four waves (one per SIMD), 864: as eight waves of 32 channels."""
+    monkeypatch.setenv("MG_PERSIST_NT", str(16 if nt in (116, 216) else 32 if nt == 232 else nt))
+    if nt == 232:      # 32-frame tiles, the two-workgroups-per-CU build also where one tile per CU would get the other one
+        monkeypatch.setenv("MG_PERSIST_SOLO", "0")
+    else:
+        monkeypatch.delenv("MG_PERSIST_SOLO", raising=False)
+    if nt == 116:
+        monkeypatch.setenv("MG_PERSIST_TEAM", "0")
+    elif nt == 216:
+        monkeypatch.setenv("MG_PERSIST_TEAM", "2")
+    else:
+        monkeypatch.delenv("MG_PERSIST_TEAM", raising=False)

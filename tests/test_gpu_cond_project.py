@@ -4,7 +4,7 @@ and p_sample reading it instead of projecting inside the kernel -- the same x_{t
 import pytest
 import torch
 
-from helpers import golden, T, seeded, assert_close, hot_path_configs, write_stats, load_seeded, Tape
+from helpers import golden, T, seeded, assert_close, hot_path_configs, write_stats, load_seeded, Tape, pin_width
 from oracle import refmath as R, schedule as S
 
 pytestmark = pytest.mark.gpu
@@ -28,20 +28,6 @@ def _diffusion(mg, manifest, tmp_path, ms=False):
     return gd.cuda().eval(), W
 
 
-def _pin_width(monkeypatch, nt):
-    monkeypatch.setenv("MG_PERSIST_NT", str(16 if nt in (116, 216) else 32 if nt == 232 else nt))
-    if nt == 232:      # 32-frame tiles, the two-workgroups-per-CU build also where one tile per CU would get the other one
-        monkeypatch.setenv("MG_PERSIST_SOLO", "0")
-    else:
-        monkeypatch.delenv("MG_PERSIST_SOLO", raising=False)
-    if nt == 116:
-        monkeypatch.setenv("MG_PERSIST_TEAM", "0")
-    elif nt == 216:
-        monkeypatch.setenv("MG_PERSIST_TEAM", "2")
-    else:
-        monkeypatch.delenv("MG_PERSIST_TEAM", raising=False)
-
-
 @pytest.mark.parametrize("B,L", [(2, 200), (1, 77), (3, 1000), (1, 1)])
 def test_cond_projection_matches_every_layers_conv(mg, manifest, tmp_path, B, L):
     gd, _ = _diffusion(mg, manifest, tmp_path)
@@ -59,7 +45,7 @@ def test_cond_projection_matches_every_layers_conv(mg, manifest, tmp_path, B, L)
 @pytest.mark.parametrize("nt", [16, 216, 116, 32, 232, 64, 328, 864])
 @pytest.mark.parametrize("ms", [False, True])
 def test_p_sample_reading_the_projection_is_bitwise_the_same(mg, manifest, tmp_path, monkeypatch, ms, nt):
-    _pin_width(monkeypatch, nt)
+    pin_width(monkeypatch, nt)
     gd, W = _diffusion(mg, manifest, tmp_path, ms)
     den = gd.denoise_fn
     buf = {k: T(v) for k, v in S.diffusion_buffers(S.beta_schedule("vpsde", 4, 0.1, 40, 0.008)).items()}

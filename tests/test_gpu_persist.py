@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import golden, T, seeded, assert_close, hot_path_configs, write_stats, load_seeded, Tape
+from helpers import golden, T, seeded, assert_close, hot_path_configs, write_stats, load_seeded, Tape, pin_width
 from oracle import refmath as R, schedule as S
 
 pytestmark = pytest.mark.gpu
@@ -30,27 +30,10 @@ def _den(mg, manifest, tmp_path, ms=False):
     return den.cuda(), W
 
 
-def _pin_width(monkeypatch, nt):
-    """MG_PERSIST_NT pins a tile width; 16: teams of workgroups per tile where they fit (denoiser_team16.h: 4 members,
-    else 2), 216: teams of 2 only, 116: 16-frame tiles with one workgroup per tile (denoiser_persist16.h) everywhere;
-    328: 32-frame tiles, 8 waves; 64: 64-frame tiles as four waves (one per SIMD), 864: as eight waves of 32 channels."""
-    monkeypatch.setenv("MG_PERSIST_NT", str(16 if nt in (116, 216) else 32 if nt == 232 else nt))
-    if nt == 232:      # 32-frame tiles, the two-workgroups-per-CU build also where one tile per CU would get the other one
-        monkeypatch.setenv("MG_PERSIST_SOLO", "0")
-    else:
-        monkeypatch.delenv("MG_PERSIST_SOLO", raising=False)
-    if nt == 116:
-        monkeypatch.setenv("MG_PERSIST_TEAM", "0")
-    elif nt == 216:
-        monkeypatch.setenv("MG_PERSIST_TEAM", "2")
-    else:
-        monkeypatch.delenv("MG_PERSIST_TEAM", raising=False)
-
-
 @pytest.mark.parametrize("nt", [16, 216, 116, 32, 232, 64, 328, 864])
 @pytest.mark.parametrize("ms", [False, True])
 def test_single_launch_forward_vs_oracle_and_per_layer_path(mg, manifest, tmp_path, monkeypatch, ms, nt):
-    _pin_width(monkeypatch, nt)     # every tile width, whatever the heuristic would pick
+    pin_width(monkeypatch, nt)     # every tile width, whatever the heuristic would pick
     den, W = _den(mg, manifest, tmp_path, ms)
     gen = torch.Generator().manual_seed(11)
     # one tile, a partial tile, tile boundaries, L % 4 != 0 (scalar staging) and == 0 (float4 staging)
@@ -199,7 +182,7 @@ def test_handoff_timeout_poisons_the_output_and_raises(mg, manifest, tmp_path, m
     """A neighbour that never sends its edge column (test hook MG_PERSIST_FLAGS bit 1) with the wait bounded to a few
     polls: the kernel must drain (not hang), its output must be NaN (not a plausible mel), the failure must reach the
     host as MixganHipError, and the module must work again afterwards."""
-    _pin_width(monkeypatch, nt)
+    pin_width(monkeypatch, nt)
     den, W = _den(mg, manifest, tmp_path)
     gen = torch.Generator(device="cuda").manual_seed(9)
     B, L = 2, 200
@@ -255,7 +238,7 @@ def test_full_occupancy_handoffs_are_never_stale(mg, manifest, tmp_path, monkeyp
     utterance gives alone (other placement, other neighbours in flight); and it must match the per-layer kernels."""
     # 512 workgroups of 32 frames (two per CU) / 256 of 64 frames.  16: one workgroup per tile also for the single
     # utterances below (the four-workgroup teams reduce in another order: their own test compares them with themselves)
-    _pin_width(monkeypatch, 116 if nt == 16 else nt)
+    pin_width(monkeypatch, 116 if nt == 16 else nt)
     den, W = _den(mg, manifest, tmp_path)
     gen = torch.Generator(device="cuda").manual_seed(16)
     B, L = 16, 1000
@@ -290,7 +273,7 @@ def test_full_occupancy_handoffs_are_never_stale(mg, manifest, tmp_path, monkeyp
 def test_more_tiles_than_slots_and_long_utterances(mg, manifest, tmp_path, monkeypatch, nt):
     """B=40, L=1000 = 1280 (640) workgroups on 512 (256) slots (later tiles start as earlier utterances finish), and
     L=4000 (125- / 63-tile chains): finite, deterministic, equal to each sample alone."""
-    _pin_width(monkeypatch, 116 if nt == 16 else nt)     # (one workgroup per tile also for the sample alone)
+    pin_width(monkeypatch, 116 if nt == 16 else nt)     # (one workgroup per tile also for the sample alone)
     den, _ = _den(mg, manifest, tmp_path)
     gen = torch.Generator(device="cuda").manual_seed(40)
     for B, L in [(40, 1000), (6, 4000 if nt > 16 else 2000)]:     # 16-frame chains: L <= 2048
