@@ -578,6 +578,48 @@ int mg_duration_head(const float *logp, const int64_t *target, const int64_t *wb
 int mg_posenc_add(const float *x, int x_rowmajor, const float *coef, const float *table, float *out, int B, int C,
                   int L, void *stream);
 
+/* ------------------------------------------------------------------ linguistic encoder, training (lingenc.hip,
+ * lingenc_train.hip).  Every reduction has a fixed order: two runs give bit-identical gradients.
+ * Train-mode relative self-attention: mg_rel_attention_fwd plus dropout on the probabilities (model/blocks.py:1059)
+ * with keep [B,H,L,L] uint8 (NULL: none) and keep_scale = 1/(1-p); P [B,H,L,L] receives the softmax before dropout
+ * (NULL: not saved). */
+int mg_rel_attention_train_fwd(const float *qkv, const uint8_t *valid, const float *emb_k, const float *emb_v,
+                               const uint8_t *keep, float keep_scale, float *out, float *P, int B, int L, int n_head,
+                               int d_head, int window, void *stream);
+/* Workspace (floats) of mg_rel_attention_bwd; 0 for unsupported sizes. */
+size_t mg_rel_attention_bwd_ws_floats(int B, int L, int n_head, int window);
+/* Backward of mg_rel_attention_train_fwd: dOut [B,H*D,L] -> dqkv [B,3*H*D,L], d_emb_k / d_emb_v [2*window+1, D]
+ * (summed over batch, heads and queries: the heads share one table).  Masked scores pass no gradient. */
+int mg_rel_attention_bwd(const float *qkv, const uint8_t *valid, const float *P, const uint8_t *keep, float keep_scale,
+                         const float *dOut, const float *emb_k, const float *emb_v, float *dqkv, float *d_emb_k,
+                         float *d_emb_v, float *ws, size_t ws_floats, int B, int L, int n_head, int d_head, int window,
+                         void *stream);
+/* Workspace (floats) of mg_w2p_attention_bwd. */
+size_t mg_w2p_attention_bwd_ws_floats(int B, int Lq, int Lk, int n_head);
+/* Backward of mg_w2p_attention_fwd from its inputs and its attn / attn_raw / logprob outputs.  Upstream gradients:
+ * dOut [B,H*D,Lq], and d_attn / d_raw / d_logprob [H,B,Lq,Lk] each NULL when zero.  -> dq [B,H*D,Lq],
+ * dkv [B,2*H*D,Lk].  Padded keys (-inf scores) get exactly zero. */
+int mg_w2p_attention_bwd(const float *q, const float *kv, const uint8_t *key_valid, const uint8_t *query_valid,
+                         const uint8_t *mapping, const float *prior, const float *attn, const float *attn_raw,
+                         const float *logprob, const float *dOut, const float *d_attn, const float *d_raw,
+                         const float *d_logprob, float *dq, float *dkv, float *ws, size_t ws_floats, int B, int Lq,
+                         int Lk, int n_head, int d_head, void *stream);
+/* nn.Embedding gradient: dtable [n_rows, C] (overwritten) = sum of dout[b,:,l] over the tokens with ids[b,l] == row
+ * (and valid[b,l], when valid is not NULL); row skip_row (padding_idx, or -1) is zero. */
+int mg_embed_cm_bwd(const int64_t *ids, const float *dout, const uint8_t *valid, float *dtable, int B, int L, int C,
+                    int n_rows, int skip_row, void *stream);
+/* Backward of mg_variance_head's prediction: g = dpred * valid * scale (scale = control without a target, else 1);
+ * dh [B,C,L] = weight[c] g, dweight [C] = sum h g, dbias [1] = sum g. */
+int mg_variance_head_bwd(const float *h, const float *weight, const uint8_t *valid, float scale, const float *dpred,
+                         float *dh, float *dweight, float *dbias, int B, int C, int L, void *stream);
+/* Backward of mg_duration_head's logw: dlogp [B,Tp] = dlogw[word] * exp(logp - logw[word]), 0 outside counted words. */
+int mg_duration_head_bwd(const float *logp, const float *logw, const float *dlogw, const int64_t *wb,
+                         const int64_t *src_w_len, float *dlogp, int B, int Tp, int Tw, int W, void *stream);
+/* Backward of mg_posenc_add into the table: dtable [L,C] = sum_b coef[b,l] * dout[b,c,l] (dout channel-major). */
+int mg_posenc_add_bwd(const float *dout, const float *coef, float *dtable, int B, int C, int L, void *stream);
+/* Dropout with a given keep-mask: out[e] = keep[e] ? x[e] * scale : 0 (also its own backward). */
+int mg_dropout_apply(const float *x, const uint8_t *keep, float scale, float *out, size_t n, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

@@ -23,5 +23,6 @@ from .mixgantts import MixGANTTS, get_mask_from_lengths  # noqa: F401
 from .transformer import Decoder, FFTBlock, PostNet, MultiHeadAttention, PositionwiseFeedForward  # noqa: F401
 from .model_io import get_model, save_checkpoint, get_param_num  # noqa: F401
 from .linguistic_encoder import LinguisticEncoder  # noqa: F401
+from .losses import LinguisticEncoderLoss  # noqa: F401
 
 __version__ = "0.1.0"

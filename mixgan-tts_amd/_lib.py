@@ -29,6 +29,9 @@ EXPORTS = (
     "mg_multi_loss_scratch_floats", "mg_multi_loss_fwd", "mg_multi_loss_bwd",
     "mg_rel_attention_fwd", "mg_w2p_attention_fwd", "mg_embed_cm", "mg_variance_head", "mg_duration_head",
     "mg_posenc_add",
+    "mg_rel_attention_train_fwd", "mg_rel_attention_bwd_ws_floats", "mg_rel_attention_bwd", "mg_w2p_attention_bwd_ws_floats",
+    "mg_w2p_attention_bwd", "mg_embed_cm_bwd", "mg_variance_head_bwd", "mg_duration_head_bwd", "mg_posenc_add_bwd",
+    "mg_dropout_apply",
 )
 
 
@@ -171,6 +174,16 @@ def _declare(L):
         "mg_variance_head": (i, [vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, i, i, i, vp]),
         "mg_duration_head": (i, [vp, vp, vp, vp, f, vp, vp, i, i, i, i, vp]),
         "mg_posenc_add": (i, [vp, i, vp, vp, vp, i, i, i, vp]),
+        "mg_rel_attention_train_fwd": (i, [vp, vp, vp, vp, vp, f, vp, vp, i, i, i, i, i, vp]),
+        "mg_rel_attention_bwd_ws_floats": (sz, [i, i, i, i]),
+        "mg_rel_attention_bwd": (i, [vp, vp, vp, vp, f] + [vp] * 7 + [sz, i, i, i, i, i, vp]),
+        "mg_w2p_attention_bwd_ws_floats": (sz, [i, i, i, i]),
+        "mg_w2p_attention_bwd": (i, [vp] * 16 + [sz, i, i, i, i, i, vp]),
+        "mg_embed_cm_bwd": (i, [vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "mg_variance_head_bwd": (i, [vp, vp, vp, f, vp, vp, vp, vp, i, i, i, vp]),
+        "mg_duration_head_bwd": (i, [vp] * 6 + [i, i, i, i, vp]),
+        "mg_posenc_add_bwd": (i, [vp, vp, vp, i, i, i, vp]),
+        "mg_dropout_apply": (i, [vp, vp, f, vp, sz, vp]),
         "mg_resblock_fwd": (i, [vp] * 16 + [i, i, i, i, vp]),
         "mg_gate_bwd": (i, [vp, vp, vp, vp, i, i, i, vp]),
         "mg_mish_fwd": (i, [vp, vp, sz, vp]),

@@ -1,6 +1,7 @@
 // Inference kernels of the LinguisticEncoder (model/linguistic_encoder.py, model/blocks.py) that the
 // generic library kernels do not cover:
 //   mg_rel_attention_fwd   RelativeSelfAttention.attention (blocks.py:1016-1123): windowed relative keys/values
+//                          (mg_rel_attention_train_fwd: the same with attention dropout and the probabilities saved)
 //   mg_w2p_attention_fwd   ScaledDotProductAttention inside WordToPhonemeAttention (blocks.py:695-768)
 //   mg_embed_cm            nn.Embedding gather straight into the channel-major layout, pads zeroed
 //   mg_variance_head       VariancePredictor.linear_layer + mask + control + bucketize + embedding add
@@ -37,14 +38,19 @@ static size_t le_lds_bytes(int rows, int Lk)
 // REL: RelativeSelfAttention (q, k, v are slices of one qkv tensor; x_mask in kvalid; -1e4 masking; relative terms
 //      within |j - i| <= w).  !REL: word-to-phoneme attention (-inf key masking, optional ctc prior, query and
 //      mapping masks, the three [H, B, Lq, Lk] probability / log-probability tensors written head-major).
-template <bool REL, int ROWS>
+// TRAIN (REL only): the softmax probabilities go to psave [B, H, L, L] (when not NULL) and the P of both products is
+//      dropout(P) with the uint8 keep-mask [B, H, L, L] (when not NULL) -- `self.drop(p_attn)`, model/blocks.py:1059.
+//      The inference instantiation (TRAIN = false) never reads the three extra arguments.
+template <bool REL, int ROWS, bool TRAIN = false>
 __global__ __launch_bounds__(256) void le_attention_kernel(
     const float *__restrict__ q, long q_bs, const float *__restrict__ k, const float *__restrict__ v, long kv_bs,
     int Lq, int Lk, int B, const uint8_t *__restrict__ qvalid, const uint8_t *__restrict__ kvalid,
     const float *__restrict__ emb_k, const float *__restrict__ emb_v, int w, const uint8_t *__restrict__ mapping,
     const float *__restrict__ prior, float *__restrict__ out, long out_bs, float *__restrict__ attn,
-    float *__restrict__ attn_raw, float *__restrict__ logprob)
+    float *__restrict__ attn_raw, float *__restrict__ logprob, const uint8_t *__restrict__ keep, float keep_scale,
+    float *__restrict__ psave)
 {
+    static_assert(REL || !TRAIN, "the train form is the relative self-attention's");
     static_assert(ROWS % 4 == 0, "one softmax wave per row, four waves");
     extern __shared__ float le_sm[];
     float *qs = le_sm;                        // [D][ROWS]
@@ -130,7 +136,15 @@ __global__ __launch_bounds__(256) void le_attention_kernel(
             sum += e;
         }
         sum = le_wave_sum(sum);
-        if (REL) {
+        if (REL && TRAIN) {
+            const size_t pb = (((size_t)b * gridDim.y + h) * Lq + i) * Lk;
+            for (int j = lane; j < Lk; j += 64) {
+                float p = Sr[j] / sum;
+                if (psave) psave[pb + j] = p;
+                if (keep) p = keep[pb + j] ? p * keep_scale : 0.f;
+                Sr[j] = p;
+            }
+        } else if (REL) {
             for (int j = lane; j < Lk; j += 64) Sr[j] = Sr[j] / sum;
         } else {
             const float qm = qvalid[(size_t)b * Lq + i] ? 1.f : 0.f;
@@ -185,20 +199,21 @@ __global__ __launch_bounds__(256) void le_attention_kernel(
     }
 }
 
-template <bool REL>
+template <bool REL, bool TRAIN = false>
 static int le_attention_launch(const float *q, long q_bs, const float *k, const float *v, long kv_bs, int Lq, int Lk,
                                int B, int H, const uint8_t *qvalid, const uint8_t *kvalid, const float *emb_k,
                                const float *emb_v, int w, const uint8_t *mapping, const float *prior, float *out,
-                               long out_bs, float *attn, float *attn_raw, float *logprob, hipStream_t st)
+                               long out_bs, float *attn, float *attn_raw, float *logprob, hipStream_t st,
+                               const uint8_t *keep = nullptr, float keep_scale = 1.f, float *psave = nullptr)
 {
     if (le_lds_bytes(16, Lk) <= LE_LDS_MAX) {
-        hipLaunchKernelGGL((le_attention_kernel<REL, 16>), dim3(mg_cdiv(Lq, 16), H, B), dim3(256), le_lds_bytes(16, Lk),
-                           st, q, q_bs, k, v, kv_bs, Lq, Lk, B, qvalid, kvalid, emb_k, emb_v, w, mapping, prior, out,
-                           out_bs, attn, attn_raw, logprob);
+        hipLaunchKernelGGL((le_attention_kernel<REL, 16, TRAIN>), dim3(mg_cdiv(Lq, 16), H, B), dim3(256),
+                           le_lds_bytes(16, Lk), st, q, q_bs, k, v, kv_bs, Lq, Lk, B, qvalid, kvalid, emb_k, emb_v, w,
+                           mapping, prior, out, out_bs, attn, attn_raw, logprob, keep, keep_scale, psave);
     } else if (le_lds_bytes(4, Lk) <= LE_LDS_MAX) {
-        hipLaunchKernelGGL((le_attention_kernel<REL, 4>), dim3(mg_cdiv(Lq, 4), H, B), dim3(256), le_lds_bytes(4, Lk),
-                           st, q, q_bs, k, v, kv_bs, Lq, Lk, B, qvalid, kvalid, emb_k, emb_v, w, mapping, prior, out,
-                           out_bs, attn, attn_raw, logprob);
+        hipLaunchKernelGGL((le_attention_kernel<REL, 4, TRAIN>), dim3(mg_cdiv(Lq, 4), H, B), dim3(256),
+                           le_lds_bytes(4, Lk), st, q, q_bs, k, v, kv_bs, Lq, Lk, B, qvalid, kvalid, emb_k, emb_v, w,
+                           mapping, prior, out, out_bs, attn, attn_raw, logprob, keep, keep_scale, psave);
     } else {
         return MG_ERR_SHAPE;
     }
@@ -215,6 +230,20 @@ extern "C" int mg_rel_attention_fwd(const float *qkv, const uint8_t *valid, cons
     return le_attention_launch<true>(qkv, 3 * HD * L, qkv + HD * L, qkv + 2 * HD * L, 3 * HD * L, L, L, B, n_head,
                                      valid, valid, emb_k, emb_v, window, nullptr, nullptr, out, HD * L, nullptr,
                                      nullptr, nullptr, (hipStream_t)stream);
+}
+
+// Train form: keep [B, H, L, L] uint8 or NULL (no dropout), P [B, H, L, L] (the softmax before dropout) or NULL
+// (nothing saved: a train-mode forward under no_grad).
+extern "C" int mg_rel_attention_train_fwd(const float *qkv, const uint8_t *valid, const float *emb_k,
+                                          const float *emb_v, const uint8_t *keep, float keep_scale, float *out,
+                                          float *P, int B, int L, int n_head, int d_head, int window, void *stream)
+{
+    if (!qkv || !valid || !emb_k || !emb_v || !out) return MG_ERR_ARG;
+    if (B <= 0 || L <= 0 || n_head <= 0 || d_head != LE_D || window < 0 || window > LE_WMAX) return MG_ERR_SHAPE;
+    const long HD = (long)n_head * LE_D;
+    return le_attention_launch<true, true>(qkv, 3 * HD * L, qkv + HD * L, qkv + 2 * HD * L, 3 * HD * L, L, L, B,
+                                           n_head, valid, valid, emb_k, emb_v, window, nullptr, nullptr, out, HD * L,
+                                           nullptr, nullptr, nullptr, (hipStream_t)stream, keep, keep_scale, P);
 }
 
 extern "C" int mg_w2p_attention_fwd(const float *q, const float *kv, const uint8_t *key_valid,

@@ -1,9 +1,14 @@
-"""Native LinguisticEncoder for inference (model/linguistic_encoder.py:41-380, model/blocks.py:695-768,915-1123).
+"""Native LinguisticEncoder (model/linguistic_encoder.py:41-380, model/blocks.py:695-768,915-1123).
 
 Same class names, constructor arguments, forward signature (14 arguments, nine outputs) and state_dict keys,
-shapes and order as the reference, so a reference checkpoint loads with strict=True.  Eval-mode forward only:
-training the encoder needs backward passes this module does not have, so a forward with grad enabled on
-trainable parameters raises instead of returning outputs that silently lack gradients.
+shapes and order as the reference, so a reference checkpoint loads with strict=True.
+
+Three forwards: eval (no_grad, the inference kernels only); train mode with grad (every op a torch.autograd.Function
+whose forward and backward are library calls: lingenc_train.hip for the two attentions and the per-token glue, the
+conv / LayerNorm / word-pooling / length-regulator Functions otherwise); and train mode under no_grad (the D phase of
+a training step: the same kernels and dropout, nothing saved).  Dropout keep-masks come from transformer._keep_mask
+(so DROPOUT_FN / a module's `dropout_fn` can replay the reference's), requested in the reference's call order and
+with its shapes; where the native layout differs the mask is transposed here.
 
 Internally everything is channel-major [B, C, L] like transformer.py's forward_cm: k=1 / k=3 / k=9 convolutions
 are the generic conv kernel, LayerNorms are mg_layernorm_cm_fwd, the two attentions and the per-token glue
@@ -18,10 +23,10 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops, lingops, _lib
+from . import ops, lingops, _lib, autograd as ag
 from ._lib import fptr, iptr, check, stream_ptr
 from .blocks import ConvNorm, LinearNorm
-from .transformer import get_sinusoid_encoding_table
+from .transformer import get_sinusoid_encoding_table, _keep_mask
 
 # len(text.symbols.symbols) + 1 of the reference (text/symbols.py: pad, punctuation, letters, the ARPAbet set with
 # its "@" prefix, pinyin and the silences), the vocabulary of src_emb.  A constant: the text front end is not ours.
@@ -103,6 +108,307 @@ def posenc_add(x, rowmajor, coef, table):
     return out
 
 
+# ------------------------------------------------------------------------------------ training (lingenc_train.hip)
+def _ws(n):
+    return torch.empty(max(int(n), 1), device="cuda", dtype=torch.float32)
+
+
+def rel_attention_train(qkv, valid8, emb_k, emb_v, n_head, window, keep=None, keep_scale=1.0, save=True):
+    """Train-mode rel_attention: dropout(P) with the uint8 keep-mask [B, H, L, L] -> (out, P or None)."""
+    B, C3, L = qkv.shape
+    d = C3 // (3 * n_head)
+    out = torch.empty(B, n_head * d, L, device=qkv.device, dtype=torch.float32)
+    P = torch.empty(B, n_head, L, L, device=qkv.device, dtype=torch.float32) if save else None
+    check(_lib.lib().mg_rel_attention_train_fwd(fptr(qkv), iptr(valid8, torch.uint8), fptr(emb_k.contiguous()),
+                                                fptr(emb_v.contiguous()), iptr(keep, torch.uint8, True),
+                                                float(keep_scale), fptr(out), fptr(P, True), B, L, n_head, d,
+                                                int(window), stream_ptr()))
+    return out, P
+
+
+def rel_attention_bwd(qkv, valid8, P, keep, keep_scale, d_out, emb_k, emb_v, n_head, window):
+    """-> (d_qkv [B, 3HD, L], d_emb_k, d_emb_v [2w+1, D])."""
+    B, C3, L = qkv.shape
+    d = C3 // (3 * n_head)
+    Lb = _lib.lib()
+    n = Lb.mg_rel_attention_bwd_ws_floats(B, L, n_head, int(window))
+    ws = _ws(n)
+    dqkv = torch.empty_like(qkv)
+    dek = torch.empty_like(emb_k)
+    dev_ = torch.empty_like(emb_v)
+    check(Lb.mg_rel_attention_bwd(fptr(qkv), iptr(valid8, torch.uint8), fptr(P), iptr(keep, torch.uint8, True),
+                                  float(keep_scale), fptr(d_out), fptr(emb_k.contiguous()), fptr(emb_v.contiguous()),
+                                  fptr(dqkv), fptr(dek), fptr(dev_), fptr(ws), ws.numel(), B, L, n_head, d, int(window),
+                                  stream_ptr()))
+    return dqkv, dek, dev_
+
+
+def w2p_attention_bwd(q, kv, key_valid8, query_valid8, mapping8, prior, attn, raw, logp, d_out, d_attn, d_raw, d_logp,
+                      n_head):
+    """-> (dq [B, HD, Lq], dkv [B, 2HD, Lk]); d_attn / d_raw / d_logp may be None."""
+    B, HD, Lq = q.shape
+    Lk = kv.shape[2]
+    Lb = _lib.lib()
+    ws = _ws(Lb.mg_w2p_attention_bwd_ws_floats(B, Lq, Lk, n_head))
+    dq = torch.empty_like(q)
+    dkv = torch.empty_like(kv)
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    check(Lb.mg_w2p_attention_bwd(fptr(q), fptr(kv), iptr(key_valid8, torch.uint8), iptr(query_valid8, torch.uint8),
+                                  iptr(mapping8, torch.uint8), fptr(prior, True), fptr(attn), fptr(raw), fptr(logp),
+                                  fptr(d_out), fptr(c(d_attn), True), fptr(c(d_raw), True), fptr(c(d_logp), True),
+                                  fptr(dq), fptr(dkv), fptr(ws), ws.numel(), B, Lq, Lk, n_head, HD // n_head,
+                                  stream_ptr()))
+    return dq, dkv
+
+
+def embed_cm_bwd(ids, d_out, valid8, n_rows, skip_row=-1):
+    """nn.Embedding's weight gradient [n_rows, C] from a channel-major output gradient [B, C, L]."""
+    B, C, L = d_out.shape
+    dt = torch.empty(n_rows, C, device=d_out.device, dtype=torch.float32)
+    check(_lib.lib().mg_embed_cm_bwd(iptr(ids.to(torch.int64).contiguous(), torch.int64), fptr(d_out),
+                                     iptr(valid8, torch.uint8, True), fptr(dt), B, L, C, n_rows, int(skip_row),
+                                     stream_ptr()))
+    return dt
+
+
+def variance_head_bwd(h, weight, valid8, scale, d_pred):
+    B, C, L = h.shape
+    dh = torch.empty_like(h)
+    dw = torch.empty(C, device=h.device, dtype=torch.float32)
+    db = torch.empty(1, device=h.device, dtype=torch.float32)
+    check(_lib.lib().mg_variance_head_bwd(fptr(h), fptr(weight.reshape(-1).contiguous()), iptr(valid8, torch.uint8),
+                                          float(scale), fptr(d_pred), fptr(dh), fptr(dw), fptr(db), B, C, L,
+                                          stream_ptr()))
+    return dh, dw, db
+
+
+def duration_head_bwd(logp, logw, d_logw, wb, src_w_len):
+    B, Tp = logp.shape
+    d = torch.empty_like(logp)
+    check(_lib.lib().mg_duration_head_bwd(fptr(logp), fptr(logw), fptr(d_logw), iptr(wb, torch.int64),
+                                          iptr(src_w_len, torch.int64), fptr(d), B, Tp, wb.shape[1], logw.shape[1],
+                                          stream_ptr()))
+    return d
+
+
+def posenc_add_bwd(d_out, coef):
+    """-> d table[:L] [L, C] = sum_b coef[b, l] * d_out[b, :, l]."""
+    B, C, L = d_out.shape
+    dt = torch.empty(L, C, device=d_out.device, dtype=torch.float32)
+    check(_lib.lib().mg_posenc_add_bwd(fptr(d_out), fptr(coef), fptr(dt), B, C, L, stream_ptr()))
+    return dt
+
+
+def dropout_apply(x, keep, scale):
+    out = torch.empty_like(x)
+    check(_lib.lib().mg_dropout_apply(fptr(x), iptr(keep, torch.uint8), float(scale), fptr(out), x.numel(),
+                                      stream_ptr()))
+    return out
+
+
+class _RelAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, emb_k, emb_v, valid8, keep, scale, n_head, window):
+        qkv = qkv.contiguous()
+        out, P = rel_attention_train(qkv, valid8, emb_k.detach(), emb_v.detach(), n_head, window, keep, scale)
+        ctx.save_for_backward(qkv, emb_k, emb_v, valid8, P, keep if keep is not None else P.new_empty(0, dtype=torch.uint8))
+        ctx.cfg = (keep is not None, scale, n_head, window)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, emb_k, emb_v, valid8, P, keep = ctx.saved_tensors
+        has_keep, scale, n_head, window = ctx.cfg
+        dqkv, dek, dev_ = rel_attention_bwd(qkv, valid8, P, keep if has_keep else None, scale, g.contiguous(),
+                                            emb_k.detach(), emb_v.detach(), n_head, window)
+        return dqkv, dek, dev_, None, None, None, None, None
+
+
+class _W2PAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, kv, key_valid8, query_valid8, mapping8, prior, n_head):
+        ctx.set_materialize_grads(False)
+        q, kv = q.contiguous(), kv.contiguous()
+        out, attn, raw, logp = w2p_attention(q, kv, key_valid8, query_valid8, mapping8, prior, n_head)
+        ctx.save_for_backward(q, kv, key_valid8, query_valid8, mapping8,
+                              prior if prior is not None else q.new_empty(0), attn, raw, logp)
+        ctx.cfg = (prior is not None, n_head)
+        return out, attn, raw, logp
+
+    @staticmethod
+    def backward(ctx, d_out, d_attn, d_raw, d_logp):
+        q, kv, kvalid, qvalid, mapping, prior, attn, raw, logp = ctx.saved_tensors
+        has_prior, n_head = ctx.cfg
+        if d_out is None:
+            d_out = torch.zeros_like(q)
+        dq, dkv = w2p_attention_bwd(q, kv, kvalid, qvalid, mapping, prior if has_prior else None, attn, raw, logp,
+                                    d_out.contiguous(), d_attn, d_raw, d_logp, n_head)
+        return dq, dkv, None, None, None, None, None
+
+
+class _EmbedFn(torch.autograd.Function):
+    """src_emb gather into [B, C, L] (pads zeroed); the padding_idx row gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, table, ids, valid8, padding_idx):
+        ctx.save_for_backward(ids, valid8)
+        ctx.cfg = (table.shape[0], -1 if padding_idx is None else padding_idx)
+        return embed_cm(ids, table.detach().contiguous(), valid8)
+
+    @staticmethod
+    def backward(ctx, g):
+        ids, valid8 = ctx.saved_tensors
+        n, skip = ctx.cfg
+        return embed_cm_bwd(ids, g.contiguous(), valid8, n, skip), None, None, None
+
+
+class _VarianceHeadFn(torch.autograd.Function):
+    """(pred [B, L], x + emb[bucket] [B, C, L]) = mg_variance_head on a copy of x; without `emb` only pred.
+    `bucket` ([B, L] int64, bucketize of the target or of the detached prediction) routes the embedding gradient."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, x, emb, valid8, control, target, bins):
+        h = h.contiguous()
+        x2 = None if x is None else x.detach().clone()
+        pred = variance_head(h, weight.detach(), bias.detach(), valid8, control, target, bins,
+                             None if emb is None else emb.detach().contiguous(), x2)
+        bucket = None
+        if emb is not None:
+            bucket = torch.bucketize(target if target is not None else pred, bins)
+        ctx.save_for_backward(h, weight, valid8, bucket if bucket is not None else valid8.new_empty(0, dtype=torch.int64))
+        ctx.cfg = (1.0 if target is not None else float(control), None if emb is None else emb.shape[0])
+        if x2 is None:
+            return pred
+        return pred, x2
+
+    @staticmethod
+    def backward(ctx, d_pred, d_x2=None):
+        h, weight, valid8, bucket = ctx.saved_tensors
+        scale, n_emb = ctx.cfg
+        if d_pred is None:
+            d_pred = torch.zeros(h.shape[0], h.shape[2], device=h.device)
+        dh, dw, db = variance_head_bwd(h, weight.detach(), valid8, scale, d_pred.contiguous())
+        dx = demb = None
+        if n_emb is not None and d_x2 is not None:
+            dx = d_x2
+            demb = embed_cm_bwd(bucket, d_x2.contiguous(), None, n_emb)
+        return dh, dw.reshape(weight.shape), db, dx, demb, None, None, None, None
+
+
+class _DurationHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logp, target, wb, src_w_len, d_control, W):
+        logp = logp.contiguous()
+        logw, dur = duration_head(logp, target, wb, src_w_len, d_control, W)
+        ctx.save_for_backward(logp, logw, wb, src_w_len)
+        ctx.mark_non_differentiable(dur)
+        return logw, dur
+
+    @staticmethod
+    def backward(ctx, d_logw, _):
+        logp, logw, wb, src_w_len = ctx.saved_tensors
+        return duration_head_bwd(logp, logw, d_logw.contiguous(), wb, src_w_len), None, None, None, None, None
+
+
+class _PosencAddFn(torch.autograd.Function):
+    """posenc_add with gradients to x and to the position-encoding parameter's first L rows."""
+
+    @staticmethod
+    def forward(ctx, x, param, rowmajor, coef):
+        L = x.shape[1] if rowmajor else x.shape[2]
+        ctx.save_for_backward(coef)
+        ctx.cfg = (rowmajor, tuple(param.shape), L)
+        return posenc_add(x.contiguous(), rowmajor, coef, param.detach()[0])
+
+    @staticmethod
+    def backward(ctx, g):
+        (coef,) = ctx.saved_tensors
+        rowmajor, pshape, L = ctx.cfg
+        g = g.contiguous()
+        dx = ops.transpose_bml(g, True) if rowmajor else g
+        dp = None
+        if ctx.needs_input_grad[1]:
+            dp = torch.zeros(pshape, device=g.device, dtype=torch.float32)
+            dp[0, :L] = posenc_add_bwd(g, coef)
+        return dx, dp, None, None
+
+
+class _DropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, keep, scale):
+        ctx.save_for_backward(keep)
+        ctx.scale = scale
+        return dropout_apply(x.contiguous(), keep, scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        (keep,) = ctx.saved_tensors
+        return dropout_apply(g.contiguous(), keep, ctx.scale), None, None
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """nn.LayerNorm over the channels of [B, C, L] (the VariancePredictor's), no residual, no pad."""
+
+    @staticmethod
+    def forward(ctx, a, gamma, beta, eps):
+        out, pre = ops.layernorm_cm_train(a.contiguous(), None, 1.0, None, gamma.detach(), beta.detach(), None, eps)
+        ctx.save_for_backward(pre, gamma)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pre, gamma = ctx.saved_tensors
+        d_pre, _, dg, db = ops.layernorm_cm_bwd(pre, g.contiguous(), gamma.detach(), None, None, 1.0, ctx.eps)
+        return d_pre, dg, db, None
+
+
+class _LinearAddFn(torch.autograd.Function):
+    """y = W x + res on [B, C, L] (a bias-free k=1 conv with the residual added in its epilogue)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, res):
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        return ops.conv1d_packed(x, ops.pack_cached(weight[:, :, None]), None, weight.shape[0], 1,
+                                 add=res.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        g = g.contiguous()
+        dx = ops.conv1d_packed(g, ops.pack_cached(weight[:, :, None], ops.PACK_DGRAD), None, weight.shape[1], 1,
+                               split=True)
+        dw = ops.conv1d_wgrad(g, x, 1)[:, :, 0] if ctx.needs_input_grad[1] else None
+        return dx, dw, g
+
+
+class _MaskedToCmFn(torch.autograd.Function):
+    """[B, L, C] -> [B, C, L] with the padded frames zeroed (the block's x * x_mask)."""
+
+    @staticmethod
+    def forward(ctx, x, keep8):
+        return ops.transpose_bml(x.contiguous(), False, keep=keep8)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.transpose_bml(g.contiguous(), True), None
+
+
+class CpuTrainingError(_lib.MixganHipError, NotImplementedError):
+    """A train-mode or grad-enabled forward on CPU tensors: training runs on the HIP path only.  Both a library
+    error (no CPU fallback) and NotImplementedError (the native encoder does not train on the CPU)."""
+
+
+def _grad():
+    return torch.is_grad_enabled()
+
+
+def _p(module, p):
+    """Dropout probability of `module` now: p in train mode, 0 in eval mode (an eval forward with grad enabled)."""
+    return p if module.training else 0.0
+
+
 def _packed(*weights):
     """k=1 weights [Co, Ci] stacked along Co, packed once per parameter version."""
     return torch.cat([ops.pack_cached(w[:, :, None] if w.dim() == 2 else w) for w in weights])
@@ -144,6 +450,22 @@ class RelativeSelfAttention(nn.Module):
         self.emb_rel_k = nn.Parameter(torch.randn(1, window_size * 2 + 1, self.k_channels) * rel_stddev)
         self.emb_rel_v = nn.Parameter(torch.randn(1, window_size * 2 + 1, self.k_channels) * rel_stddev)
         self.conv_o = _Conv1d(channels, out_channels, 1)
+        self.p_dropout = p_dropout
+
+    def forward_cm_train(self, x, valid8):
+        """Train mode: returns conv_o(attention with dropout on p_attn) (before the block's drop(y))."""
+        B, C, L = x.shape
+        keep, scale = _keep_mask(self, (B, self.n_heads, L, L), _p(self, self.p_dropout), x.device)
+        w = torch.cat([self.conv_q.weight, self.conv_k.weight, self.conv_v.weight])
+        b = torch.cat([self.conv_q.bias, self.conv_k.bias, self.conv_v.bias])
+        qkv = ag.conv1d(x, w, b)
+        if _grad():
+            att = _RelAttentionFn.apply(qkv, self.emb_rel_k[0], self.emb_rel_v[0], valid8, keep, scale, self.n_heads,
+                                        self.window_size)
+        else:
+            att, _ = rel_attention_train(qkv, valid8, self.emb_rel_k[0], self.emb_rel_v[0], self.n_heads,
+                                         self.window_size, keep, scale, save=False)
+        return ag.conv1d(att, self.conv_o.weight, self.conv_o.bias)
 
     def forward_cm(self, x, valid8):
         C = self.channels
@@ -163,6 +485,7 @@ class FFN(nn.Module):
         if activation is not None:
             raise NotImplementedError("RelativeFFTBlock builds its FFN with the ReLU activation")
         self.kernel_size = kernel_size
+        self.p_dropout = p_dropout
         self.conv = _Conv1d(in_channels, out_channels, kernel_size)
 
     def forward_cm(self, x):
@@ -178,6 +501,7 @@ class RelativeFFTBlock(nn.Module):
                  window_size=None):
         super().__init__()
         self.n_layers = n_layers
+        self.p_dropout = p_dropout
         self.attn_layers = nn.ModuleList()
         self.norm_layers_1 = nn.ModuleList()
         self.ffn_layers = nn.ModuleList()
@@ -204,6 +528,27 @@ class RelativeFFTBlock(nn.Module):
             x = ops.layernorm_cm(y, x, n2.gamma.detach(), n2.beta.detach(), pad8, n2.eps)
         return x
 
+    def forward_cm_train(self, x, valid8, pad8):
+        """Train mode (model/blocks.py:941-954): per layer the keep-masks of p_attn, drop(y) after the attention, the
+        FFN's inner drop and drop(y) after the FFN, in that order.  The FFN's two dropouts act on the same tensor one
+        after the other, so they enter the LayerNorm kernel as one mask (keep1 * keep2, scale1 * scale2)."""
+        for i in range(self.n_layers):
+            n1, n2 = self.norm_layers_1[i], self.norm_layers_2[i]
+            ffn = self.ffn_layers[i]
+            y = self.attn_layers[i].forward_cm_train(x, valid8)
+            keep, scale = _keep_mask(self, tuple(y.shape), _p(self, self.p_dropout), y.device)
+            x = ag.layernorm_train(y, x, n1.gamma, n1.beta, pad8, keep, scale, n1.eps)
+            k = ffn.kernel_size
+            y = ag.conv1d(x, ffn.conv.weight, ffn.conv.bias, 1, k // 2, "relu")
+            keep1, s1 = _keep_mask(ffn, tuple(y.shape), _p(ffn, ffn.p_dropout), y.device)
+            keep2, s2 = _keep_mask(self, tuple(y.shape), _p(self, self.p_dropout), y.device)
+            if keep1 is not None and keep2 is not None:
+                keep, scale = (keep1 & keep2).contiguous(), s1 * s2
+            else:
+                keep, scale = (keep1 if keep1 is not None else keep2), s1 * s2
+            x = ag.layernorm_train(y, x, n2.gamma, n2.beta, pad8, keep, scale, n2.eps)
+        return x
+
 
 class VariancePredictor(nn.Module):
     """model/linguistic_encoder.py:419-478: (ConvNorm k -> ReLU -> LayerNorm) x 2 -> Linear(., 1) -> * mask."""
@@ -222,6 +567,29 @@ class VariancePredictor(nn.Module):
             ("layer_norm_2", nn.LayerNorm(self.filter_size)),
         ]))
         self.linear_layer = nn.Linear(self.conv_output_size, 1)
+        self.dropout_p = model_config["variance_predictor"]["dropout"]
+
+    def hidden_cm_train(self, x):
+        """Train mode: (conv -> ReLU -> LayerNorm -> dropout) x 2; the keep-masks are drawn [B, L, F] (the reference's
+        channel-last layout) and transposed."""
+        c1, c2 = self.conv_layer.conv1d_1, self.conv_layer.conv1d_2
+        n1, n2 = self.conv_layer.layer_norm_1, self.conv_layer.layer_norm_2
+        h = ag.conv1d(x, c1.conv.weight, c1.conv.bias, 1, (self.kernel - 1) // 2, "relu")
+        h = self._drop(_LayerNormFn.apply(h, n1.weight, n1.bias, n1.eps))
+        h = ag.conv1d(h, c2.conv.weight, c2.conv.bias, 1, 1, "relu")
+        return self._drop(_LayerNormFn.apply(h, n2.weight, n2.bias, n2.eps))
+
+    def _drop(self, h):
+        B, F, L = h.shape
+        keep, scale = _keep_mask(self, (B, L, F), _p(self, self.dropout_p), h.device)
+        if keep is None:
+            return h
+        return _DropoutFn.apply(h, keep.transpose(1, 2).contiguous(), scale)
+
+    def head_train(self, h, valid8, control=1.0, target=None, bins=None, emb=None, x=None):
+        """-> pred, or (pred, x + emb[bucket]) with `emb`."""
+        return _VarianceHeadFn.apply(h, self.linear_layer.weight, self.linear_layer.bias, x, emb, valid8, control,
+                                     None if target is None else target.to(torch.float32).contiguous(), bins)
 
     def hidden_cm(self, x):
         """The conv stack on x [B, C, L] (pads are read as they are, like the reference) -> [B, filter, L]."""
@@ -260,6 +628,18 @@ class WordToPhonemeAttention(nn.Module):
         prior = None if attn_prior is None else attn_prior.to(torch.float32).contiguous()
         out, attn, raw, logp = w2p_attention(q, kv, key_valid8, query_valid8, mapping8, prior, self.n_head)
         y = ops.conv1d_packed(out, _packed(self.fc.linear.weight), None, D, 1, add=q_in)
+        return y, (attn, raw), logp
+
+    def forward_cm_train(self, q_in, kv_in, key_valid8, query_valid8, mapping8, attn_prior=None):
+        q = ag.conv1d(q_in, self.w_qs.linear.weight[:, :, None])
+        kv = ag.conv1d(kv_in, torch.cat([self.w_ks.linear.weight, self.w_vs.linear.weight])[:, :, None])
+        prior = None if attn_prior is None else attn_prior.to(torch.float32).contiguous()
+        if _grad():
+            out, attn, raw, logp = _W2PAttentionFn.apply(q, kv, key_valid8, query_valid8, mapping8, prior, self.n_head)
+        else:
+            out, attn, raw, logp = w2p_attention(q.contiguous(), kv.contiguous(), key_valid8, query_valid8, mapping8,
+                                                 prior, self.n_head)
+        y = _LinearAddFn.apply(out, self.fc.linear.weight, q_in)
         return y, (attn, raw), logp
 
 
@@ -340,9 +720,9 @@ class LinguisticEncoder(nn.Module):
                 max_len=None, attn_prior=None, pitch_target=None, energy_target=None, duration_target=None,
                 p_control=1.0, duration_control=1.0):
         if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(
-                "the native LinguisticEncoder is inference-only (eval() under torch.no_grad(), or parameters with "
-                "requires_grad=False): for training, inject the reference's model.linguistic_encoder.LinguisticEncoder")
+            return self._forward_train(src_p_seq, src_p_len, word_boundary, src_p_mask, src_w_len, src_w_mask,
+                                       mel_mask, max_len, attn_prior, pitch_target, energy_target, duration_target,
+                                       p_control, duration_control)
         if not src_p_seq.is_cuda:
             raise _lib.MixganHipError("LinguisticEncoder on %s: the HIP path has no CPU fallback" % src_p_seq.device)
         dev = src_p_seq.device
@@ -391,5 +771,68 @@ class LinguisticEncoder(nn.Module):
             q_in, kv_in, pv8, _u8(mel_mask), _u8(mapping),
             attn_prior if self.helper_type == "ctc" else None)
         out = ops.transpose_bml(y, True)
+        return (out, pitch_prediction, energy_prediction, log_duration_w_prediction, duration_w_rounded, mel_len,
+                mel_mask, attns, attn_logprob)
+
+    def _forward_train(self, src_p_seq, src_p_len, word_boundary, src_p_mask, src_w_len, src_w_mask, mel_mask=None,
+                       max_len=None, attn_prior=None, pitch_target=None, energy_target=None, duration_target=None,
+                       p_control=1.0, duration_control=1.0):
+        """The forward of model/linguistic_encoder.py:238-380 with autograd (grad enabled) and, in train mode,
+        dropout (eval mode with grad enabled runs it without dropout).  The order of the keep-mask requests is the reference's: phoneme encoder, pitch predictor, energy
+        predictor, word encoder, duration predictor."""
+        B, Tp = src_p_mask.shape
+        if Tp > self.max_seq_len:
+            raise ValueError("LinguisticEncoder training: %d phonemes exceed max_seq_len %d (the position-encoding "
+                             "tables have max_seq_len + 1 rows)" % (Tp, self.max_seq_len))
+        if not src_p_seq.is_cuda:
+            raise CpuTrainingError(
+                "LinguisticEncoder training on %s: the HIP path has no CPU fallback (move the inputs to the GPU, or "
+                "inject the reference's model.linguistic_encoder.LinguisticEncoder to train on the CPU)"
+                % src_p_seq.device)
+        dev = src_p_seq.device
+        W = src_w_mask.shape[1]
+        pv8, pp8 = _u8(src_p_mask), _u8(~src_p_mask.bool())
+        wv8, wp8 = _u8(src_w_mask), _u8(~src_w_mask.bool())
+        wb = word_boundary.to(torch.int64).contiguous()
+        src_w_len = src_w_len.to(torch.int64).contiguous()
+
+        ids = src_p_seq[:, :Tp].to(torch.int64).contiguous()
+        x = _EmbedFn.apply(self.src_emb.weight, ids, pv8, self.src_emb.padding_idx)
+        enc_p = self.phoneme_encoder.forward_cm_train(x, pv8, pp8)
+        pp, ep = self.pitch_predictor, self.energy_predictor
+        pitch_prediction, enc_p = pp.head_train(pp.hidden_cm_train(enc_p), pv8, p_control, pitch_target,
+                                                self.pitch_bins.detach(), self.pitch_embedding.weight, enc_p)
+        energy_prediction, enc_p = ep.head_train(ep.hidden_cm_train(enc_p), pv8, p_control, energy_target,
+                                                 self.energy_bins.detach(), self.energy_embedding.weight, enc_p)
+
+        enc_p_rm = ag.transpose_to_blm(enc_p)
+        src_w_seq = lingops.word_level_pooling(enc_p_rm, src_p_len, wb, src_w_len, "mean", max_words=W)
+        enc_w = self.word_encoder.forward_cm_train(_MaskedToCmFn.apply(src_w_seq, wv8), wv8, wp8)
+        enc_w_rm = ag.transpose_to_blm(enc_w)
+        if self.record:
+            self.recorded = {"enc_p_out": enc_p_rm, "enc_w_out": enc_w_rm}
+
+        dp = self.duration_predictor
+        log_d_p = dp.head_train(dp.hidden_cm_train(enc_p), pv8)
+        log_duration_w_prediction, duration_w_rounded = _DurationHeadFn.apply(
+            log_d_p, None if duration_target is None else duration_target.to(torch.int64).contiguous(), wb, src_w_len,
+            float(duration_control), W)
+        xr, mel_len = self.length_regulator(enc_w_rm, duration_w_rounded, max_len)
+        if duration_target is None:
+            ids_ = torch.arange(xr.shape[1], device=dev)
+            mel_mask = ids_[None, :] < mel_len[:, None]
+        Lq = xr.shape[1]
+        if Lq > self.max_seq_len:
+            raise ValueError("LinguisticEncoder training: %d frames exceed max_seq_len %d (the position-encoding "
+                             "tables have max_seq_len + 1 rows)" % (Lq, self.max_seq_len))
+
+        mapping = lingops.get_mapping_mask(xr, enc_p_rm, duration_w_rounded, wb, src_w_len)
+        coef_q = lingops.get_rel_coef(duration_w_rounded, src_w_len, mel_mask)
+        coef_kv = lingops.get_rel_coef(wb, src_p_len, src_p_mask)
+        q_in = _PosencAddFn.apply(xr, self.q_position_enc, True, coef_q)
+        kv_in = _PosencAddFn.apply(enc_p, self.kv_position_enc, False, coef_kv)
+        y, attns, attn_logprob = self.w2p_attn.forward_cm_train(
+            q_in, kv_in, pv8, _u8(mel_mask), _u8(mapping), attn_prior if self.helper_type == "ctc" else None)
+        out = ag.transpose_to_blm(y)
         return (out, pitch_prediction, energy_prediction, log_duration_w_prediction, duration_w_rounded, mel_len,
                 mel_mask, attns, attn_logprob)

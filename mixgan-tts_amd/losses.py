@@ -284,3 +284,99 @@ def get_mel_loss(mel_predictions, mel_targets, mel_masks_fill):
     """model/loss.py:229-242: masked_fill(pad, 0) on both, L1 weighted by non-zero target rows.
     mel_masks_fill: bool [B, L], True = pad."""
     return _MelL1Fn.apply(mel_predictions, mel_targets, mel_masks_fill)
+
+
+# --------------------------------------------------------------------------------------------------
+# the linguistic encoder's terms of recon_loss (model/loss.py:128-195): small masked means, a guided-attention mask
+# and a CTC dynamic program -- device-side torch, vectorised over the batch (no per-utterance host loop).
+# --------------------------------------------------------------------------------------------------
+def guided_attention_loss(att, ilens, olens, sigma, alpha):
+    """GuidedAttentionLoss (model/loss.py:261-352) on att [B, T_out, T_in]: alpha * mean over the valid (out, in)
+    cells of att * (1 - exp(-(in/ilen - out/olen)^2 / (2 sigma^2)))."""
+    B, To, Ti = att.shape
+    il = ilens.to(att.device, torch.float32)[:, None, None]
+    ol = olens.to(att.device, torch.float32)[:, None, None]
+    o = torch.arange(To, device=att.device, dtype=torch.float32)[None, :, None]
+    i = torch.arange(Ti, device=att.device, dtype=torch.float32)[None, None, :]
+    mask = (o < ol) & (i < il)
+    g = 1.0 - torch.exp(-((i / il - o / ol) ** 2) / (2 * sigma ** 2))
+    return alpha * (g * att).masked_select(mask).mean()
+
+
+def forward_sum_loss(attn_logprob, in_lens, out_lens, blank_logprob=-1.0):
+    """ForwardSumLoss (model/loss.py:420-447) on attn_logprob [B, 1, T_out, T_in]: a blank column of `blank_logprob`
+    in front, log_softmax over the first in_len + 1 columns, CTC against 1..in_len (zero_infinity, mean over the
+    target length), then the batch mean.  Columns past in_len + 1 are filled with -1e4 rather than cut (one batched
+    call): exp(-1e4 - max) is exactly 0 in fp32, so the value is the reference's, and unlike -inf the filler gives
+    the CTC backward finite gradients there (at -inf it returns NaN, which the log_softmax backward would spread over
+    the whole row).  The padded keys' -inf scores all lie in those columns."""
+    B, _, To, Ti = attn_logprob.shape
+    dev = attn_logprob.device
+    il = in_lens.to(dev, torch.int64)
+    ol = out_lens.to(dev, torch.int64)
+    lp = torch.nn.functional.pad(attn_logprob[:, 0], (1, 0), value=blank_logprob)          # [B, To, Ti + 1]
+    cols = torch.arange(Ti + 1, device=dev)
+    lp = lp.masked_fill(cols[None, None, :] > il[:, None, None], -1e4)
+    lp = torch.log_softmax(lp, -1).transpose(0, 1)                                       # [To, B, Ti + 1]
+    targets = (torch.arange(1, Ti + 1, device=dev)[None, :].expand(B, Ti) * (cols[None, 1:] <= il[:, None]))
+    per = torch.nn.functional.ctc_loss(lp, targets, ol, il, blank=0, reduction="none", zero_infinity=True)
+    return (per / il.clamp(min=1).to(per.dtype)).mean()
+
+
+class LinguisticEncoderLoss:
+    """model/loss.py:128-195's linguistic-encoder terms: lambda_d * duration + lambda_p * pitch + lambda_e * energy +
+    helper (dga: guided attention on alignments[1], one term per head; ctc: the forward-sum loss per head, weight
+    switched at ctc_step).  Zero for `shallow`.  Callable as `upstream_loss(batch, output, step)` of
+    HotPathTrainer.step_from_model; `terms(...)` returns every term for logging, and the last call's terms stay in
+    `self.last`."""
+
+    def __init__(self, preprocess_config, model_config, train_config, model="naive"):
+        for lvl in (preprocess_config["preprocessing"]["pitch"]["feature"],
+                    preprocess_config["preprocessing"]["energy"]["feature"]):
+            if lvl != "phoneme_level":
+                raise NotImplementedError("LinguisticEncoderLoss: phoneme_level pitch / energy only")
+        self.model = model
+        lc = train_config["loss"]
+        self.lambda_d, self.lambda_p, self.lambda_e = lc["lambda_d"], lc["lambda_p"], lc["lambda_e"]
+        al = train_config["aligner"]
+        self.helper_type = al["helper_type"]
+        if self.helper_type == "dga":
+            self.guided_sigma, self.guided_lambda = al["guided_sigma"], al["guided_lambda"]
+            self.guided_weight = al["guided_weight"]
+        elif self.helper_type == "ctc":
+            self.ctc_step = train_config["step"]["ctc_step"]
+            self.ctc_weight_start, self.ctc_weight_end = al["ctc_weight_start"], al["ctc_weight_end"]
+        self.last = None
+
+    def terms(self, batch, output, step):
+        """batch: the reference's batch list (pitch / energy targets at 14 / 15); output: MixGANTTS.forward's 16 slots."""
+        p_pred, e_pred, logd_pred, d_rounded = output[4], output[5], output[6], output[7]
+        src_masks, src_lens, mel_lens = output[8], output[10], output[11]
+        alignments, logprobs, src_w_masks = output[12], output[13], output[14]
+        dev = logd_pred.device
+        zero = torch.zeros((), device=dev)
+        t = {"duration_loss": zero, "pitch_loss": zero, "energy_loss": zero, "helper_loss": zero}
+        if self.model != "shallow":
+            mse = torch.nn.functional.mse_loss
+            logd_tgt = torch.log(d_rounded.float() + 1)
+            t["duration_loss"] = mse(logd_pred.masked_select(src_w_masks), logd_tgt.masked_select(src_w_masks))
+            t["pitch_loss"] = mse(p_pred.masked_select(src_masks), batch[14].to(dev).masked_select(src_masks))
+            t["energy_loss"] = mse(e_pred.masked_select(src_masks), batch[15].to(dev).masked_select(src_masks))
+            if self.helper_type == "dga":
+                attn = sum(guided_attention_loss(a, src_lens, mel_lens, self.guided_sigma, self.guided_lambda)
+                           for a in alignments[1])
+                t["attn_loss"] = attn
+                t["helper_loss"] = self.guided_weight * attn
+            elif self.helper_type == "ctc":
+                ctc = sum(forward_sum_loss(lp, src_lens, mel_lens) for lp in logprobs)
+                t["ctc_loss"] = ctc
+                w = self.ctc_weight_start if step <= self.ctc_step else self.ctc_weight_end
+                t["helper_loss"] = w * ctc
+        t["total"] = (self.lambda_d * t["duration_loss"] + self.lambda_p * t["pitch_loss"] +
+                      self.lambda_e * t["energy_loss"] + t["helper_loss"])
+        return t
+
+    def __call__(self, batch, output, step):
+        t = self.terms(batch, output, step)
+        self.last = {k: v.detach() for k, v in t.items()}
+        return t["total"]

@@ -1,9 +1,9 @@
 """MixGANTTS.forward orchestration (model/mixgantts.py:16-183) around the HIP path.
 
 The linguistic encoder is either injected (`linguistic_encoder=`, any module with the reference's call
-signature, model/linguistic_encoder.py:238-380, e.g. the reference's own one for training) or, with
-`linguistic_encoder="native"`, the inference-only HIP LinguisticEncoder of linguistic_encoder.py, which
-makes phoneme ids -> mel run on this package alone.  Everything downstream of it -- FFT decoder /
+signature, model/linguistic_encoder.py:238-380, e.g. the reference's own one) or, with
+`linguistic_encoder="native"`, the HIP LinguisticEncoder of linguistic_encoder.py (inference and training), which
+makes phoneme ids -> mel, and the train.py step, run on this package alone.  Everything downstream of it -- FFT decoder /
 mel_linear / PostNet for aux|shallow, GaussianDiffusion -- is ours.  The 16-slot output list, `p_targets` and `coarse_mels` are laid out exactly as the reference
 returns them (consumed positionally by train.py / evaluate.py / synthesize.py / model/loss.py).
 """
@@ -77,8 +77,8 @@ class MixGANTTS(nn.Module):
                 speak_embeds=None, attn_priors=None, mels=None, mel_lens=None, max_mel_len=None, p_targets=None,
                 e_targets=None, d_targets=None, spker_embeds=None, p_control=1.0, e_control=1.0, d_control=1.0):
         if not hasattr(self, "linguistic_encoder"):
-            raise RuntimeError("MixGANTTS needs a linguistic_encoder: pass linguistic_encoder='native' (inference) or "
-                               "the reference's model.linguistic_encoder.LinguisticEncoder instance (training)")
+            raise RuntimeError("MixGANTTS needs a linguistic_encoder: pass linguistic_encoder='native' or a module "
+                               "with the reference's call signature")
         src_masks = get_mask_from_lengths(src_lens, max_src_len)
         src_w_masks = get_mask_from_lengths(src_w_lens, max_src_w_len)
         mel_masks = get_mask_from_lengths(mel_lens, max_mel_len) if mel_lens is not None else None

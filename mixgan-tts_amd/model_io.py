@@ -6,7 +6,7 @@ Checkpoint format (unchanged): `<train_config.path.ckpt_path>/<step>.pth.tar`, a
 file only holds tensors and plain containers, and nothing in it is ever executed.
 
 The linguistic encoder is injected (`linguistic_encoder=` a module) or native (`linguistic_encoder="native"`, the
-inference-only HIP encoder of linguistic_encoder.py): with either the generator's state dict has the reference's full
+HIP encoder of linguistic_encoder.py, which also trains): with either the generator's state dict has the reference's full
 key set and `G` loads strictly; without one only the keys of the modules on the HIP path are restored (and the call
 says which were skipped).
 """

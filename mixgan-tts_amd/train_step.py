@@ -273,7 +273,7 @@ class HotPathTrainer:
         `model(*(batch[2:]))` again for the G phase (a train-mode encoder gives a different conditioner and consumes
         its random draws between the two sets of diffusion draws, exactly as in the reference), `batch[9] = p_targets`,
         G update.  upstream_loss(batch, output, step_no) -> tensor | None supplies model/loss.py:195's duration / pitch /
-        energy / helper terms of the (out-of-scope) linguistic encoder.
+        energy / helper terms of the linguistic encoder (losses.LinguisticEncoderLoss for the native one).
         pair=True launches both generator forwards together: the encoder then runs twice up front, which moves its
         second-pass draws ahead of the first diffusion draws (statistically the same step, not draw-for-draw)."""
         if getattr(model, "diffusion", None) is not self.G:
