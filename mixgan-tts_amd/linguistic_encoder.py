@@ -3,12 +3,15 @@
 Same class names, constructor arguments, forward signature (14 arguments, nine outputs) and state_dict keys,
 shapes and order as the reference, so a reference checkpoint loads with strict=True.
 
-Three forwards: eval (no_grad, the inference kernels only); train mode with grad (every op a torch.autograd.Function
-whose forward and backward are library calls: lingenc_train.hip for the two attentions and the per-token glue, the
-conv / LayerNorm / word-pooling / length-regulator Functions otherwise); and train mode under no_grad (the D phase of
-a training step: the same kernels and dropout, nothing saved).  Dropout keep-masks come from transformer._keep_mask
-(so DROPOUT_FN / a module's `dropout_fn` can replay the reference's), requested in the reference's call order and
-with its shapes; where the native layout differs the mask is transposed here.
+One forward per module, run in the mode LinguisticEncoder.forward chooses once per call; each op picks its kernel or
+autograd Function for the mode in one place (_conv, _block_norm, _rel_attention, ...).  _INFER (eval mode, unless
+grad is enabled and a parameter requires it): the inference kernels only.  _RECORD (any other call with grad
+enabled): every op a torch.autograd.Function whose forward and backward are library calls (lingenc_train.hip for the
+two attentions and the per-token glue, the conv / LayerNorm / word-pooling / length-regulator Functions otherwise),
+with dropout in train mode and p = 0 in eval mode.  _NOGRAD (train mode under no_grad, the D phase of a training
+step): the same kernels and dropout, nothing saved.  Dropout keep-masks come from transformer._keep_mask (so
+DROPOUT_FN / a module's `dropout_fn` can replay the reference's), requested in the reference's call order and with
+its shapes; where the native layout differs the mask is transposed here.
 
 Internally everything is channel-major [B, C, L] like transformer.py's forward_cm: k=1 / k=3 / k=9 convolutions
 are the generic conv kernel, LayerNorms are mg_layernorm_cm_fwd, the two attentions and the per-token glue
@@ -400,18 +403,75 @@ class CpuTrainingError(_lib.MixganHipError, NotImplementedError):
     error (no CPU fallback) and NotImplementedError (the native encoder does not train on the CPU)."""
 
 
-def _grad():
-    return torch.is_grad_enabled()
+# ------------------------------------------------------------------------------------ per-op choice by mode
+_INFER, _RECORD, _NOGRAD = "infer", "record", "no_grad"
 
 
-def _p(module, p):
-    """Dropout probability of `module` now: p in train mode, 0 in eval mode (an eval forward with grad enabled)."""
-    return p if module.training else 0.0
+def _stack(ts):
+    return ts[0] if len(ts) == 1 else torch.cat(ts)
 
 
 def _packed(*weights):
-    """k=1 weights [Co, Ci] stacked along Co, packed once per parameter version."""
+    """Inference pack of `weights` stacked along Co (k=1 ones may be [Co, Ci]), each packed once per parameter
+    version; a single Conv1d weight's pack is used as it is."""
+    if len(weights) == 1 and weights[0].dim() == 3:
+        return ops.pack_cached(weights[0])
     return torch.cat([ops.pack_cached(w[:, :, None] if w.dim() == 2 else w) for w in weights])
+
+
+def _keep(mode, module, shape, p, device):
+    """Keep-mask and scale of `module`'s dropout(p): none in inference, p = 0 in eval mode (grad enabled)."""
+    if mode == _INFER:
+        return None, 1.0
+    return _keep_mask(module, tuple(shape), p if module.training else 0.0, device)
+
+
+def _conv(mode, x, weights, biases=(), padding=0, act=None, add=None):
+    """Stride-1 convolution of x [B, Ci, L] by `weights` (Conv1d [Co, Ci, k] or k=1 Linear [Co, Ci]) stacked along Co
+    plus their stacked `biases`, then `act`; `add` (one bias-free k=1 weight) is a residual added in the epilogue.
+    Inference: the conv kernel on the cached packs, no split.  Training: ag.conv1d (split reduction), or _LinearAddFn
+    with `add`."""
+    w = weights[0]
+    if mode == _INFER:
+        packed = _packed(*weights)
+        b = _stack(biases).detach() if biases else None
+        return ops.conv1d_packed(x, packed, b, w.shape[0] * len(weights), w.shape[2] if w.dim() == 3 else 1, 1,
+                                 padding, act, add=add)
+    if add is not None:
+        return _LinearAddFn.apply(x, w, add)
+    w = _stack(weights)
+    return ag.conv1d(x, w if w.dim() == 3 else w[:, :, None], _stack(biases) if biases else None, 1, padding, act)
+
+
+def _block_norm(mode, y, x, norm, pad8, keep, scale):
+    """LayerNorm(dropout(y) + x) of a RelativeFFTBlock, pads zeroed."""
+    if mode == _INFER:
+        return ops.layernorm_cm(y, x, norm.gamma.detach(), norm.beta.detach(), pad8, norm.eps)
+    return ag.layernorm_train(y, x, norm.gamma, norm.beta, pad8, keep, scale, norm.eps)
+
+
+def _norm_drop(mode, module, h, norm):
+    """dropout(nn.LayerNorm(h)) of a VariancePredictor; the keep-mask is drawn [B, L, F] (the reference's channel-last
+    layout) and transposed."""
+    if mode == _INFER:
+        return ops.layernorm_cm(h, None, norm.weight.detach(), norm.bias.detach(), None, norm.eps)
+    h = _LayerNormFn.apply(h, norm.weight, norm.bias, norm.eps)
+    B, F, L = h.shape
+    keep, scale = _keep(mode, module, (B, L, F), module.dropout_p, h.device)
+    return h if keep is None else _DropoutFn.apply(h, keep.transpose(1, 2).contiguous(), scale)
+
+
+def _rel_attention(mode, qkv, valid8, emb_k, emb_v, keep, scale, n_head, window):
+    if mode == _INFER:
+        return rel_attention(qkv, valid8, emb_k.detach(), emb_v.detach(), n_head, window)
+    if mode == _RECORD:
+        return _RelAttentionFn.apply(qkv, emb_k, emb_v, valid8, keep, scale, n_head, window)
+    return rel_attention_train(qkv, valid8, emb_k, emb_v, n_head, window, keep, scale, save=False)[0]
+
+
+def _to_rm(mode, x):
+    """[B, C, L] -> [B, L, C]."""
+    return ops.transpose_bml(x, True) if mode == _INFER else ag.transpose_to_blm(x)
 
 
 # ------------------------------------------------------------------------------------ modules
@@ -452,29 +512,15 @@ class RelativeSelfAttention(nn.Module):
         self.conv_o = _Conv1d(channels, out_channels, 1)
         self.p_dropout = p_dropout
 
-    def forward_cm_train(self, x, valid8):
-        """Train mode: returns conv_o(attention with dropout on p_attn) (before the block's drop(y))."""
+    def forward_cm(self, x, valid8, mode):
+        """conv_o(attention, with dropout on p_attn in training) (before the block's drop(y))."""
         B, C, L = x.shape
-        keep, scale = _keep_mask(self, (B, self.n_heads, L, L), _p(self, self.p_dropout), x.device)
-        w = torch.cat([self.conv_q.weight, self.conv_k.weight, self.conv_v.weight])
-        b = torch.cat([self.conv_q.bias, self.conv_k.bias, self.conv_v.bias])
-        qkv = ag.conv1d(x, w, b)
-        if _grad():
-            att = _RelAttentionFn.apply(qkv, self.emb_rel_k[0], self.emb_rel_v[0], valid8, keep, scale, self.n_heads,
-                                        self.window_size)
-        else:
-            att, _ = rel_attention_train(qkv, valid8, self.emb_rel_k[0], self.emb_rel_v[0], self.n_heads,
-                                         self.window_size, keep, scale, save=False)
-        return ag.conv1d(att, self.conv_o.weight, self.conv_o.bias)
-
-    def forward_cm(self, x, valid8):
-        C = self.channels
-        qkv = ops.conv1d_packed(x, _packed(self.conv_q.weight, self.conv_k.weight, self.conv_v.weight),
-                                torch.cat([self.conv_q.bias, self.conv_k.bias, self.conv_v.bias]).detach(), 3 * C, 1)
-        att = rel_attention(qkv, valid8, self.emb_rel_k.detach()[0], self.emb_rel_v.detach()[0], self.n_heads,
-                            self.window_size)
-        return ops.conv1d_packed(att, ops.pack_cached(self.conv_o.weight), self.conv_o.bias.detach(),
-                                 self.conv_o.weight.shape[0], 1)
+        keep, scale = _keep(mode, self, (B, self.n_heads, L, L), self.p_dropout, x.device)
+        qkv = _conv(mode, x, (self.conv_q.weight, self.conv_k.weight, self.conv_v.weight),
+                    (self.conv_q.bias, self.conv_k.bias, self.conv_v.bias))
+        att = _rel_attention(mode, qkv, valid8, self.emb_rel_k[0], self.emb_rel_v[0], keep, scale, self.n_heads,
+                             self.window_size)
+        return _conv(mode, att, (self.conv_o.weight,), (self.conv_o.bias,))
 
 
 class FFN(nn.Module):
@@ -488,10 +534,8 @@ class FFN(nn.Module):
         self.p_dropout = p_dropout
         self.conv = _Conv1d(in_channels, out_channels, kernel_size)
 
-    def forward_cm(self, x):
-        k = self.kernel_size
-        return ops.conv1d_packed(x, ops.pack_cached(self.conv.weight), self.conv.bias.detach(),
-                                 self.conv.weight.shape[0], k, 1, k // 2, "relu")
+    def forward_cm(self, x, mode):
+        return _conv(mode, x, (self.conv.weight,), (self.conv.bias,), self.kernel_size // 2, "relu")
 
 
 class RelativeFFTBlock(nn.Module):
@@ -513,40 +557,28 @@ class RelativeFFTBlock(nn.Module):
             self.ffn_layers.append(FFN(hidden_channels, hidden_channels, kernel_size, p_dropout=p_dropout))
             self.norm_layers_2.append(LayerNorm(hidden_channels))
 
-    def forward_cm(self, x, valid8, pad8):
+    def forward_cm(self, x, valid8, pad8, mode):
         """x [B, C, L] with zeros at the pads -> the block's output (zeros at the pads).
 
         The reference masks x at the top of every layer, the FFN's input and output, and the block's output.  Every
         LayerNorm here zeroes its padded frames instead: a frame's LayerNorm reads only that frame, the convolutions
         and the attention read the pads only through those masks, so the valid frames and the (zero) pads of the
-        block's output are the reference's."""
-        for i in range(self.n_layers):
-            n1, n2 = self.norm_layers_1[i], self.norm_layers_2[i]
-            y = self.attn_layers[i].forward_cm(x, valid8)
-            x = ops.layernorm_cm(y, x, n1.gamma.detach(), n1.beta.detach(), pad8, n1.eps)
-            y = self.ffn_layers[i].forward_cm(x)
-            x = ops.layernorm_cm(y, x, n2.gamma.detach(), n2.beta.detach(), pad8, n2.eps)
-        return x
+        block's output are the reference's.
 
-    def forward_cm_train(self, x, valid8, pad8):
-        """Train mode (model/blocks.py:941-954): per layer the keep-masks of p_attn, drop(y) after the attention, the
-        FFN's inner drop and drop(y) after the FFN, in that order.  The FFN's two dropouts act on the same tensor one
-        after the other, so they enter the LayerNorm kernel as one mask (keep1 * keep2, scale1 * scale2)."""
+        In training (model/blocks.py:941-954) the keep-masks are requested per layer in the reference's order: p_attn,
+        drop(y) after the attention, the FFN's inner drop and drop(y) after the FFN.  The FFN's two dropouts act on the
+        same tensor one after the other, so they enter the LayerNorm kernel as one mask (keep1 * keep2, s1 * s2)."""
         for i in range(self.n_layers):
-            n1, n2 = self.norm_layers_1[i], self.norm_layers_2[i]
-            ffn = self.ffn_layers[i]
-            y = self.attn_layers[i].forward_cm_train(x, valid8)
-            keep, scale = _keep_mask(self, tuple(y.shape), _p(self, self.p_dropout), y.device)
-            x = ag.layernorm_train(y, x, n1.gamma, n1.beta, pad8, keep, scale, n1.eps)
-            k = ffn.kernel_size
-            y = ag.conv1d(x, ffn.conv.weight, ffn.conv.bias, 1, k // 2, "relu")
-            keep1, s1 = _keep_mask(ffn, tuple(y.shape), _p(ffn, ffn.p_dropout), y.device)
-            keep2, s2 = _keep_mask(self, tuple(y.shape), _p(self, self.p_dropout), y.device)
+            n1, n2, ffn = self.norm_layers_1[i], self.norm_layers_2[i], self.ffn_layers[i]
+            y = self.attn_layers[i].forward_cm(x, valid8, mode)
+            keep, scale = _keep(mode, self, y.shape, self.p_dropout, y.device)
+            x = _block_norm(mode, y, x, n1, pad8, keep, scale)
+            y = ffn.forward_cm(x, mode)
+            keep1, s1 = _keep(mode, ffn, y.shape, ffn.p_dropout, y.device)
+            keep2, s2 = _keep(mode, self, y.shape, self.p_dropout, y.device)
             if keep1 is not None and keep2 is not None:
-                keep, scale = (keep1 & keep2).contiguous(), s1 * s2
-            else:
-                keep, scale = (keep1 if keep1 is not None else keep2), s1 * s2
-            x = ag.layernorm_train(y, x, n2.gamma, n2.beta, pad8, keep, scale, n2.eps)
+                keep1, keep2 = (keep1 & keep2).contiguous(), None
+            x = _block_norm(mode, y, x, n2, pad8, keep1 if keep1 is not None else keep2, s1 * s2)
         return x
 
 
@@ -569,42 +601,24 @@ class VariancePredictor(nn.Module):
         self.linear_layer = nn.Linear(self.conv_output_size, 1)
         self.dropout_p = model_config["variance_predictor"]["dropout"]
 
-    def hidden_cm_train(self, x):
-        """Train mode: (conv -> ReLU -> LayerNorm -> dropout) x 2; the keep-masks are drawn [B, L, F] (the reference's
-        channel-last layout) and transposed."""
-        c1, c2 = self.conv_layer.conv1d_1, self.conv_layer.conv1d_2
-        n1, n2 = self.conv_layer.layer_norm_1, self.conv_layer.layer_norm_2
-        h = ag.conv1d(x, c1.conv.weight, c1.conv.bias, 1, (self.kernel - 1) // 2, "relu")
-        h = self._drop(_LayerNormFn.apply(h, n1.weight, n1.bias, n1.eps))
-        h = ag.conv1d(h, c2.conv.weight, c2.conv.bias, 1, 1, "relu")
-        return self._drop(_LayerNormFn.apply(h, n2.weight, n2.bias, n2.eps))
+    def hidden_cm(self, x, mode):
+        """(conv -> ReLU -> LayerNorm -> dropout in training) x 2 on x [B, C, L] (pads are read as they are, like the
+        reference) -> [B, filter, L]."""
+        cl = self.conv_layer
+        for conv, norm in ((cl.conv1d_1, cl.layer_norm_1), (cl.conv1d_2, cl.layer_norm_2)):
+            x = _conv(mode, x, (conv.conv.weight,), (conv.conv.bias,), conv.padding, "relu")
+            x = _norm_drop(mode, self, x, norm)
+        return x
 
-    def _drop(self, h):
-        B, F, L = h.shape
-        keep, scale = _keep_mask(self, (B, L, F), _p(self, self.dropout_p), h.device)
-        if keep is None:
-            return h
-        return _DropoutFn.apply(h, keep.transpose(1, 2).contiguous(), scale)
-
-    def head_train(self, h, valid8, control=1.0, target=None, bins=None, emb=None, x=None):
-        """-> pred, or (pred, x + emb[bucket]) with `emb`."""
-        return _VarianceHeadFn.apply(h, self.linear_layer.weight, self.linear_layer.bias, x, emb, valid8, control,
+    def head(self, h, valid8, mode, control=1.0, target=None, bins=None, emb=None, x=None):
+        """-> pred, or (pred, x + emb[bucket]) with `emb`: inference adds into x in place, training into a copy."""
+        lin = self.linear_layer
+        if mode == _INFER:
+            pred = variance_head(h, lin.weight.detach(), lin.bias.detach(), valid8, control, target, bins,
+                                 None if emb is None else emb.detach(), x)
+            return pred if emb is None else (pred, x)
+        return _VarianceHeadFn.apply(h, lin.weight, lin.bias, x, emb, valid8, control,
                                      None if target is None else target.to(torch.float32).contiguous(), bins)
-
-    def hidden_cm(self, x):
-        """The conv stack on x [B, C, L] (pads are read as they are, like the reference) -> [B, filter, L]."""
-        c1, c2 = self.conv_layer.conv1d_1, self.conv_layer.conv1d_2
-        n1, n2 = self.conv_layer.layer_norm_1, self.conv_layer.layer_norm_2
-        F = self.filter_size
-        h = ops.conv1d_packed(x, ops.pack_cached(c1.conv.weight), c1.conv.bias.detach(), F, self.kernel, 1,
-                              (self.kernel - 1) // 2, "relu")
-        h = ops.layernorm_cm(h, None, n1.weight.detach(), n1.bias.detach(), None, n1.eps)
-        h = ops.conv1d_packed(h, ops.pack_cached(c2.conv.weight), c2.conv.bias.detach(), F, self.kernel, 1, 1, "relu")
-        return ops.layernorm_cm(h, None, n2.weight.detach(), n2.bias.detach(), None, n2.eps)
-
-    def head(self, h, valid8, control=1.0, target=None, bins=None, emb=None, x=None):
-        return variance_head(h, self.linear_layer.weight.detach(), self.linear_layer.bias.detach(), valid8, control,
-                             target, bins, emb, x)
 
 
 class WordToPhonemeAttention(nn.Module):
@@ -618,33 +632,20 @@ class WordToPhonemeAttention(nn.Module):
         self.w_vs = LinearNorm(d_model, n_head * d_v)
         self.fc = LinearNorm(n_head * d_v, d_model)
 
-    def forward_cm(self, q_in, kv_in, key_valid8, query_valid8, mapping8, attn_prior=None):
+    def forward_cm(self, q_in, kv_in, key_valid8, query_valid8, mapping8, attn_prior, mode):
         """q_in [B, D, Lq], kv_in [B, D, Lk] (k and v are the same tensor in the encoder) ->
         (fc(attention) + q_in [B, D, Lq], (attn, attn_raw) [H, B, Lq, Lk], attn_logprob [H, B, 1, Lq, Lk])."""
-        HD = self.n_head * self.d_k
-        D = self.fc.linear.weight.shape[0]
-        q = ops.conv1d_packed(q_in, _packed(self.w_qs.linear.weight), None, HD, 1)
-        kv = ops.conv1d_packed(kv_in, _packed(self.w_ks.linear.weight, self.w_vs.linear.weight), None, 2 * HD, 1)
+        q = _conv(mode, q_in, (self.w_qs.linear.weight,))
+        kv = _conv(mode, kv_in, (self.w_ks.linear.weight, self.w_vs.linear.weight))
         prior = None if attn_prior is None else attn_prior.to(torch.float32).contiguous()
-        out, attn, raw, logp = w2p_attention(q, kv, key_valid8, query_valid8, mapping8, prior, self.n_head)
-        y = ops.conv1d_packed(out, _packed(self.fc.linear.weight), None, D, 1, add=q_in)
-        return y, (attn, raw), logp
-
-    def forward_cm_train(self, q_in, kv_in, key_valid8, query_valid8, mapping8, attn_prior=None):
-        q = ag.conv1d(q_in, self.w_qs.linear.weight[:, :, None])
-        kv = ag.conv1d(kv_in, torch.cat([self.w_ks.linear.weight, self.w_vs.linear.weight])[:, :, None])
-        prior = None if attn_prior is None else attn_prior.to(torch.float32).contiguous()
-        if _grad():
-            out, attn, raw, logp = _W2PAttentionFn.apply(q, kv, key_valid8, query_valid8, mapping8, prior, self.n_head)
-        else:
-            out, attn, raw, logp = w2p_attention(q.contiguous(), kv.contiguous(), key_valid8, query_valid8, mapping8,
-                                                 prior, self.n_head)
-        y = _LinearAddFn.apply(out, self.fc.linear.weight, q_in)
+        attend = _W2PAttentionFn.apply if mode == _RECORD else w2p_attention
+        out, attn, raw, logp = attend(q, kv, key_valid8, query_valid8, mapping8, prior, self.n_head)
+        y = _conv(mode, out, (self.fc.linear.weight,), add=q_in)
         return y, (attn, raw), logp
 
 
 class LinguisticEncoder(nn.Module):
-    """model/linguistic_encoder.py:41-380, inference."""
+    """model/linguistic_encoder.py:41-380."""
 
     def __init__(self, preprocess_config, model_config, train_config):
         super().__init__()
@@ -716,75 +717,34 @@ class LinguisticEncoder(nn.Module):
             return t
         return position_enc.detach()[0]
 
+    def _posenc(self, x, rowmajor, coef, position_enc, mode):
+        """x + coef * position_enc -> [B, C, L]; training has no table past max_seq_len (_check_len)."""
+        if mode == _INFER:
+            L = x.shape[1] if rowmajor else x.shape[2]
+            return posenc_add(x, rowmajor, coef, self._table(position_enc, L, x.device))
+        return _PosencAddFn.apply(x, position_enc, rowmajor, coef)
+
+    def _check_len(self, n, what):
+        if n > self.max_seq_len:
+            raise ValueError("LinguisticEncoder training: %d %s exceed max_seq_len %d (the position-encoding tables "
+                             "have max_seq_len + 1 rows)" % (n, what, self.max_seq_len))
+
     def forward(self, src_p_seq, src_p_len, word_boundary, src_p_mask, src_w_len, src_w_mask, mel_mask=None,
                 max_len=None, attn_prior=None, pitch_target=None, energy_target=None, duration_target=None,
                 p_control=1.0, duration_control=1.0):
-        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
-            return self._forward_train(src_p_seq, src_p_len, word_boundary, src_p_mask, src_w_len, src_w_mask,
-                                       mel_mask, max_len, attn_prior, pitch_target, energy_target, duration_target,
-                                       p_control, duration_control)
-        if not src_p_seq.is_cuda:
-            raise _lib.MixganHipError("LinguisticEncoder on %s: the HIP path has no CPU fallback" % src_p_seq.device)
-        dev = src_p_seq.device
+        """model/linguistic_encoder.py:238-380 in the mode of this call (module docstring).  In training the keep-masks
+        are requested in the reference's order: phoneme encoder, pitch predictor, energy predictor, word encoder,
+        duration predictor."""
+        grad = torch.is_grad_enabled()
+        train = self.training or (grad and any(p.requires_grad for p in self.parameters()))
+        mode = (_RECORD if grad else _NOGRAD) if train else _INFER
         B, Tp = src_p_mask.shape
-        W = src_w_mask.shape[1]
-        pv8, pp8 = _u8(src_p_mask), _u8(~src_p_mask.bool())
-        wv8, wp8 = _u8(src_w_mask), _u8(~src_w_mask.bool())
-        wb = word_boundary.to(torch.int64).contiguous()
-        src_w_len = src_w_len.to(torch.int64).contiguous()
-
-        # phoneme encoder (:318-320), pitch / energy embeddings added at every phoneme, pads included (:322-333)
-        x = embed_cm(src_p_seq[:, :Tp], self.src_emb.weight.detach(), pv8)
-        enc_p = self.phoneme_encoder.forward_cm(x, pv8, pp8)
-        pitch_prediction = self.pitch_predictor.head(
-            self.pitch_predictor.hidden_cm(enc_p), pv8, p_control, pitch_target, self.pitch_bins.detach(),
-            self.pitch_embedding.weight.detach(), enc_p)
-        energy_prediction = self.energy_predictor.head(
-            self.energy_predictor.hidden_cm(enc_p), pv8, p_control, energy_target, self.energy_bins.detach(),
-            self.energy_embedding.weight.detach(), enc_p)
-
-        # word pooling -> word encoder (:347-353)
-        enc_p_rm = ops.transpose_bml(enc_p, True)
-        src_w_seq = lingops.word_level_pooling(enc_p_rm, src_p_len, wb, src_w_len, "mean", max_words=W)
-        enc_w = self.word_encoder.forward_cm(ops.transpose_bml(src_w_seq, False, keep=wv8), wv8, wp8)
-        enc_w_rm = ops.transpose_bml(enc_w, True)
-        if self.record:
-            self.recorded = {"enc_p_out": enc_p_rm, "enc_w_out": enc_w_rm}
-
-        # durations (:355-376)
-        log_d_p = self.duration_predictor.head(self.duration_predictor.hidden_cm(enc_p), pv8)
-        log_duration_w_prediction, duration_w_rounded = duration_head(
-            log_d_p, duration_target, wb, src_w_len, duration_control, W)
-        xr, mel_len = self.length_regulator(enc_w_rm, duration_w_rounded, max_len)
-        if duration_target is None:
-            ids = torch.arange(xr.shape[1], device=dev)
-            mel_mask = ids[None, :] < mel_len[:, None]
-        Lq = xr.shape[1]
-
-        # word-to-phoneme attention (:378-407); k and v share one input, and their rel coefficients are one tensor
-        mapping = lingops.get_mapping_mask(xr, enc_p_rm, duration_w_rounded, wb, src_w_len)
-        coef_q = lingops.get_rel_coef(duration_w_rounded, src_w_len, mel_mask)
-        coef_kv = lingops.get_rel_coef(wb, src_p_len, src_p_mask)
-        q_in = posenc_add(xr, True, coef_q, self._table(self.q_position_enc, Lq, dev))
-        kv_in = posenc_add(enc_p, False, coef_kv, self._table(self.kv_position_enc, Tp, dev))
-        y, attns, attn_logprob = self.w2p_attn.forward_cm(
-            q_in, kv_in, pv8, _u8(mel_mask), _u8(mapping),
-            attn_prior if self.helper_type == "ctc" else None)
-        out = ops.transpose_bml(y, True)
-        return (out, pitch_prediction, energy_prediction, log_duration_w_prediction, duration_w_rounded, mel_len,
-                mel_mask, attns, attn_logprob)
-
-    def _forward_train(self, src_p_seq, src_p_len, word_boundary, src_p_mask, src_w_len, src_w_mask, mel_mask=None,
-                       max_len=None, attn_prior=None, pitch_target=None, energy_target=None, duration_target=None,
-                       p_control=1.0, duration_control=1.0):
-        """The forward of model/linguistic_encoder.py:238-380 with autograd (grad enabled) and, in train mode,
-        dropout (eval mode with grad enabled runs it without dropout).  The order of the keep-mask requests is the reference's: phoneme encoder, pitch predictor, energy
-        predictor, word encoder, duration predictor."""
-        B, Tp = src_p_mask.shape
-        if Tp > self.max_seq_len:
-            raise ValueError("LinguisticEncoder training: %d phonemes exceed max_seq_len %d (the position-encoding "
-                             "tables have max_seq_len + 1 rows)" % (Tp, self.max_seq_len))
+        if mode != _INFER:
+            self._check_len(Tp, "phonemes")
         if not src_p_seq.is_cuda:
+            if mode == _INFER:
+                raise _lib.MixganHipError("LinguisticEncoder on %s: the HIP path has no CPU fallback"
+                                          % src_p_seq.device)
             raise CpuTrainingError(
                 "LinguisticEncoder training on %s: the HIP path has no CPU fallback (move the inputs to the GPU, or "
                 "inject the reference's model.linguistic_encoder.LinguisticEncoder to train on the CPU)"
@@ -796,43 +756,51 @@ class LinguisticEncoder(nn.Module):
         wb = word_boundary.to(torch.int64).contiguous()
         src_w_len = src_w_len.to(torch.int64).contiguous()
 
-        ids = src_p_seq[:, :Tp].to(torch.int64).contiguous()
-        x = _EmbedFn.apply(self.src_emb.weight, ids, pv8, self.src_emb.padding_idx)
-        enc_p = self.phoneme_encoder.forward_cm_train(x, pv8, pp8)
+        # phoneme encoder (:318-320), pitch / energy embeddings added at every phoneme, pads included (:322-333)
+        if mode == _INFER:
+            x = embed_cm(src_p_seq[:, :Tp], self.src_emb.weight.detach(), pv8)
+        else:
+            x = _EmbedFn.apply(self.src_emb.weight, src_p_seq[:, :Tp].to(torch.int64).contiguous(), pv8,
+                               self.src_emb.padding_idx)
+        enc_p = self.phoneme_encoder.forward_cm(x, pv8, pp8, mode)
         pp, ep = self.pitch_predictor, self.energy_predictor
-        pitch_prediction, enc_p = pp.head_train(pp.hidden_cm_train(enc_p), pv8, p_control, pitch_target,
-                                                self.pitch_bins.detach(), self.pitch_embedding.weight, enc_p)
-        energy_prediction, enc_p = ep.head_train(ep.hidden_cm_train(enc_p), pv8, p_control, energy_target,
-                                                 self.energy_bins.detach(), self.energy_embedding.weight, enc_p)
+        pitch_prediction, enc_p = pp.head(pp.hidden_cm(enc_p, mode), pv8, mode, p_control, pitch_target,
+                                          self.pitch_bins.detach(), self.pitch_embedding.weight, enc_p)
+        energy_prediction, enc_p = ep.head(ep.hidden_cm(enc_p, mode), pv8, mode, p_control, energy_target,
+                                           self.energy_bins.detach(), self.energy_embedding.weight, enc_p)
 
-        enc_p_rm = ag.transpose_to_blm(enc_p)
+        # word pooling -> word encoder (:347-353)
+        enc_p_rm = _to_rm(mode, enc_p)
         src_w_seq = lingops.word_level_pooling(enc_p_rm, src_p_len, wb, src_w_len, "mean", max_words=W)
-        enc_w = self.word_encoder.forward_cm_train(_MaskedToCmFn.apply(src_w_seq, wv8), wv8, wp8)
-        enc_w_rm = ag.transpose_to_blm(enc_w)
+        if mode == _INFER:
+            src_w_seq = ops.transpose_bml(src_w_seq, False, keep=wv8)
+        else:
+            src_w_seq = _MaskedToCmFn.apply(src_w_seq, wv8)
+        enc_w = self.word_encoder.forward_cm(src_w_seq, wv8, wp8, mode)
+        enc_w_rm = _to_rm(mode, enc_w)
         if self.record:
             self.recorded = {"enc_p_out": enc_p_rm, "enc_w_out": enc_w_rm}
 
+        # durations (:355-376)
         dp = self.duration_predictor
-        log_d_p = dp.head_train(dp.hidden_cm_train(enc_p), pv8)
-        log_duration_w_prediction, duration_w_rounded = _DurationHeadFn.apply(
-            log_d_p, None if duration_target is None else duration_target.to(torch.int64).contiguous(), wb, src_w_len,
-            float(duration_control), W)
+        log_d_p = dp.head(dp.hidden_cm(enc_p, mode), pv8, mode)
+        log_duration_w_prediction, duration_w_rounded = (duration_head if mode == _INFER else _DurationHeadFn.apply)(
+            log_d_p, duration_target, wb, src_w_len, duration_control, W)
         xr, mel_len = self.length_regulator(enc_w_rm, duration_w_rounded, max_len)
         if duration_target is None:
-            ids_ = torch.arange(xr.shape[1], device=dev)
-            mel_mask = ids_[None, :] < mel_len[:, None]
-        Lq = xr.shape[1]
-        if Lq > self.max_seq_len:
-            raise ValueError("LinguisticEncoder training: %d frames exceed max_seq_len %d (the position-encoding "
-                             "tables have max_seq_len + 1 rows)" % (Lq, self.max_seq_len))
+            ids = torch.arange(xr.shape[1], device=dev)
+            mel_mask = ids[None, :] < mel_len[:, None]
+        if mode != _INFER:
+            self._check_len(xr.shape[1], "frames")
 
+        # word-to-phoneme attention (:378-407); k and v share one input, and their rel coefficients are one tensor
         mapping = lingops.get_mapping_mask(xr, enc_p_rm, duration_w_rounded, wb, src_w_len)
         coef_q = lingops.get_rel_coef(duration_w_rounded, src_w_len, mel_mask)
         coef_kv = lingops.get_rel_coef(wb, src_p_len, src_p_mask)
-        q_in = _PosencAddFn.apply(xr, self.q_position_enc, True, coef_q)
-        kv_in = _PosencAddFn.apply(enc_p, self.kv_position_enc, False, coef_kv)
-        y, attns, attn_logprob = self.w2p_attn.forward_cm_train(
-            q_in, kv_in, pv8, _u8(mel_mask), _u8(mapping), attn_prior if self.helper_type == "ctc" else None)
-        out = ag.transpose_to_blm(y)
+        q_in = self._posenc(xr, True, coef_q, self.q_position_enc, mode)
+        kv_in = self._posenc(enc_p, False, coef_kv, self.kv_position_enc, mode)
+        y, attns, attn_logprob = self.w2p_attn.forward_cm(
+            q_in, kv_in, pv8, _u8(mel_mask), _u8(mapping), attn_prior if self.helper_type == "ctc" else None, mode)
+        out = _to_rm(mode, y)
         return (out, pitch_prediction, energy_prediction, log_duration_w_prediction, duration_w_rounded, mel_len,
                 mel_mask, attns, attn_logprob)
