@@ -373,6 +373,31 @@ int mg_conv_transpose_pack(const float *w, float *packed, int Ci, int Co, int u,
 int mg_conv_transpose1d_fwd(const float *in, const float *packed, const float *bias, float *out, int B, int Ci,
                             int Lin, int Co, int u, float in_slope, float alpha, void *stream);
 
+/* ------------------------------------------------------------------ MelGAN vocoder (melgan.py)
+ * Generator(80, ngf=32, n_residual_layers=3) of descriptinc/melgan-neurips mel2wav/modules.py.  in_bs / out_bs are
+ * batch strides in floats (0 = dense): they let x and t of a ResnetBlock share one [B, 2C, L] buffer. */
+/* Same as mg_conv_transpose1d_fwd, writing channels [0, Co) of a buffer with batch stride out_bs (0 -> Co*u*Lin). */
+int mg_conv_transpose1d_fwd_slice(const float *in, const float *packed, const float *bias, float *out, long out_bs,
+                                  int B, int Ci, int Lin, int Co, int u, float in_slope, float alpha, void *stream);
+/* ReflectionPad1d(pad) + Conv1d on the MG_PACK_PLAIN pack, pad = dil*(K-1)/2, Lout = L: out = act(alpha *
+ * conv(reflect(lrelu(in, in_slope))) + bias).  Out-of-range input positions read in[-l] / in[2(L-1)-l].  K = 7 with
+ * dil = 1 (first and last conv) or K = 3 with dil <= 9 (ResnetBlock); MG_ERR_SHAPE for L <= pad, as ReflectionPad1d. */
+int mg_conv1d_reflect_fwd(const float *in, long in_bs, const float *packed, const float *bias, float *out, long out_bs,
+                          int B, int Ci, int L, int Co, int K, int dil, float in_slope, int act, float act_slope,
+                          float alpha, void *stream);
+/* out = W in + bias, a K = 1 conv with batch strides.  A ResnetBlock's shortcut(x) + W2 t is this with Ci = 2C over
+ * [x ; t] and the packs of Ws and W2 concatenated along the reduction (mg_conv_pack_at), bias = bs + b2. */
+int mg_conv1x1_fwd_strided(const float *in, long in_bs, const float *packed, const float *bias, float *out, long out_bs,
+                           int B, int Ci, int L, int Co, void *stream);
+/* The three ResnetBlocks (dilations 1, 3, 9) of one stage in one launch, C in {32, 64}: out = block3(block2(block1(in))),
+ * in != out, both [B, C, L] dense, L > 9.  Per block k: w1[k] = mg_conv_pack of W1 [C, C, 3]; b1[k] [C];
+ * wmix[k] = [Ws | W2'] packed as K = 1 k-groups [0, C/8) and [C/8, C/4) of a C/4-group stream (mg_conv_pack_at), where
+ * W2' = W2[:, perm], perm[8g + 2e + h] = 8g + 4h + e (the accumulator row order, melgan.hip); bmix[k] = bs + b2. */
+int mg_melgan_stack_fwd(const float *in, float *out, const float *const *w1, const float *const *b1,
+                        const float *const *wmix, const float *const *bmix, int B, int C, int L, void *stream);
+/* Output samples per workgroup tile of mg_melgan_stack_fwd for C (0 if C is not taken). */
+int mg_melgan_stack_tile(int C);
+
 /* Step-embedding MLP: out = W2 mish(W0 [sin|cos](t * freq)).  Denoiser: model/modules.py:398-403,434;
  * JCUDiscriminator: model/mixgantts.py:203-208,265.  emb [B,D0], pre/h [B,D1] are saved for backward. */
 int mg_step_mlp_fwd(const int64_t *t, const float *freq, const float *W0, const float *W2, float *emb,

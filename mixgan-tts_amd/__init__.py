@@ -24,5 +24,6 @@ from .transformer import Decoder, FFTBlock, PostNet, MultiHeadAttention, Positio
 from .model_io import get_model, save_checkpoint, get_param_num  # noqa: F401
 from .linguistic_encoder import LinguisticEncoder  # noqa: F401
 from .losses import LinguisticEncoderLoss  # noqa: F401
+from .melgan import MelGANGenerator, MelVocoder  # noqa: F401
 
 __version__ = "0.1.0"

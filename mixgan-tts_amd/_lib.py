@@ -32,6 +32,8 @@ EXPORTS = (
     "mg_rel_attention_train_fwd", "mg_rel_attention_bwd_ws_floats", "mg_rel_attention_bwd", "mg_w2p_attention_bwd_ws_floats",
     "mg_w2p_attention_bwd", "mg_embed_cm_bwd", "mg_variance_head_bwd", "mg_duration_head_bwd", "mg_posenc_add_bwd",
     "mg_dropout_apply",
+    "mg_conv_transpose1d_fwd_slice", "mg_conv1d_reflect_fwd", "mg_conv1x1_fwd_strided", "mg_melgan_stack_fwd",
+    "mg_melgan_stack_tile",
 )
 
 
@@ -199,6 +201,12 @@ def _declare(L):
         "mg_profile_begin": (i, [i]),
         "mg_profile_begin_sampled": (i, [i, i]),
         "mg_profile_end": (i, [vp, i]),
+        "mg_conv_transpose1d_fwd_slice": (i, [vp, vp, vp, vp, lg, i, i, i, i, i, f, f, vp]),
+        "mg_conv1d_reflect_fwd": (i, [vp, lg, vp, vp, vp, lg, i, i, i, i, i, i, f, i, f, f, vp]),
+        "mg_conv1x1_fwd_strided": (i, [vp, lg, vp, vp, vp, lg, i, i, i, i, vp]),
+        "mg_melgan_stack_fwd": (i, [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                    ctypes.POINTER(vp), i, i, i, vp]),
+        "mg_melgan_stack_tile": (i, [i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

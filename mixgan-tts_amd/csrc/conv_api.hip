@@ -115,6 +115,17 @@ extern "C" int mg_conv1d_fwd(const float *in, const float *in_vec, const float *
                             alpha, accumulate, stream);
 }
 
+extern "C" int mg_conv1x1_fwd_strided(const float *in, long in_bs, const float *packed, const float *bias, float *out,
+                                      long out_bs, int B, int Ci, int L, int Co, void *stream)
+{
+    if (!in || !packed || !out) return MG_ERR_ARG;
+    if (B <= 0 || Ci <= 0 || Co <= 0 || L <= 0 || in_bs < 0 || out_bs < 0) return MG_ERR_SHAPE;
+    if ((in_bs != 0 && in_bs < (long)Ci * L) || (out_bs != 0 && out_bs < (long)Co * L)) return MG_ERR_SHAPE;
+    ConvShape s{B, Ci, L, L, 1, 1, 0, Co, in_bs, 0};
+    EpiBiasAct::Params ep{out, bias, nullptr, 1.f, Co, MG_ACT_NONE, 0, out_bs, nullptr, 0.f};
+    return conv_launch<EpiBiasAct>(s, in, nullptr, packed, ep, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // weight gradient + row sums (bias gradients, per-sample channel sums)
 // ---------------------------------------------------------------------------------------------

@@ -249,10 +249,19 @@ struct EpiBiasAct {
     }
 };
 
+// Epilogues that serve the MelGAN generator only (melgan.hip) opt in here, and instantiate only its shapes (conv_launch):
+//   1 = reflect padding (ReflectionPad1d in front of the conv, MelGAN mel2wav/modules.py): an input position l < 0
+//       stages in[-l], l >= Lin stages in[2 (Lin-1) - l] (a launcher guarantees pad < Lin), and every in-tile element
+//       is live -- K = 7 (first and last conv) and K = 3 with dilation <= 9 (the ResnetBlock convs);
+//   2 = the polyphase transposed conv writing a channel slice of a wider buffer (K = 3 only).
+template <class Epi>
+struct EpiMelGAN { static constexpr int value = 0; };
+
 // ---------------------------------------------------------------------------------------------
 template <int KW, int STRIDE, int CK, int DILMAX, int MW, int WM, int NNB, class Epi>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, typename Epi::Params ep)
 {
+    constexpr bool REFLECT = EpiMelGAN<Epi>::value == 1;
     static_assert(MW == 2 || (MW == 1 && WM == 1), "wave layouts: 2(M) x 2(N), or 1 x 4 for <= 32 output rows");
     constexpr int NW = 4 / MW;         // waves along the frame axis
     constexpr int NT = NW * 32 * NNB;  // output frames per workgroup
@@ -311,14 +320,19 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, typename 
         const int idx = tid + k * 256;
         const int row = idx / TW;
         const int l = lbase + (idx - row * TW);
-        if (idx < TILE && l >= 0 && l < a.Lin) lmask |= 1ull << k;
+        if (idx < TILE && (REFLECT || (l >= 0 && l < a.Lin))) lmask |= 1ull << k;
     }
     const bool has_vec = a.in_vec != nullptr;
     const float *vecb = has_vec ? a.in_vec + (size_t)b * a.Ci : nullptr;
     // element k of the slab of `chunk`: one clamped global load (+ the per-channel vector)
     auto load_elem = [&](int chunk, int k) {
         const int idx = tid + k * 256, row = idx / TW;
-        const int ci = chunk * CK + row, l = lbase + (idx - row * TW);
+        const int ci = chunk * CK + row;
+        int l = lbase + (idx - row * TW);
+        if constexpr (REFLECT) {   // mirrored about 0 and Lin - 1; what lands outside after that feeds no stored output
+            l = l < 0 ? -l : l;
+            l = l >= a.Lin ? 2 * (a.Lin - 1) - l : l;
+        }
         const int cic = ci < a.Ci ? ci : a.Ci - 1;
         const int lcl = l < 0 ? 0 : (l >= a.Lin ? a.Lin - 1 : l);   // clamped: always a valid address
         stage[k] = inb[(size_t)cic * a.in_rs + lcl];
@@ -573,17 +587,24 @@ static int conv_launch(const ConvShape &s, const float *in, const float *in_vec,
     if (s.B <= 0 || s.Lout <= 0 || s.Ci <= 0 || s.Mrows <= 0 || s.dil < 1) return MG_ERR_SHAPE;
 #define MG_CONV_CASE(KW_, ST_, CK_, DM_) \
     if (s.K == KW_ && s.stride == ST_ && s.dil <= DM_) return conv_launch_k<KW_, ST_, CK_, DM_, Epi>(s, in, in_vec, wp, ep, st);
-    MG_CONV_CASE(1, 1, 32, 1)
-    MG_CONV_CASE(3, 1, 32, 1)
-    MG_CONV_CASE(5, 1, 16, 1)
-    MG_CONV_CASE(9, 1, 16, 1)
-    MG_CONV_CASE(5, 2, 16, 1)
-    if constexpr (EpiWide<Epi>::value) {
-        MG_CONV_CASE(3, 1, 32, 5)
-        MG_CONV_CASE(7, 1, 16, 5)
-        MG_CONV_CASE(11, 1, 16, 5)
-        MG_CONV_CASE(16, 1, 16, 1)
-        MG_CONV_CASE(4, 1, 16, 1)
+    if constexpr (EpiMelGAN<Epi>::value == 1) {
+        MG_CONV_CASE(3, 1, 32, 9)
+        MG_CONV_CASE(7, 1, 16, 1)
+    } else if constexpr (EpiMelGAN<Epi>::value == 2) {
+        MG_CONV_CASE(3, 1, 32, 1)
+    } else {
+        MG_CONV_CASE(1, 1, 32, 1)
+        MG_CONV_CASE(3, 1, 32, 1)
+        MG_CONV_CASE(5, 1, 16, 1)
+        MG_CONV_CASE(9, 1, 16, 1)
+        MG_CONV_CASE(5, 2, 16, 1)
+        if constexpr (EpiWide<Epi>::value) {
+            MG_CONV_CASE(3, 1, 32, 5)
+            MG_CONV_CASE(7, 1, 16, 5)
+            MG_CONV_CASE(11, 1, 16, 5)
+            MG_CONV_CASE(16, 1, 16, 1)
+            MG_CONV_CASE(4, 1, 16, 1)
+        }
     }
 #undef MG_CONV_CASE
     return MG_ERR_SHAPE;

@@ -14,6 +14,8 @@ stride-1 convolution on the transposed, tap-flipped pack); the three ResBlocks o
 one buffer and the 1/3 is folded into the next convolution (leaky ReLU is positively homogeneous).
 Inference only (the vocoder is not trained on this path).
 """
+import math
+
 import torch
 from torch import nn
 
@@ -160,15 +162,39 @@ class AttrDict(dict):
         self.__dict__ = self
 
 
+class MelGANCheckpointRequired(_lib.MixganHipError, NotImplementedError):
+    """get_vocoder for MelGAN without `checkpoint_path`: the reference fetches the weights with torch.hub, which is a
+    download and is not mirrored here."""
+
+
+MELGAN_HUB_FILES = {"LJSpeech": "linda_johnson.pt", "universal": "multi_speaker.pt"}
+
+
 def get_vocoder(config, device, config_path="hifigan/config.json", checkpoint_path=None):
-    """utils/model.py:74-105 for `vocoder.model == "HiFi-GAN"`: build from hifigan/config.json, load the
-    `generator` state dict of hifigan/generator_<speaker>.pth.tar, eval, remove_weight_norm, move to the device.
-    (MelGAN comes from torch.hub -- a download -- and is not mirrored.)"""
+    """utils/model.py:74-105.  "HiFi-GAN": build from hifigan/config.json, load the `generator` state dict of
+    hifigan/generator_<speaker>.pth.tar, eval, remove_weight_norm, move to the device.  "MelGAN": build
+    melgan.MelVocoder and load `checkpoint_path` -- the generator state dict of descriptinc/melgan-neurips
+    models/<name>.pt (linda_johnson.pt for LJSpeech, multi_speaker.pt for universal) -- into `.mel2wav`, eval,
+    move to the device; weight norm stays, as in the hub.  Nothing is fetched: without `checkpoint_path` MelGAN
+    raises MelGANCheckpointRequired."""
     import json
     name = config["vocoder"]["model"]
     speaker = config["vocoder"]["speaker"]
+    if name == "MelGAN":
+        hub_file = MELGAN_HUB_FILES.get(speaker, "multi_speaker.pt")
+        if checkpoint_path is None:
+            raise MelGANCheckpointRequired(
+                "vocoder MelGAN (speaker %r): pass checkpoint_path= the melgan-neurips state dict models/%s; the "
+                "reference's torch.hub download is not mirrored" % (speaker, hub_file))
+        from .melgan import MelVocoder
+        vocoder = MelVocoder()
+        sd = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+        vocoder.mel2wav.load_state_dict(sd)
+        vocoder.mel2wav.eval()
+        vocoder.mel2wav.to(device)
+        return vocoder
     if name != "HiFi-GAN":
-        raise NotImplementedError("vocoder %r: only HiFi-GAN is on the HIP path" % name)
+        raise NotImplementedError("vocoder %r: only HiFi-GAN and MelGAN are on the HIP path" % name)
     with open(config_path, "r") as f:
         h = AttrDict(json.load(f))
     vocoder = Generator(h)
@@ -185,10 +211,14 @@ def get_vocoder(config, device, config_path="hifigan/config.json", checkpoint_pa
 def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None):
     """utils/model.py:108-126: mels [B, 80, L] -> list of int16 numpy waveforms (cropped to `lengths`).  The scaling
     and the int16 conversion run on the device, so the host copy is half the bytes of the reference's."""
-    if model_config["vocoder"]["model"] != "HiFi-GAN":
-        raise NotImplementedError("only HiFi-GAN is on the HIP path")
+    name = model_config["vocoder"]["model"]
+    if name not in ("HiFi-GAN", "MelGAN"):
+        raise NotImplementedError("only HiFi-GAN and MelGAN are on the HIP path")
     with torch.no_grad():
-        wavs = vocoder(mels).squeeze(1)
+        if name == "MelGAN":   # vocoder.inverse(mels / np.log(10)), the 1/ln 10 on the first conv's alpha
+            wavs = vocoder.mel2wav.forward_scaled(mels, 1.0 / math.log(10.0)).squeeze(1)
+        else:
+            wavs = vocoder(mels).squeeze(1)
         scaled = wavs * float(preprocess_config["preprocessing"]["audio"]["max_wav_value"])
         wavs = scaled.to(torch.int32).to(torch.int16).cpu().numpy()     # truncation toward zero, as numpy's astype
     wavs = [w for w in wavs]

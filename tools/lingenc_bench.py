@@ -6,7 +6,8 @@
 Inference forward (phoneme ids -> the nine outputs, including its one host sync for the frame count) at B=1 and
 B=16, ~120 phonemes and ~1000 frames per utterance, timed with device events around each call; the same forward as
 stock PyTorch-ROCm eager (the plain-torch restatement tests/lingenc_torch.py on the same GPU), alternated call by
-call with the native one; and text -> wav: phoneme ids -> native encoder -> naive T=4 diffusion -> HiFi-GAN.
+call with the native one; and text -> wav: phoneme ids -> native encoder -> naive T=4 diffusion -> HiFi-GAN (or, with
+--vocoder melgan, the native MelGAN).
 The configs are the LJSpeech ones recorded in tests/golden/lingenc_manifest.json; weights are the modules' own
 initialisation (torch seed 0) with the duration predictor's bias set so that a phoneme lasts ~9 frames.  For launch counts run it under `rocprofv3 --kernel-trace --stats -- python
 tools/lingenc_bench.py --iters 3`.
@@ -78,6 +79,8 @@ def timed(fn, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--vocoder", choices=("hifigan", "melgan"), default="hifigan",
+                    help="vocoder of the text -> wav rows (melgan: the native MelGAN, fused residual stacks)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     tmp = tempfile.mkdtemp()
@@ -114,9 +117,13 @@ def main():
     with torch.no_grad():
         m.linguistic_encoder.duration_predictor.linear_layer.bias.fill_(DUR_BIAS)
     m = m.to(dev).eval()
-    voc = mg.vocoder.Generator(types.SimpleNamespace(**HIFIGAN_V1)).to(dev).eval()
-    voc.remove_weight_norm()
-    vmc = {"vocoder": {"model": "HiFi-GAN", "speaker": "LJSpeech"}}
+    if args.vocoder == "melgan":
+        voc = mg.MelVocoder().to(dev).eval()
+        vmc = {"vocoder": {"model": "MelGAN", "speaker": "LJSpeech"}}
+    else:
+        voc = mg.vocoder.Generator(types.SimpleNamespace(**HIFIGAN_V1)).to(dev).eval()
+        voc.remove_weight_norm()
+        vmc = {"vocoder": {"model": "HiFi-GAN", "speaker": "LJSpeech"}}
     vpre = {"preprocessing": {"audio": {"max_wav_value": 32768.0}}}
     for B in (1, 16):
         texts, src_lens, wb, _, src_w_lens, _ = batch(B, 120, gen, dev)
@@ -132,6 +139,7 @@ def main():
         mel, mel_len, _ = run()
         audio = float(mel_len.sum()) * 256 / 22050.0
         print(json.dumps({"config": "e2e phoneme ids -> native encoder -> mel (T=4) -> wav, B=%d, 120 phonemes" % B,
+                          "vocoder": vmc["vocoder"]["model"],
                           "frames_max": int(mel.shape[1]), "ms": round(t, 2), "audio_s": round(audio, 1),
                           "real_time_factor": round(t / 1e3 / audio, 5)}), flush=True)
 
