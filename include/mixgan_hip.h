@@ -398,6 +398,30 @@ int mg_melgan_stack_fwd(const float *in, float *out, const float *const *w1, con
 /* Output samples per workgroup tile of mg_melgan_stack_fwd for C (0 if C is not taken). */
 int mg_melgan_stack_tile(int C);
 
+/* Audio front end (audio/stft.py, audio/audio_processing.py; csrc/audio.hip).  n_fft = MG_STFT_N, hop a power of two
+ * <= MG_STFT_N; window [MG_STFT_N] fp32 (centre-padded), twiddle [MG_STFT_N] complex fp32 interleaved,
+ * twiddle[k] = exp(-2 pi i k / MG_STFT_N).  x [B, L] with batch stride x_bs, L > MG_STFT_N / 2; lengths [B] int32
+ * (null: all L) gives each item its own reflect end and frame count 1 + lengths[b] / hop; frames past it are 0.
+ * T (<= 1 + L / hop) is the frame dimension of the outputs. */
+#define MG_STFT_N 1024
+#define MG_STFT_MAX_MELS 128
+/* STFT.transform (stft.py:55-82): magnitude and phase [B, N/2+1, T] at element (b, k, t) = b s_bs + k s_ks + t s_ts.
+ * mag null: phase only (the Griffin-Lim update). */
+int mg_stft_fwd(const float *x, long x_bs, const int *lengths, int B, int L, int hop, const float *window,
+                const float *twiddle, float *mag, float *phase, long s_bs, long s_ks, long s_ts, int T, void *stream);
+/* TacotronSTFT.mel_spectrogram (stft.py:160-178): mel [B, n_mels, T] = log(max(mel_basis |STFT|, 1e-5)), energy [B, T]
+ * = ||STFT||_2 over bins.  The basis is passed as per-row nonzero bands: band[m], band[n_mels + m],
+ * band[2 n_mels + m] = first bin, bin count, offset into band_w. */
+int mg_stft_mel(const float *x, long x_bs, const int *lengths, int B, int L, int hop, const float *window,
+                const float *twiddle, const int *band, const float *band_w, int n_mels, float *mel, float *energy,
+                int T, void *stream);
+/* STFT.inverse (stft.py:84-121): out [B, (T-1) hop] from magnitude / phase (strides as mg_stft_fwd), T >= 2.
+ * wsq [MG_STFT_N] float64 = the squared centre-padded window (window_sumsquare is evaluated in-kernel from it).
+ * tile: output samples per workgroup, a multiple of 64 up to 1024 (a launch-shape choice; the result does not
+ * depend on it). */
+int mg_istft(const float *mag, const float *phase, long s_bs, long s_ks, long s_ts, int B, int T, int hop,
+             const float *window, const double *wsq, const float *twiddle, float *out, int tile, void *stream);
+
 /* Step-embedding MLP: out = W2 mish(W0 [sin|cos](t * freq)).  Denoiser: model/modules.py:398-403,434;
  * JCUDiscriminator: model/mixgantts.py:203-208,265.  emb [B,D0], pre/h [B,D1] are saved for backward. */
 int mg_step_mlp_fwd(const int64_t *t, const float *freq, const float *W0, const float *W2, float *emb,

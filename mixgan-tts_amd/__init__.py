@@ -15,7 +15,7 @@ from .diffusion import GaussianDiffusion  # noqa: F401
 from .discriminator import JCUDiscriminator  # noqa: F401
 from . import ops, autograd, losses, distributed  # noqa: F401
 from .train_step import HotPathTrainer, AuxTrainer  # noqa: F401
-from . import lingops, vocoder, data  # noqa: F401
+from . import lingops, vocoder, data, audio  # noqa: F401
 from . import optimizer  # noqa: F401
 from .optimizer import ScheduledOptim, FlatAdam  # noqa: F401
 from .distributed import GradBucket  # noqa: F401

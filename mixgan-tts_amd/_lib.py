@@ -33,7 +33,7 @@ EXPORTS = (
     "mg_w2p_attention_bwd", "mg_embed_cm_bwd", "mg_variance_head_bwd", "mg_duration_head_bwd", "mg_posenc_add_bwd",
     "mg_dropout_apply",
     "mg_conv_transpose1d_fwd_slice", "mg_conv1d_reflect_fwd", "mg_conv1x1_fwd_strided", "mg_melgan_stack_fwd",
-    "mg_melgan_stack_tile",
+    "mg_melgan_stack_tile", "mg_stft_fwd", "mg_stft_mel", "mg_istft",
 )
 
 
@@ -207,6 +207,9 @@ def _declare(L):
         "mg_melgan_stack_fwd": (i, [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                     ctypes.POINTER(vp), i, i, i, vp]),
         "mg_melgan_stack_tile": (i, [i]),
+        "mg_stft_fwd": (i, [vp, lg, vp, i, i, i, vp, vp, vp, vp, lg, lg, lg, i, vp]),
+        "mg_stft_mel": (i, [vp, lg, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, i, vp]),
+        "mg_istft": (i, [vp, vp, lg, lg, lg, i, i, i, vp, vp, vp, vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
