@@ -669,6 +669,25 @@ int mg_posenc_add_bwd(const float *dout, const float *coef, float *dtable, int B
 /* Dropout with a given keep-mask: out[e] = keep[e] ? x[e] * scale : 0 (also its own backward). */
 int mg_dropout_apply(const float *x, const uint8_t *keep, float scale, float *out, size_t n, void *stream);
 
+/* DeepSpeaker ResCNN speaker embedder (reference deepspeaker package; csrc/deepspeaker.hip), fp32.
+ * Filterbank front end: audio [B, x_bs] fp32; item b's trimmed signal is audio[b, start[b] : end[b]) (end > start);
+ * out [B, frames, nfilt] = the normalised fbank of its frames offset[b] .. offset[b] + frames - 1 (frame_len samples
+ * every frame_step, pre-emphasis 0.97, rectangular window, zero-padded 1024-point power spectrum / 1024, banded
+ * filters as mg_stft_mel's band table, exact zeros -> DBL_EPSILON, per-frame (v - mean) / max(std, 1e-12)); rows at
+ * or past the item's frame count are zeros.  frame_len <= MG_STFT_N, nfilt <= 64. */
+int mg_ds_fbank(const float *audio, long x_bs, const int *start, const int *end, const int *offset, int B, int frames,
+                int frame_len, int frame_step, const float *twiddle, const int *band, const float *band_w, int nfilt,
+                float *out, void *stream);
+/* 2-D convolution with TF 'same' padding (asymmetric: pad_total / 2 before), NHWC: x [Nb, H, W, Ci], w packed
+ * [(kh ks + kw) Ci + ci][Co] (BN folded), y [Nb, ceil(H / stride), ceil(W / stride), Co] = clip(conv + bias, 0, 20),
+ * then with res (same shape as y, or NULL) clip(y + res, 0, 20).  Co % 64 == 0; Ci % 32 == 0 runs the MFMA implicit
+ * GEMM, other Ci a direct kernel. */
+int mg_ds_conv2d(const float *x, const float *w, const float *bias, const float *res, float *y, int Nb, int H, int W,
+                 int Ci, int Co, int ks, int stride, void *stream);
+/* Head: out [B, O] = l2_normalize(mean over rows of x[b] ([rows, D]) . w [D, O] + bias).  O % 64 == 0, O <= 512. */
+int mg_ds_head(const float *x, const float *w, const float *bias, float *out, int B, int rows, int D, int O,
+               void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

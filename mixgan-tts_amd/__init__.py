@@ -25,5 +25,8 @@ from .model_io import get_model, save_checkpoint, get_param_num  # noqa: F401
 from .linguistic_encoder import LinguisticEncoder  # noqa: F401
 from .losses import LinguisticEncoderLoss  # noqa: F401
 from .melgan import MelGANGenerator, MelVocoder  # noqa: F401
+from . import speaker_embedder  # noqa: F401
+from .speaker_embedder import (DeepSpeakerModel, PreDefinedEmbedder, DeepSpeakerCheckpointRequired,  # noqa: F401
+                               save_speaker_embeddings)
 
 __version__ = "0.1.0"

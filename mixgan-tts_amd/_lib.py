@@ -33,7 +33,7 @@ EXPORTS = (
     "mg_w2p_attention_bwd", "mg_embed_cm_bwd", "mg_variance_head_bwd", "mg_duration_head_bwd", "mg_posenc_add_bwd",
     "mg_dropout_apply",
     "mg_conv_transpose1d_fwd_slice", "mg_conv1d_reflect_fwd", "mg_conv1x1_fwd_strided", "mg_melgan_stack_fwd",
-    "mg_melgan_stack_tile", "mg_stft_fwd", "mg_stft_mel", "mg_istft",
+    "mg_melgan_stack_tile", "mg_stft_fwd", "mg_stft_mel", "mg_istft", "mg_ds_fbank", "mg_ds_conv2d", "mg_ds_head",
 )
 
 
@@ -210,6 +210,9 @@ def _declare(L):
         "mg_stft_fwd": (i, [vp, lg, vp, i, i, i, vp, vp, vp, vp, lg, lg, lg, i, vp]),
         "mg_stft_mel": (i, [vp, lg, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, i, vp]),
         "mg_istft": (i, [vp, vp, lg, lg, lg, i, i, i, vp, vp, vp, vp, i, vp]),
+        "mg_ds_fbank": (i, [vp, lg, vp, vp, vp, i, i, i, i, vp, vp, vp, i, vp, vp]),
+        "mg_ds_conv2d": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]),
+        "mg_ds_head": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -24,6 +24,7 @@
 // 1 / (n_fft / hop) in its pseudo-inverse and its * (n_fft / hop) after the division are powers of two that cancel
 // exactly, so neither is applied.
 #include "common.h"
+#include "fft1024.h"
 
 #include <float.h>
 
@@ -32,46 +33,6 @@ namespace {
 constexpr int N = MG_STFT_N;   // 1024
 constexpr int NB = N / 2 + 1;  // 513 bins
 constexpr int MAX_TILE = 1024;
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b)
-{
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// In-place forward FFT of d[0, 1024) by one wave: radix-4 Stockham, pass s (Ns = 4^s) maps butterfly j, k = j mod Ns,
-// from d[j + 256 r] (times W^(r k 256 / Ns)) to d[4 (j - k) + k + r Ns].  Every lane reads its 16 points before the
-// barrier and writes after it.
-__device__ __forceinline__ void fft1024(float2 *d, const float2 *__restrict__ tw, int lane)
-{
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        const int Ns = 1 << (2 * s), tws = 256 >> (2 * s);
-        float2 v[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[q][r] = d[lane + 64 * q + 256 * r];
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = lane + 64 * q, k = j & (Ns - 1);
-            if (s > 0) {
-#pragma unroll
-                for (int r = 1; r < 4; ++r) v[q][r] = cmul(v[q][r], tw[r * k * tws]);
-            }
-            const float2 s02 = make_float2(v[q][0].x + v[q][2].x, v[q][0].y + v[q][2].y);
-            const float2 d02 = make_float2(v[q][0].x - v[q][2].x, v[q][0].y - v[q][2].y);
-            const float2 s13 = make_float2(v[q][1].x + v[q][3].x, v[q][1].y + v[q][3].y);
-            const float2 d13 = make_float2(v[q][1].x - v[q][3].x, v[q][1].y - v[q][3].y);
-            const int base = 4 * (j - k) + k;
-            d[base] = make_float2(s02.x + s13.x, s02.y + s13.y);
-            d[base + Ns] = make_float2(d02.x + d13.y, d02.y - d13.x);
-            d[base + 2 * Ns] = make_float2(s02.x - s13.x, s02.y - s13.y);
-            d[base + 3 * Ns] = make_float2(d02.x - d13.y, d02.y + d13.x);
-        }
-        __syncthreads();
-    }
-}
 
 struct FwdArgs {
     const float *x;
@@ -149,7 +110,7 @@ __device__ __forceinline__ void stft_fwd_body(const FwdArgs &a)
         d[n] = z;
     }
     __syncthreads();
-    fft1024(d, a.tw, lane);
+    mg_fft1024(d, a.tw, lane);
 
     float e0 = 0.f, e1 = 0.f;
 #pragma unroll
@@ -258,7 +219,7 @@ __global__ __launch_bounds__(64) void istft_ola_kernel(InvArgs a)
             if (k != 0 && k != N / 2) d[N - k] = make_float2(ra + ib, -(rb - ia));
         }
         __syncthreads();
-        fft1024(d, a.tw, lane);
+        mg_fft1024(d, a.tw, lane);
         // frame ta is Re(d) / N, frame ta + 1 is -Im(d) / N; add them in that order
         const int ba = ta * hop, bb = ba + hop;
 #pragma unroll
