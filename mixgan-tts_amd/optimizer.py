@@ -146,22 +146,31 @@ class FlatAdam(torch.optim.Adam):
         return self._norm if max_grad_norm is not None else None
 
     def enable_device_hyper(self):
-        """From now on the update kernel reads lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) from device memory (written
+        """From now on the update kernel reads lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) from a device pair (filled
         by write_hyper) instead of taking them as launch arguments: a hipGraph that contains step() then replays with the
-        step count and learning rate of the moment (HotPathTrainer.capture)."""
+        step count and learning rate of the moment (HotPathTrainer.capture).  The host may queue any number of steps
+        ahead of the GPU either way (write_hyper)."""
         if self._hyper is None:
             self._hyper = torch.zeros(2, device=self.flat_p.device, dtype=torch.float32)
-            self._hyper_host = torch.zeros(2, dtype=torch.float32).pin_memory()
         return self
 
     def write_hyper(self, step=None):
-        """Host -> device: the two scalars of the step about to run (step: 1-based count; default: the current one)."""
+        """Queue on the current stream the two scalars of the step about to run (step: 1-based count; default: the
+        current one): one fill launch per element of the device pair, float32 of the double expressions below.  Each
+        value travels as an argument of its launch, fixed when the host queues it, so queued steps and replays each
+        read their own pair.  (A non_blocking copy from a host staging buffer would read that buffer only when it runs
+        on the GPU, after the host may have rewritten it for a later step.)"""
         g = self.param_groups[0]
         t = float(self._steps) if step is None else float(step)
         b1, b2 = g["betas"]
-        self._hyper_host[0] = g["lr"] / (1.0 - b1 ** t)
-        self._hyper_host[1] = 1.0 / (1.0 - b2 ** t) ** 0.5
-        self._hyper.copy_(self._hyper_host, non_blocking=True)
+        self._hyper[0].fill_(g["lr"] / (1.0 - b1 ** t))
+        self._hyper[1].fill_(1.0 / (1.0 - b2 ** t) ** 0.5)
+
+    def prepare_replay(self):
+        """Ahead of each replay of a graph that captured step(): queue the scalars of the step the replay performs and
+        count that step (under capture, step() writes no scalars, and the capturing side undoes its count)."""
+        self.write_hyper(float(self._steps) + 1.0)
+        self._steps += 1
 
     def adopt(self, adam):
         """Continue from a stock torch.optim.Adam over (a superset of) the same parameter objects -- e.g. the optG /

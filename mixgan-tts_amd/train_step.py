@@ -116,9 +116,11 @@ class HotPathTrainer:
         copied into static buffers) and return value (the loss tensors are static too: read them before the next call).
 
         What differs from step(): t / noise come from torch's graph-safe generator state; the optimizers' step counts and
-        learning rates travel through device memory (FlatAdam.enable_device_hyper), so lr schedulers keep working; the
-        discriminator's gradients are zeroed in place instead of set to None (same numbers).  Single process only (the
-        gradient exchange is not captured), grad_acc_step = 1, no grad_hook / t_fn / noise_fn."""
+        learning rates travel through device memory (FlatAdam.enable_device_hyper), so lr schedulers keep working -- each
+        call queues its own pair of Adam scalars ahead of its replay (FlatAdam.prepare_replay), so the host may queue any
+        number of replays without waiting for the GPU; the discriminator's gradients are zeroed in place instead of set
+        to None (same numbers).  Single process only (the gradient exchange is not captured), grad_acc_step = 1, no
+        grad_hook / t_fn / noise_fn."""
         if not (isinstance(self.optG, FlatAdam) and isinstance(self.optD, FlatAdam)):
             raise RuntimeError("capture() needs the GPU trainer (FlatAdam optimizers)")
         if self.bucketG.exchanging() or self.grad_acc != 1 or self.grad_hook is not None or self.G.t_fn or self.G.noise_fn:
@@ -384,10 +386,8 @@ class _GraphedStep:
             if dst is not None and dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         for opt in (tr.optD, tr.optG):         # the step counts / learning rates this replay's updates use
-            opt.write_hyper(float(opt._steps) + 1.0)
+            opt.prepare_replay()
         self.graph.replay()
-        tr.optD._steps += 1
-        tr.optG._steps += 1
         tr.step_no += 1
         torch.autograd.graph.increment_version(self._params)     # derived caches (packed weights) of eager users
         return self.out
