@@ -342,6 +342,11 @@ int mg_denoiser_bwd(const mg_denoiser_dims *d, const float *packed, const float 
                     const float *x_t, const float *cond, const float *spk, float *workspace,
                     float *bwd_workspace, size_t bwd_workspace_floats, float *const *grads,
                     float *d_x_t, float *d_cond, float *d_spk, int B, int L, void *stream);
+/* Copies the single-launch data-gradient kernel's counter words {ticket, error, launches, workgroups done} of a (B, L)
+ * backward workspace to host_out4 and synchronises the stream.  launches counts the single launches completed on this
+ * workspace (the launch-per-layer path leaves it alone); error != 0: a hand-off timed out (sticky). */
+int mg_denoiser_bwd_status(const mg_denoiser_dims *d, const float *bwd_workspace, int B, int L, unsigned *host_out4,
+                           void *stream);
 /* Same; conv3_grads_done (a hipEvent_t, or NULL) is recorded on `stream` right behind the launches that produce the
  * conv_layer weight and bias gradients of all layers (entries j=0/1: a third of the generator's gradient bytes), 0.6 ms
  * of GPU work before the last launch of the backward at B=8, L=1000 -- a data-parallel caller starts the all-reduce of

@@ -17,7 +17,7 @@ EXPORTS = (
     "mg_conv1d_wgrad_grouped_scratch_floats", "mg_conv1d_wgrad_grouped_bias", "mg_rowsum",
     "mg_diffuse_fwd", "mg_posterior_sample_fwd", "mg_posterior_sample_bwd", "mg_spec_affine", "mg_transpose_bml",
     "mg_denoiser_packed_floats", "mg_denoiser_pack", "mg_denoiser_workspace_floats", "mg_denoiser_fwd",
-    "mg_denoiser_bwd_workspace_floats", "mg_denoiser_bwd", "mg_denoiser_bwd_staged",
+    "mg_denoiser_bwd_workspace_floats", "mg_denoiser_bwd", "mg_denoiser_bwd_staged", "mg_denoiser_bwd_status",
     "mg_profile_begin", "mg_profile_begin_sampled", "mg_profile_end", "mg_transpose_bml_strided", "mg_act_bwd", "mg_upsample_zero",
     "mg_step_mlp_fwd", "mg_step_mlp_bwd", "mg_linear_small_fwd", "mg_linear_small_bwd",
     "mg_loss_sum", "mg_loss_grad", "mg_mel_l1_fwd", "mg_mel_l1_bwd", "mg_attention_fwd", "mg_attention_fwd_f16", "mg_layernorm_cm_fwd",
@@ -198,6 +198,7 @@ def _declare(L):
         "mg_denoiser_cond_project": (i, [dp, vp, vp, vp, i, i, vp]),
         "mg_persist_error": (ctypes.c_uint, [i]),
         "mg_denoiser_persist_status": (i, [dp, vp, i, i, vp, vp]),
+        "mg_denoiser_bwd_status": (i, [dp, vp, i, i, vp, vp]),
         "mg_profile_begin": (i, [i]),
         "mg_profile_begin_sampled": (i, [i, i]),
         "mg_profile_end": (i, [vp, i]),

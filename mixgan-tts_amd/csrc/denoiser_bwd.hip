@@ -180,6 +180,16 @@ extern "C" size_t mg_denoiser_bwd_workspace_floats(const mg_denoiser_dims *d, in
     return den_bws(d, B, L).total;
 }
 
+extern "C" int mg_denoiser_bwd_status(const mg_denoiser_dims *d, const float *bws, int B, int L, unsigned *host_out4,
+                                      void *stream)
+{
+    if (den_check(d) != MG_OK || !bws || !host_out4 || B <= 0 || L <= 0) return MG_ERR_ARG;
+    const DenBws bw = den_bws(d, B, L);
+    hipError_t e = hipMemcpyAsync(host_out4, bws + bw.sync, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? MG_OK : (int)e;
+}
+
 extern "C" int mg_denoiser_bwd(const mg_denoiser_dims *d, const float *packed, const float *g_out, const float *x_t,
                                const float *cond, const float *spk, float *ws, float *bws, size_t bws_floats,
                                float *const *grads, float *d_x_t, float *d_cond, float *d_spk, int B, int L,

@@ -332,6 +332,18 @@ class Denoiser(nn.Module):
         check(_lib.lib().mg_denoiser_persist_status(ctypes.byref(self._dims), fptr(ws), B, L, host, stream_ptr()))
         return {"ticket": host[0], "error": host[1], "launches": host[2], "done": host[3]}
 
+    def backward_status(self, B, L):
+        """{ticket, error, launches, done} of the single-launch data-gradient kernel's counters in the cached backward
+        workspace of this shape on the current stream (synchronises).  launches counts the single launches completed on
+        that workspace -- the launch-per-layer backward does not touch it; error != 0: a hand-off timed out (sticky).
+        All zero when no backward workspace of this shape is cached (none has run, or the cache evicted it)."""
+        dev = next(self.parameters()).device
+        bws = self._bws.get((B, L, dev, torch.cuda.current_stream(dev).cuda_stream))
+        host = (ctypes.c_uint * 4)()
+        if bws is not None:
+            check(_lib.lib().mg_denoiser_bwd_status(ctypes.byref(self._dims), fptr(bws), B, L, host, stream_ptr()))
+        return {"ticket": host[0], "error": host[1], "launches": host[2], "done": host[3]}
+
     def forward(self, mel, diffusion_step, conditioner, speaker_emb, mask=None):
         """mel [B,1,M,T], diffusion_step [B], conditioner [B,H,T], speaker_emb [B,H]|None -> [B,1,M,T]."""
         if not mel.is_cuda:

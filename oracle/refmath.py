@@ -13,8 +13,11 @@ import torch.nn.functional as F
 
 
 # ----------------------------------------------------------------------------- primitives
-def step_embedding(t, dim=256):
-    """model/blocks.py:906-913 -- [sin | cos] of t * exp(-i ln(1e4)/(dim/2-1))."""
+def step_embedding(t, dim=256, dtype=torch.float32):
+    """model/blocks.py:906-913 -- [sin | cos] of t * exp(-i ln(1e4)/(dim/2-1)).
+
+    `dtype`: what the caller's weights are in.  The values are always the fp32-rounded embedding (the number the
+    kernel's contract names); a float64 run of the denoiser sees exactly those, widened."""
     half = dim // 2
     rate = math.log(10000) / (half - 1)
     # The reference takes torch.exp of the fp32 products.  A host's vectorised fp32 exp is only good to ~1 ulp and
@@ -24,7 +27,7 @@ def step_embedding(t, dim=256):
     # 3.4e-6 from the fixture at t = 999, identical on every machine.
     freq = torch.exp((torch.arange(half, device=t.device) * -rate).double()).float()
     ang = (t[:, None] * freq[None, :]).double()
-    return torch.cat((ang.sin(), ang.cos()), dim=-1).float()
+    return torch.cat((ang.sin(), ang.cos()), dim=-1).float().to(dtype)
 
 
 def mish(x):
@@ -112,15 +115,19 @@ def denoiser_n_layers(W, p=""):
     return n
 
 
-def denoiser_forward(W, p, mel, t, cond, spk=None, stack_skips=True):
+def denoiser_forward(W, p, mel, t, cond, spk=None, stack_skips=True, taps=None):
     """model/modules.py:420-446.  mel [B,1,M,L], t int64 [B], cond [B,H,L] -> [B,1,M,L].
 
     `stack_skips=True` reproduces the reference's `torch.stack(skip)` reduction (the op the
-    CPU baseline must pay for).
+    CPU baseline must pay for).  `taps`: a dict that receives the inputs of the two ReLUs
+    ("input_pre", "skip_pre"), the only points where the gradient is discontinuous.
     """
-    x = F.relu(_conv(W, p + "input_projection.0", mel[:, 0]))
-    x = F.relu(x)
-    s = step_embedding(t, W[p + "mlp.0.linear.weight"].shape[1])
+    x = _conv(W, p + "input_projection.0", mel[:, 0])
+    if taps is not None:
+        taps["input_pre"] = x.detach()
+    x = F.relu(F.relu(x))
+    w0 = W[p + "mlp.0.linear.weight"]
+    s = step_embedding(t, w0.shape[1], w0.dtype)
     s = _lin(W, p + "mlp.2", mish(_lin(W, p + "mlp.0", s)))
     n = denoiser_n_layers(W, p)
     skips = []
@@ -134,8 +141,10 @@ def denoiser_forward(W, p, mel, t, cond, spk=None, stack_skips=True):
         for sk in skips[1:]:
             acc = acc + sk
         x = acc / math.sqrt(n)
-    x = F.relu(_conv(W, p + "skip_projection", x))
-    x = _conv(W, p + "output_projection", x)
+    x = _conv(W, p + "skip_projection", x)
+    if taps is not None:
+        taps["skip_pre"] = x.detach()
+    x = _conv(W, p + "output_projection", F.relu(x))
     return x[:, None, :, :]
 
 

@@ -11,6 +11,7 @@ if ROOT not in sys.path:
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 from oracle import weights as WR  # noqa: E402
+from oracle import refmath  # noqa: E402
 
 
 def golden(name):
@@ -31,6 +32,69 @@ def seeded(manifest, name, seed, prefix="", requires_grad=False):
             t.requires_grad_()
         out[prefix + k] = t
     return out, WR.checksum(w)
+
+
+def oracle_grads(W, x, t, cond, spk, go, dtype, chunk=4):
+    """out and every gradient of sum(out * go) by torch.autograd through the oracle, in `dtype`, `chunk` utterances at a
+    time (parameter gradients accumulate over the chunks; bounds the graph's memory at B = 16, L = 1000)."""
+    for w in W.values():
+        w.grad = None
+    res = {"out": [], "d_x": [], "d_cond": [], "d_spk": []}
+    for b0 in range(0, x.shape[0], chunk):
+        s = slice(b0, b0 + chunk)
+        xs, cs = x[s].to(dtype).requires_grad_(), cond[s].to(dtype).requires_grad_()
+        ss = None if spk is None else spk[s].to(dtype).requires_grad_()
+        out = refmath.denoiser_forward(W, "", xs, t[s], cs, ss)
+        (out * go[s].to(dtype)).sum().backward()
+        res["out"].append(out.detach())
+        res["d_x"].append(xs.grad)
+        res["d_cond"].append(cs.grad)
+        if ss is not None:
+            res["d_spk"].append(ss.grad)
+    ref = {k: torch.cat(v) for k, v in res.items() if v}
+    for k, w in W.items():
+        ref["param/" + k] = w.grad
+        w.grad = None
+    return ref
+
+
+def condition_relu_kinks(W64, x, t, cond, spk, go, band, gen, chunk=4):
+    """The denoiser's gradient is discontinuous where the input of one of its two ReLUs is zero, and a forward that is
+    right to `band` (relative to the largest such input) may put any element within that band on either side: there the
+    gradient has two legitimate values that differ by O(1) -- at B*L = 16 000 frames about 300 of the 8 M ReLU inputs
+    lie within 2e-5.  Makes the float64 reference single-valued without touching the product, in place:
+      input ReLU (a function of one frame of x): frames with an input inside the band are drawn again;
+      skip ReLU: at frames with an input inside the band, go loses its component along the output-projection columns
+      of those channels, so that the gradient arriving at them is zero and their mask bit multiplies nothing.
+    Returns (frames of x redrawn, frames of go projected)."""
+    Wd = {k: v.detach() for k, v in W64.items()}
+    w_in, b_in = Wd["input_projection.0.conv.weight"][:, :, 0], Wd["input_projection.0.conv.bias"]
+    redrawn = 0
+    while True:
+        pre = torch.einsum("cm,bml->bcl", w_in, x[:, 0].double()) + b_in[None, :, None]
+        bad = (pre.abs() <= band * pre.abs().max()).any(1)                # [B, L]
+        if not bool(bad.any()):
+            break
+        idx = bad.nonzero()
+        redrawn += len(idx)
+        x[idx[:, 0], 0, :, idx[:, 1]] = torch.randn(len(idx), x.shape[2], generator=gen)
+    pres = []
+    with torch.no_grad():
+        for b0 in range(0, x.shape[0], chunk):
+            s = slice(b0, b0 + chunk)
+            taps = {}
+            refmath.denoiser_forward(Wd, "", x[s].double(), t[s], cond[s].double(), None if spk is None else spk[s].double(),
+                                     taps=taps)
+            pres.append(taps["skip_pre"])
+    pre = torch.cat(pres)
+    bad = pre.abs() <= band * pre.abs().max()                             # [B, C, L]
+    w_out = Wd["output_projection.conv.weight"][:, :, 0]                  # [M, C]: d y_c = sum_m w_out[m, c] go[m]
+    frames = bad.any(1).nonzero()
+    for b, l in frames.tolist():
+        A = w_out[:, bad[b, :, l]]                                        # [M, k]
+        g = go[b, 0, :, l].double()
+        go[b, 0, :, l] = (g - A @ torch.linalg.lstsq(A, g[:, None]).solution[:, 0]).float()
+    return redrawn, len(frames)
 
 
 def rel_err(a, b):

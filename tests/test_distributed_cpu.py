@@ -48,7 +48,7 @@ def _worker(rank, world, port, q):
         b2.all_reduce_mean(async_op=True).wait()
         assert torch.equal(b.flat, b2.flat)
         if rank == 0:
-            q.put(b.flat.clone())
+            q.put(b.flat.numpy().copy())      # numpy: pickled by value (a tensor travels as a handle its sender must outlive)
     finally:
         dist.destroy_process_group()
 
@@ -61,7 +61,7 @@ def test_grad_bucket_allreduce_matches_full_batch():
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
-    flat = q.get(timeout=120)
+    flat = torch.from_numpy(q.get(timeout=120))
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
