@@ -173,19 +173,32 @@ int mg_transpose_bml_strided(const float *in, float *out, const float *spec_min,
                              void *stream);
 
 /* ------------------------------------------------------------------ Denoiser (model/modules.py:382-446)
- * Weight pointer table order for mg_denoiser_pack (names are the reference state_dict keys under
- * `diffusion.denoise_fn.`):
- *   [0] input_projection.0.conv.weight [C,M,1]   [1] input_projection.0.conv.bias [C]
- *   [2] mlp.0.linear.weight [4C,C]               [3] mlp.2.linear.weight [C,4C]
- *   [4] skip_projection.conv.weight [C,C,1]      [5] skip_projection.conv.bias [C]
- *   [6] output_projection.conv.weight [M,C,1]    [7] output_projection.conv.bias [M]
- *   then per residual layer i (8 + 9*i + j):
- *   j=0 conv_layer.conv.weight [2C,C,3]          j=1 conv_layer.conv.bias [2C]
- *   j=2 diffusion_projection.linear.weight [C,C] j=3 conditioner_projection.conv.weight [C,H,1]
- *   j=4 conditioner_projection.conv.bias [C]     j=5 output_projection.conv.weight [2C,C,1]
- *   j=6 output_projection.conv.bias [2C]         j=7 speaker_projection.linear.weight [C,H] or NULL
- *   j=8 reserved (NULL)
- */
+ * The pointer table of mg_denoiser_pack (weights) and mg_denoiser_bwd (gradients): MG_DEN_HEAD_PTRS head slots, then
+ * MG_DEN_LAYER_PTRS slots per residual layer -- slot j of layer l is entry MG_DEN_HEAD_PTRS + MG_DEN_LAYER_PTRS * l + j.
+ * Each slot is listed with the reference state_dict key it holds (under `diffusion.denoise_fn.`) and its shape. */
+#define MG_DEN_HEAD_PTRS 8
+#define MG_DEN_LAYER_PTRS 9
+enum mg_den_head_slot {
+    MG_DEN_IN_W = 0,   /* input_projection.0.conv.weight [C,M,1] */
+    MG_DEN_IN_B = 1,   /* input_projection.0.conv.bias [C]       */
+    MG_DEN_MLP0_W = 2, /* mlp.0.linear.weight [4C,C]             */
+    MG_DEN_MLP2_W = 3, /* mlp.2.linear.weight [C,4C]             */
+    MG_DEN_SKIP_W = 4, /* skip_projection.conv.weight [C,C,1]    */
+    MG_DEN_SKIP_B = 5, /* skip_projection.conv.bias [C]          */
+    MG_DEN_OUT_W = 6,  /* output_projection.conv.weight [M,C,1]  */
+    MG_DEN_OUT_B = 7   /* output_projection.conv.bias [M]        */
+};
+enum mg_den_layer_slot { /* keys under residual_layers.<l>. */
+    MG_DEN_L_CONV_W = 0,  /* conv_layer.conv.weight [2C,C,3]             */
+    MG_DEN_L_CONV_B = 1,  /* conv_layer.conv.bias [2C]                   */
+    MG_DEN_L_DIFF_W = 2,  /* diffusion_projection.linear.weight [C,C]    */
+    MG_DEN_L_COND_W = 3,  /* conditioner_projection.conv.weight [C,H,1]  */
+    MG_DEN_L_COND_B = 4,  /* conditioner_projection.conv.bias [C]        */
+    MG_DEN_L_OUT_W = 5,   /* output_projection.conv.weight [2C,C,1]      */
+    MG_DEN_L_OUT_B = 6,   /* output_projection.conv.bias [2C]            */
+    MG_DEN_L_SPK_W = 7,   /* speaker_projection.linear.weight [C,H]; NULL unless multi_speaker */
+    MG_DEN_L_RESERVED = 8 /* NULL */
+};
 typedef struct {
     int32_t n_layers;      /* model.denoiser.residual_layers (20) */
     int32_t channels;      /* C: residual_channels (256)          */
@@ -193,9 +206,6 @@ typedef struct {
     int32_t mel_bins;      /* M: n_mel_channels (80)              */
     int32_t multi_speaker; /* 0/1                                 */
 } mg_denoiser_dims;
-
-#define MG_DEN_HEAD_PTRS 8
-#define MG_DEN_LAYER_PTRS 9
 
 /* flags for mg_denoiser_packed_floats / mg_denoiser_pack */
 #define MG_DEN_BACKWARD 1 /* also pack the transposed (data-gradient) forms mg_denoiser_bwd consumes */
@@ -331,9 +341,8 @@ int mg_denoiser_persist_status(const mg_denoiser_dims *d, const float *workspace
  * forward's workspace of a save_for_backward call on the same inputs; `bwd_workspace` has
  * mg_denoiser_bwd_workspace_floats() floats.  g_out [B, M, L] is dL/d(out).
  * grads: pointer table in the order of mg_denoiser_pack's weight table; every non-NULL entry
- * receives dL/dW (overwritten, not accumulated).  Every per-layer entry (j=0/1 conv_layer weight/bias, j=2
- * diffusion_projection, j=3/4 conditioner_projection weight/bias, j=5/6 output_projection weight/bias, j=7
- * speaker_projection) must be the layer's slice of one contiguous [n_layers, ...] buffer: the layer loop only
+ * receives dL/dW (overwritten, not accumulated).  Every per-layer entry (MG_DEN_L_CONV_W .. MG_DEN_L_SPK_W)
+ * must be the layer's slice of one contiguous [n_layers, ...] buffer: the layer loop only
  * runs the two data-gradient GEMMs per layer and keeps their results (0.5 GB of the workspace at B=8, L=1000);
  * all weight and bias gradients are then produced by a few launches grouped over the layer axis.
  * d_x_t [B,M,L], d_cond [B,H,L], d_spk [B,H] may be NULL when not needed. */
@@ -348,7 +357,7 @@ int mg_denoiser_bwd(const mg_denoiser_dims *d, const float *packed, const float 
 int mg_denoiser_bwd_status(const mg_denoiser_dims *d, const float *bwd_workspace, int B, int L, unsigned *host_out4,
                            void *stream);
 /* Same; conv3_grads_done (a hipEvent_t, or NULL) is recorded on `stream` right behind the launches that produce the
- * conv_layer weight and bias gradients of all layers (entries j=0/1: a third of the generator's gradient bytes), 0.6 ms
+ * conv_layer weight and bias gradients of all layers (MG_DEN_L_CONV_W / _CONV_B: a third of the generator's gradient bytes), 0.6 ms
  * of GPU work before the last launch of the backward at B=8, L=1000 -- a data-parallel caller starts the all-reduce of
  * that slice behind the event while the remaining gradients are still being computed (train.py has no such exchange:
  * the reference is single-device). */

@@ -8,41 +8,26 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-EXPORTS = (
-    "mg_version", "mg_error_string",
-    "mg_conv_packed_floats", "mg_conv_pack", "mg_conv_pack_at", "mg_conv1d_fwd", "mg_conv1d_fwd_ex", "mg_conv1d_fwd_split",
-    "mg_upsample_zero_act", "mg_diffuse_trace_bwd", "mg_bgemm", "mg_softmax_rows_fwd", "mg_softmax_rows_bwd", "mg_layernorm_cm_train_fwd",
-    "mg_layernorm_cm_bwd", "mg_bn_stats", "mg_bn_act_fwd", "mg_bn_act_bwd_reduce", "mg_bn_act_bwd_apply", "mg_conv_transpose_packed_floats", "mg_conv_transpose_pack", "mg_conv_transpose1d_fwd",
-    "mg_conv1d_wgrad_scratch_floats", "mg_conv1d_wgrad", "mg_conv1d_wgrad_strided", "mg_conv1d_wgrad_grouped",
-    "mg_conv1d_wgrad_grouped_scratch_floats", "mg_conv1d_wgrad_grouped_bias", "mg_rowsum",
-    "mg_diffuse_fwd", "mg_posterior_sample_fwd", "mg_posterior_sample_bwd", "mg_spec_affine", "mg_transpose_bml",
-    "mg_denoiser_packed_floats", "mg_denoiser_pack", "mg_denoiser_workspace_floats", "mg_denoiser_fwd",
-    "mg_denoiser_bwd_workspace_floats", "mg_denoiser_bwd", "mg_denoiser_bwd_staged", "mg_denoiser_bwd_status",
-    "mg_profile_begin", "mg_profile_begin_sampled", "mg_profile_end", "mg_transpose_bml_strided", "mg_act_bwd", "mg_upsample_zero",
-    "mg_step_mlp_fwd", "mg_step_mlp_bwd", "mg_linear_small_fwd", "mg_linear_small_bwd",
-    "mg_loss_sum", "mg_loss_grad", "mg_mel_l1_fwd", "mg_mel_l1_bwd", "mg_attention_fwd", "mg_attention_fwd_f16", "mg_layernorm_cm_fwd",
-    "mg_length_regulate_fwd", "mg_length_regulate_bwd", "mg_word_pool_fwd", "mg_word_pool_bwd", "mg_mapping_mask",
-    "mg_rel_coef", "mg_resblock_fwd", "mg_gate_bwd", "mg_mish_fwd", "mg_mish_bwd", "mg_step_embed",
-    "mg_denoiser_psample", "mg_denoiser_cond_project", "mg_denoiser_step_vectors_floats", "mg_denoiser_step_vectors", "mg_denoiser_persist_status", "mg_persist_error", "mg_denoiser_fwd_pair",
-    "mg_denoiser_fwd_plan",
-    "mg_grad_norm_scratch_floats", "mg_grad_norm", "mg_adam_flat", "mg_adam_flat_dev",
-    "mg_multi_loss_scratch_floats", "mg_multi_loss_fwd", "mg_multi_loss_bwd",
-    "mg_rel_attention_fwd", "mg_w2p_attention_fwd", "mg_embed_cm", "mg_variance_head", "mg_duration_head",
-    "mg_posenc_add",
-    "mg_rel_attention_train_fwd", "mg_rel_attention_bwd_ws_floats", "mg_rel_attention_bwd", "mg_w2p_attention_bwd_ws_floats",
-    "mg_w2p_attention_bwd", "mg_embed_cm_bwd", "mg_variance_head_bwd", "mg_duration_head_bwd", "mg_posenc_add_bwd",
-    "mg_dropout_apply",
-    "mg_conv_transpose1d_fwd_slice", "mg_conv1d_reflect_fwd", "mg_conv1x1_fwd_strided", "mg_melgan_stack_fwd",
-    "mg_melgan_stack_tile", "mg_stft_fwd", "mg_stft_mel", "mg_istft", "mg_ds_fbank", "mg_ds_conv2d", "mg_ds_head",
-)
-
-
 class MixganHipError(RuntimeError):
     pass
 
 
-MG_LOSS_MAX_TERMS = 16
-MG_LOSS_GROUPS = 4
+# ---- constants of include/mixgan_hip.h under their header names.  tests/test_host_cpu.py holds every MG_* name of this
+# module to the header's value, and _signatures() to its prototypes.
+MG_OK, MG_ERR_ARG, MG_ERR_SHAPE, MG_ERR_WORKSPACE = 0, -1, -2, -3
+MG_ACT_NONE, MG_ACT_RELU, MG_ACT_LRELU02, MG_ACT_TANH, MG_ACT_LRELU = range(5)
+MG_PACK_PLAIN, MG_PACK_GATE, MG_PACK_DGRAD, MG_PACK_TPOSE, MG_PACK_PLAIN16, MG_PACK_GATE16 = range(6)
+MG_DEN_BACKWARD, MG_DEN_SPLIT, MG_DEN_P16, MG_DEN_JOBS_RESIDENT = 1, 2, 4, 8      # mg_denoiser_pack flags
+MG_FWD_SAVE, MG_FWD_SPLIT, MG_FWD_P16 = 1, 2, 4                                   # mg_denoiser_fwd modes
+MG_PLAN_PER_LAYER, MG_PLAN_SINGLE = 0, 1                                          # mg_fwd_plan.path
+MG_PLAN_PERSIST, MG_PLAN_PERSIST16, MG_PLAN_TEAM16 = 0, 1, 2                      # mg_fwd_plan.family
+# the denoiser's weight / gradient pointer table: head slots, then MG_DEN_LAYER_PTRS slots per residual layer
+MG_DEN_HEAD_PTRS, MG_DEN_LAYER_PTRS = 8, 9
+(MG_DEN_IN_W, MG_DEN_IN_B, MG_DEN_MLP0_W, MG_DEN_MLP2_W, MG_DEN_SKIP_W, MG_DEN_SKIP_B, MG_DEN_OUT_W,
+ MG_DEN_OUT_B) = range(MG_DEN_HEAD_PTRS)
+(MG_DEN_L_CONV_W, MG_DEN_L_CONV_B, MG_DEN_L_DIFF_W, MG_DEN_L_COND_W, MG_DEN_L_COND_B, MG_DEN_L_OUT_W, MG_DEN_L_OUT_B,
+ MG_DEN_L_SPK_W, MG_DEN_L_RESERVED) = range(MG_DEN_LAYER_PTRS)
+MG_LOSS_MAX_TERMS, MG_LOSS_GROUPS = 16, 4
 
 
 class LossTerm(ctypes.Structure):
@@ -89,17 +74,16 @@ def lib():
                 "libmixgan_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C mixgan-tts_amd/csrc`. There is no CPU fallback." % path)
         L = ctypes.CDLL(path)
-        L.mg_error_string.restype = ctypes.c_char_p
         _declare(L)
         _LIB = L
     return _LIB
 
 
-def _declare(L):
-    """argtypes/restype for every export of include/mixgan_hip.h."""
+def _signatures():
+    """name -> (restype, argtypes) for every export of include/mixgan_hip.h."""
     vp, i, f, sz, lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
     dp = ctypes.POINTER(DenoiserDims)
-    sig = {
+    return {
         "mg_version": (i, []),
         "mg_error_string": (ctypes.c_char_p, [i]),
         "mg_conv_packed_floats": (sz, [i, i, i, i]),
@@ -129,8 +113,8 @@ def _declare(L):
         "mg_conv_pack_at": (i, [vp, vp, i, i, i, i, i, i, vp]),
         "mg_conv1d_wgrad_scratch_floats": (sz, [i, i, i]),
         "mg_conv1d_wgrad": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, vp]),
-        "mg_conv1d_wgrad_strided": (i, [vp, ctypes.c_long, vp, ctypes.c_long, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, vp]),
-        "mg_rowsum": (i, [vp, ctypes.c_long, i, i, i, vp, vp, f, i, vp]),
+        "mg_conv1d_wgrad_strided": (i, [vp, lg, vp, lg, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, vp]),
+        "mg_rowsum": (i, [vp, lg, i, i, i, vp, vp, f, i, vp]),
         "mg_conv1d_wgrad_grouped_scratch_floats": (sz, [i, i, i, i]),
         "mg_conv1d_wgrad_grouped": (i, [vp, lg, lg, vp, lg, lg, vp, lg, vp, i, i, i, i, i, i, i, i, i, f, i, vp]),
         "mg_conv1d_wgrad_grouped_bias": (i, [vp, lg, lg, vp, lg, lg, vp, lg, vp, lg, vp, i, i, i, i, i, i, i, i, i, f, i, vp]),
@@ -143,7 +127,7 @@ def _declare(L):
         "mg_denoiser_fwd": (i, [dp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, vp]),
         "mg_denoiser_fwd_pair": (i, [dp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, i, i, vp]),
         "mg_denoiser_fwd_plan": (i, [dp, i, i, i, i, i, ctypes.POINTER(FwdPlan)]),
-        "mg_transpose_bml_strided": (i, [vp] * 5 + [i, i, i, i, i, ctypes.c_long, vp]),
+        "mg_transpose_bml_strided": (i, [vp] * 5 + [i, i, i, i, i, lg, vp]),
         "mg_act_bwd": (i, [vp, vp, vp, i, sz, vp]),
         "mg_upsample_zero": (i, [vp, vp, i, i, i, i, vp]),
         "mg_step_mlp_fwd": (i, [vp] * 8 + [i, i, i, i, vp]),
@@ -215,7 +199,13 @@ def _declare(L):
         "mg_ds_conv2d": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]),
         "mg_ds_head": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
     }
-    for name, (res, args) in sig.items():
+
+
+EXPORTS = tuple(_signatures())
+
+
+def _declare(L):
+    for name, (res, args) in _signatures().items():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

@@ -211,6 +211,8 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
     for (int i = 0; i < MG_DEN_HEAD_PTRS; ++i)
         if (!w[i]) return MG_ERR_ARG;
 
+    auto layer = [&](int l) { return w + MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS; };
+
     static thread_local PackJob jobs[MG_DEN_MAX_JOBS];
     int n = 0;
     unsigned blocks = 0;
@@ -242,57 +244,58 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
         push(src, dst, total, pd);
     };
     copy(o.freq, freq, C / 2);
-    pack(w[0], o.in_w, C, M, 1, MG_PACK_PLAIN);
-    copy(o.in_b, w[1], C);
-    copy(o.mlp0, w[2], (size_t)4 * C * C);
-    copy(o.mlp2, w[3], (size_t)4 * C * C);
-    pack(w[4], o.skip_w, C, C, 1, MG_PACK_PLAIN);
-    copy(o.skip_b, w[5], C);
-    pack(w[6], o.out_w, M, C, 1, MG_PACK_PLAIN);
-    copy(o.out_b, w[7], M);
+    pack(w[MG_DEN_IN_W], o.in_w, C, M, 1, MG_PACK_PLAIN);
+    copy(o.in_b, w[MG_DEN_IN_B], C);
+    copy(o.mlp0, w[MG_DEN_MLP0_W], (size_t)4 * C * C);
+    copy(o.mlp2, w[MG_DEN_MLP2_W], (size_t)4 * C * C);
+    pack(w[MG_DEN_SKIP_W], o.skip_w, C, C, 1, MG_PACK_PLAIN);
+    copy(o.skip_b, w[MG_DEN_SKIP_B], C);
+    pack(w[MG_DEN_OUT_W], o.out_w, M, C, 1, MG_PACK_PLAIN);
+    copy(o.out_b, w[MG_DEN_OUT_B], M);
     for (int l = 0; l < d->n_layers; ++l) {
-        const float *const *lw = w + MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS;
+        const float *const *lw = layer(l);
         const size_t lp = o.layers + (size_t)l * o.layer_stride;
-        for (int j = 0; j < 7; ++j)
+        for (int j = MG_DEN_L_CONV_W; j <= MG_DEN_L_OUT_B; ++j)   // (push rejects a missing speaker weight)
             if (!lw[j]) return MG_ERR_ARG;
-        pack(lw[0], lp + o.l_w3, 2 * C, C, 3, MG_PACK_GATE);
-        copy(lp + o.l_b3, lw[1], 2 * C);
-        copy(lp + o.l_wd, lw[2], (size_t)C * C);
-        pack(lw[3], lp + o.l_wc, C, H, 1, MG_PACK_PLAIN);
-        copy(lp + o.l_bc, lw[4], C);
-        pack(lw[5], lp + o.l_wo, 2 * C, C, 1, MG_PACK_PLAIN);
-        copy(lp + o.l_bo, lw[6], 2 * C);
-        if (d->multi_speaker) copy(lp + o.l_wp, lw[7], (size_t)C * H);
+        pack(lw[MG_DEN_L_CONV_W], lp + o.l_w3, 2 * C, C, 3, MG_PACK_GATE);
+        copy(lp + o.l_b3, lw[MG_DEN_L_CONV_B], 2 * C);
+        copy(lp + o.l_wd, lw[MG_DEN_L_DIFF_W], (size_t)C * C);
+        pack(lw[MG_DEN_L_COND_W], lp + o.l_wc, C, H, 1, MG_PACK_PLAIN);
+        copy(lp + o.l_bc, lw[MG_DEN_L_COND_B], C);
+        pack(lw[MG_DEN_L_OUT_W], lp + o.l_wo, 2 * C, C, 1, MG_PACK_PLAIN);
+        copy(lp + o.l_bo, lw[MG_DEN_L_OUT_B], 2 * C);
+        if (d->multi_speaker) copy(lp + o.l_wp, lw[MG_DEN_L_SPK_W], (size_t)C * H);
     }
     if (with_backward) {
         // data-gradient (transposed, tap-flipped) packs for mg_denoiser_bwd
-        pack(w[0], o.in_wT, C, M, 1, MG_PACK_DGRAD);
-        pack(w[4], o.skip_wT, C, C, 1, MG_PACK_DGRAD);
-        pack(w[6], o.out_wT, M, C, 1, MG_PACK_DGRAD);
+        pack(w[MG_DEN_IN_W], o.in_wT, C, M, 1, MG_PACK_DGRAD);
+        pack(w[MG_DEN_SKIP_W], o.skip_wT, C, C, 1, MG_PACK_DGRAD);
+        pack(w[MG_DEN_OUT_W], o.out_wT, M, C, 1, MG_PACK_DGRAD);
         const int Qtot = d->n_layers * C / 8;
         for (int l = 0; l < d->n_layers; ++l) {
-            const float *const *lw = w + MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS;
+            const float *const *lw = layer(l);
             const size_t bp = o.blayers + (size_t)l * o.blayer_stride;
-            pack(lw[3], o.wc_allT, C, H, 1, MG_PACK_DGRAD, l * (C / 8), Qtot);
-            pack(lw[0], bp + o.bl_w3T, 2 * C, C, 3, MG_PACK_DGRAD);
-            pack(lw[5], bp + o.bl_woT, 2 * C, C, 1, MG_PACK_DGRAD);
+            pack(lw[MG_DEN_L_COND_W], o.wc_allT, C, H, 1, MG_PACK_DGRAD, l * (C / 8), Qtot);
+            pack(lw[MG_DEN_L_CONV_W], bp + o.bl_w3T, 2 * C, C, 3, MG_PACK_DGRAD);
+            pack(lw[MG_DEN_L_OUT_W], bp + o.bl_woT, 2 * C, C, 1, MG_PACK_DGRAD);
         }
     }
     if (flags & MG_DEN_P16) {
         if (C != RB_C || H != RB_C) return MG_ERR_SHAPE;
-        pack(w[0], o.in_w16, C, M, 1, MG_PACK_PLAIN16);
-        pack(w[4], o.skip_w16, C, C, 1, MG_PACK_PLAIN16);
-        pack(w[6], o.out_w16, M, C, 1, MG_PACK_PLAIN16);
+        pack(w[MG_DEN_IN_W], o.in_w16, C, M, 1, MG_PACK_PLAIN16);
+        pack(w[MG_DEN_SKIP_W], o.skip_w16, C, C, 1, MG_PACK_PLAIN16);
+        pack(w[MG_DEN_OUT_W], o.out_w16, M, C, 1, MG_PACK_PLAIN16);
         for (int l = 0; l < d->n_layers; ++l) {
-            const float *const *lw = w + MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS;
+            const float *const *lw = layer(l);
             const size_t pp = o.p16layers + (size_t)l * o.p16layer_stride;
-            pack(lw[3], pp + o.p_wc, C, H, 1, MG_PACK_PLAIN16);
-            pack(lw[0], pp + o.p_w3, 2 * C, C, 3, MG_PACK_GATE16);
-            pack(lw[5], pp + o.p_wo, 2 * C, C, 1, MG_PACK_PLAIN16);
+            pack(lw[MG_DEN_L_COND_W], pp + o.p_wc, C, H, 1, MG_PACK_PLAIN16);
+            pack(lw[MG_DEN_L_CONV_W], pp + o.p_w3, 2 * C, C, 3, MG_PACK_GATE16);
+            pack(lw[MG_DEN_L_OUT_W], pp + o.p_wo, 2 * C, C, 1, MG_PACK_PLAIN16);
             // the [NL * C, H] matrix of all conditioner projections: 32-row blocks are the outermost index of a pack,
             // so the layers' own packs, one behind the other, ARE its pack (C is a multiple of the 128-row tile)
-            pack(lw[3], o.wc_all + (size_t)l * mg_conv_packed_floats(C, H, 1, MG_PACK_PLAIN), C, H, 1, MG_PACK_PLAIN);
-            copy(o.bc_all + (size_t)l * C, lw[4], C);
+            pack(lw[MG_DEN_L_COND_W], o.wc_all + (size_t)l * mg_conv_packed_floats(C, H, 1, MG_PACK_PLAIN), C, H, 1,
+                 MG_PACK_PLAIN);
+            copy(o.bc_all + (size_t)l * C, lw[MG_DEN_L_COND_B], C);
         }
     }
     if (rc != MG_OK) return rc;
@@ -310,7 +313,7 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
     if (flags & MG_DEN_SPLIT) {
         if (C != RB_C || H != RB_C) return MG_ERR_SHAPE;
         for (int l = 0; l < d->n_layers; ++l) {
-            const float *const *lw = w + MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS;
+            const float *const *lw = layer(l);
             float *sp = packed + o.slayers + (size_t)l * o.slayer_stride;
             auto pk = [&](const float *src, size_t off, int Co, int Ci, int K, int gate) {
                 const int MB = Co / 32;
@@ -319,9 +322,9 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
                 hipLaunchKernelGGL(pack_split_kernel, dim3(blocks), dim3(256), 0, st, src,
                                    reinterpret_cast<__bf16 *>(sp + off), Co, Ci, K, MB, gate);
             };
-            pk(lw[3], o.sl_wc, C, H, 1, 0);
-            pk(lw[0], o.sl_w3, 2 * C, C, 3, 1);
-            pk(lw[5], o.sl_wo, 2 * C, C, 1, 0);
+            pk(lw[MG_DEN_L_COND_W], o.sl_wc, C, H, 1, 0);
+            pk(lw[MG_DEN_L_CONV_W], o.sl_w3, 2 * C, C, 3, 1);
+            pk(lw[MG_DEN_L_OUT_W], o.sl_wo, 2 * C, C, 1, 0);
             MG_LAUNCH_CHECK();
         }
     }

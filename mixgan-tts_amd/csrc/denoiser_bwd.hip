@@ -133,18 +133,6 @@ struct EpiDhBwd {
     }
 };
 
-// thin shim over the exported weight-gradient entry point (kernel lives in conv_api.hip)
-struct WgradShape {
-    int B, Co, Ci, Ldy, Lx, K, stride, pad;
-    long dy_bs, x_bs;
-};
-static int wgrad_launch(const WgradShape &s, const float *dy, const float *x, const float *xvec, float *dw,
-                        float *scratch, float alpha, int accumulate, hipStream_t st)
-{
-    return mg_conv1d_wgrad_strided(dy, s.dy_bs, x, s.x_bs, xvec, dw, scratch, s.B, s.Co, s.Ci, s.Ldy, s.Lx, s.K, s.stride,
-                                   s.pad, alpha, accumulate, st);
-}
-
 // db (optional): the bias gradients [G][db_gs] from the same pass over dy
 static int wgrad_grouped(int G, const float *dy, long dy_bs, long dy_gs, const float *x, long x_bs, long x_gs, float *dw,
                          long dw_gs, float *scratch, int B, int Co, int Ci, int L, int K, int pad, hipStream_t st,
@@ -165,12 +153,6 @@ static __global__ void bias_scatter_kernel(const float *__restrict__ top, const 
     if (i >= NL * 2 * C) return;
     const int l = i / (2 * C), r = i - l * 2 * C;
     out[i] = r < C ? top[l * C + r] : bottom[r - C];
-}
-
-static int rowsum(const float *in, long in_bs, int B, int R, int L, float *out_r, float *out_br, float alpha,
-                  hipStream_t st)
-{
-    return mg_rowsum(in, in_bs, B, R, L, out_r, out_br, alpha, 0, st);
 }
 
 // ------------------------------------------------------------------------------------------ API
@@ -213,26 +195,35 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
     const DenWs w = den_ws(d, B, L, 1);
     const DenBws bw = den_bws(d, B, L);
     if (bws_floats < bw.total) return MG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float *const *lg0 = grads + MG_DEN_HEAD_PTRS;
-    auto LG = [&](int l, int j) { return lg0[(size_t)l * MG_DEN_LAYER_PTRS + j]; };
-    // batched outputs must be contiguous across layers
-    for (int l = 1; l < NL; ++l) {
-        if (LG(0, 0) && LG(l, 0) != LG(0, 0) + (size_t)l * 2 * C * C * 3) return MG_ERR_ARG;
-        if (LG(0, 1) && LG(l, 1) != LG(0, 1) + (size_t)l * 2 * C) return MG_ERR_ARG;
-        if (LG(0, 2) && LG(l, 2) != LG(0, 2) + (size_t)l * C * C) return MG_ERR_ARG;
-        if (LG(0, 3) && LG(l, 3) != LG(0, 3) + (size_t)l * C * H) return MG_ERR_ARG;
-        if (LG(0, 4) && LG(l, 4) != LG(0, 4) + (size_t)l * C) return MG_ERR_ARG;
-        if (LG(0, 5) && LG(l, 5) != LG(0, 5) + (size_t)l * 2 * C * C) return MG_ERR_ARG;
-        if (LG(0, 6) && LG(l, 6) != LG(0, 6) + (size_t)l * 2 * C) return MG_ERR_ARG;
-        if (d->multi_speaker && LG(0, 7) && LG(l, 7) != LG(0, 7) + (size_t)l * C * H) return MG_ERR_ARG;
+    auto LG = [&](int l, int j) { return grads[MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS + j]; };
+    // batched outputs must be contiguous across layers: layer l's pointer is layer 0's plus l x the layer's floats
+    const struct {
+        int slot;
+        size_t floats;
+    } per_layer[] = {{MG_DEN_L_CONV_W, (size_t)2 * C * C * 3}, {MG_DEN_L_CONV_B, (size_t)2 * C},
+                     {MG_DEN_L_DIFF_W, (size_t)C * C},         {MG_DEN_L_COND_W, (size_t)C * H},
+                     {MG_DEN_L_COND_B, (size_t)C},             {MG_DEN_L_OUT_W, (size_t)2 * C * C},
+                     {MG_DEN_L_OUT_B, (size_t)2 * C},          {MG_DEN_L_SPK_W, (size_t)C * H}};
+    for (const auto &k : per_layer) {
+        if (!LG(0, k.slot) || (k.slot == MG_DEN_L_SPK_W && !d->multi_speaker)) continue;
+        for (int l = 1; l < NL; ++l)
+            if (LG(l, k.slot) != LG(0, k.slot) + l * k.floats) return MG_ERR_ARG;
     }
+    // from here on only layer 0's pointers: the [NL, ...] arrays
+    float *const dW3 = LG(0, MG_DEN_L_CONV_W), *const db3 = LG(0, MG_DEN_L_CONV_B), *const dWd = LG(0, MG_DEN_L_DIFF_W);
+    float *const dWc = LG(0, MG_DEN_L_COND_W), *const dbc = LG(0, MG_DEN_L_COND_B), *const dWo = LG(0, MG_DEN_L_OUT_W);
+    float *const dbo = LG(0, MG_DEN_L_OUT_B), *const dWp = LG(0, MG_DEN_L_SPK_W);
+    hipStream_t st = (hipStream_t)stream;
     const size_t CL = (size_t)C * L;
     float *dout = bws + bw.dout, *dz_all = bws + bw.dz_all, *dx_all = bws + bw.dx_all, *dh_all = bws + bw.dh_all;
     float *dy = bws + bw.dy;
     float *dx0 = bws + bw.dx0, *scr = bws + bw.scratch;
     const long dz_bs = (long)((size_t)NL * 2 * CL), dx_bs = (long)((size_t)(NL + 1) * CL);
     const float rsNL = 1.0f / sqrtf((float)NL);
+    // weight gradient of a 1x1 convolution, dense [B, Co, L] (x) [B, Ci, L] (the kernel lives in conv_api.hip)
+    auto wgrad1x1 = [&](const float *dy, const float *x, float *dw, int Co, int Ci, float alpha) {
+        return mg_conv1d_wgrad_strided(dy, 0, x, 0, nullptr, dw, scr, B, Co, Ci, L, L, 1, 1, 0, alpha, 0, st);
+    };
 
     // ---- head: output_projection, ReLU, skip_projection (model/modules.py:441-444) ------------
     {
@@ -240,21 +231,15 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
         EpiBiasAct::Params ep{dy, nullptr, nullptr, 1.f, C, MG_ACT_NONE, 0, 0, ws + w.y, 0.f};
         MG_TRY(conv_launch<EpiBiasAct>(s, g_out, nullptr, packed + o.out_wT, ep, st));
     }
-    if (grads[6]) {
-        WgradShape s{B, M, C, L, L, 1, 1, 0, 0, 0};
-        MG_TRY(wgrad_launch(s, g_out, ws + w.y, nullptr, grads[6], scr, 1.f, 0, st));
-    }
-    if (grads[7]) MG_TRY(rowsum(g_out, 0, B, M, L, grads[7], nullptr, 1.f, st));
+    if (grads[MG_DEN_OUT_W]) MG_TRY(wgrad1x1(g_out, ws + w.y, grads[MG_DEN_OUT_W], M, C, 1.f));
+    if (grads[MG_DEN_OUT_B]) MG_TRY(mg_rowsum(g_out, 0, B, M, L, grads[MG_DEN_OUT_B], nullptr, 1.f, 0, st));
     {
         ConvShape s{B, C, L, L, 1, 1, 0, C, 0, 0};
         EpiBiasAct::Params ep{dout + CL, nullptr, nullptr, rsNL, C, MG_ACT_NONE, 0, (long)(2 * CL), nullptr, 0.f};
         MG_TRY(conv_launch<EpiBiasAct>(s, dy, nullptr, packed + o.skip_wT, ep, st));
     }
-    if (grads[4]) {
-        WgradShape s{B, C, C, L, L, 1, 1, 0, 0, 0};
-        MG_TRY(wgrad_launch(s, dy, ws + w.skip, nullptr, grads[4], scr, rsNL, 0, st));
-    }
-    if (grads[5]) MG_TRY(rowsum(dy, 0, B, C, L, grads[5], nullptr, 1.f, st));
+    if (grads[MG_DEN_SKIP_W]) MG_TRY(wgrad1x1(dy, ws + w.skip, grads[MG_DEN_SKIP_W], C, C, rsNL));
+    if (grads[MG_DEN_SKIP_B]) MG_TRY(mg_rowsum(dy, 0, B, C, L, grads[MG_DEN_SKIP_B], nullptr, 1.f, 0, st));
     {   // the last layer's x output is unused: dx_NL = 0 (in dout's top half and in slot NL of dx_all)
         hipError_t e = hipMemset2DAsync(dout, 2 * CL * sizeof(float), 0, CL * sizeof(float), B, st);
         if (e != hipSuccess) return (int)e;
@@ -318,31 +303,31 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
         const long act_gs = (long)w.act_stride;
         // The bias gradients (row sums of dz, of the dx slots and of dskip over batch and frames) come out of the
         // weight-gradient launches that read those rows anyway (mg_conv1d_wgrad_grouped_bias).
-        const bool fold3 = LG(0, 0) && LG(0, 1), foldo = LG(0, 5) && LG(0, 6);
-        if (LG(0, 0))   // k=3 conv: dW3_l = dz_l (*) h_l;  db3_l = rowsum(dz_l)
-            MG_TRY(wgrad_grouped(NL, dz_all, dz_bs, (long)(2 * CL), h_all, (long)CL, act_gs, LG(0, 0), (long)2 * C * C * 3, scr,
-                                 B, 2 * C, C, L, 3, 1, st, fold3 ? LG(0, 1) : nullptr, (long)(2 * C)));
-        if (LG(0, 1) && !fold3) MG_TRY(rowsum(dz_all, 0, B, NL * 2 * C, L, LG(0, 1), nullptr, 1.f, st));
+        const bool fold3 = dW3 && db3, foldo = dWo && dbo;
+        if (dW3)   // k=3 conv: dW3_l = dz_l (*) h_l;  db3_l = rowsum(dz_l)
+            MG_TRY(wgrad_grouped(NL, dz_all, dz_bs, (long)(2 * CL), h_all, (long)CL, act_gs, dW3, (long)2 * C * C * 3, scr,
+                                 B, 2 * C, C, L, 3, 1, st, fold3 ? db3 : nullptr, (long)(2 * C)));
+        if (db3 && !fold3) MG_TRY(mg_rowsum(dz_all, 0, B, NL * 2 * C, L, db3, nullptr, 1.f, 0, st));
         if (conv3_grads_done) {   // the largest gradient array is final from here on: its exchange may start
             const hipError_t ee = hipEventRecord((hipEvent_t)conv3_grads_done, st);
             if (ee != hipSuccess) return (int)ee;
         }
-        if (LG(0, 5)) {   // output conv: rows < C see dx_l (slot l+1), rows >= C the layer-independent dskip
-            MG_TRY(wgrad_grouped(NL, dx_all + CL, dx_bs, (long)CL, g_all, (long)CL, act_gs, LG(0, 5), (long)2 * C * C, scr, B, C,
-                                 C, L, 1, 0, st, foldo ? LG(0, 6) : nullptr, (long)(2 * C)));
-            MG_TRY(wgrad_grouped(NL, dout + CL, (long)(2 * CL), 0, g_all, (long)CL, act_gs, LG(0, 5) + (size_t)C * C,
-                                 (long)2 * C * C, scr, B, C, C, L, 1, 0, st, foldo ? LG(0, 6) + C : nullptr, (long)(2 * C)));
+        if (dWo) {   // output conv: rows < C see dx_l (slot l+1), rows >= C the layer-independent dskip
+            MG_TRY(wgrad_grouped(NL, dx_all + CL, dx_bs, (long)CL, g_all, (long)CL, act_gs, dWo, (long)2 * C * C, scr, B, C,
+                                 C, L, 1, 0, st, foldo ? dbo : nullptr, (long)(2 * C)));
+            MG_TRY(wgrad_grouped(NL, dout + CL, (long)(2 * CL), 0, g_all, (long)CL, act_gs, dWo + (size_t)C * C,
+                                 (long)2 * C * C, scr, B, C, C, L, 1, 0, st, foldo ? dbo + C : nullptr, (long)(2 * C)));
         }
-        if (LG(0, 6) && !foldo) {
-            MG_TRY(rowsum(dx_all + CL, dx_bs, B, NL * C, L, bws + bw.btop, nullptr, 1.f, st));
-            MG_TRY(rowsum(dout + CL, (long)(2 * CL), B, C, L, bws + bw.bbot, nullptr, 1.f, st));
+        if (dbo && !foldo) {
+            MG_TRY(mg_rowsum(dx_all + CL, dx_bs, B, NL * C, L, bws + bw.btop, nullptr, 1.f, 0, st));
+            MG_TRY(mg_rowsum(dout + CL, (long)(2 * CL), B, C, L, bws + bw.bbot, nullptr, 1.f, 0, st));
             hipLaunchKernelGGL(bias_scatter_kernel, dim3(mg_cdiv(NL * 2 * C, 256)), dim3(256), 0, st, bws + bw.btop,
-                               bws + bw.bbot, LG(0, 6), NL, C);
+                               bws + bw.bbot, dbo, NL, C);
             MG_LAUNCH_CHECK();
         }
         // d(Wd s)_l = sqrt2 * sum_frames of the dx layer l produced (slot l): [B][NL*C] per-sample sums
         // (the step vector enters h and the residual, model/blocks.py:1166)
-        MG_TRY(rowsum(dx_all, dx_bs, B, NL * C, L, nullptr, bws + bw.dd_all, 1.41421356237309504880f, st));
+        MG_TRY(mg_rowsum(dx_all, dx_bs, B, NL * C, L, nullptr, bws + bw.dd_all, 1.41421356237309504880f, 0, st));
     }
 
     // ---- input projection + ReLU (model/modules.py:430-431) -----------------------------------
@@ -353,11 +338,8 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
                            1.41421356237309504880f, (int)CL, n);
         MG_LAUNCH_CHECK();
     }
-    if (grads[0]) {
-        WgradShape s{B, C, M, L, L, 1, 1, 0, 0, 0};
-        MG_TRY(wgrad_launch(s, dx0, x_t, nullptr, grads[0], scr, 1.f, 0, st));
-    }
-    if (grads[1]) MG_TRY(rowsum(dx0, 0, B, C, L, grads[1], nullptr, 1.f, st));
+    if (grads[MG_DEN_IN_W]) MG_TRY(wgrad1x1(dx0, x_t, grads[MG_DEN_IN_W], C, M, 1.f));
+    if (grads[MG_DEN_IN_B]) MG_TRY(mg_rowsum(dx0, 0, B, C, L, grads[MG_DEN_IN_B], nullptr, 1.f, 0, st));
     if (d_x_t) {
         ConvShape s{B, C, L, L, 1, 1, 0, M, 0, 0};
         EpiBiasAct::Params ep{d_x_t, nullptr, nullptr, 1.f, M, MG_ACT_NONE, 0, 0, nullptr, 0.f};
@@ -372,18 +354,16 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
     }
     // single-speaker: the bias gradients rowsum(dh) ride on the weight-gradient launch; multi-speaker needs the
     // per-sample sums too (the speaker vector enters h), which stay one row-sum launch that yields both
-    const bool foldc = LG(0, 3) && LG(0, 4) && !d->multi_speaker;
-    if (LG(0, 3)) {
-        if (foldc) {
-            MG_TRY(mg_conv1d_wgrad_grouped_bias(dh_all, 0, 0, cond, 0, 0, LG(0, 3), 0, LG(0, 4), 0, scr, 1, B, NL * C, H, L, L, 1,
+    const bool foldc = dWc && dbc && !d->multi_speaker;
+    if (dWc) {
+        if (foldc)
+            MG_TRY(mg_conv1d_wgrad_grouped_bias(dh_all, 0, 0, cond, 0, 0, dWc, 0, dbc, 0, scr, 1, B, NL * C, H, L, L, 1,
                                                 1, 0, 1.f, 0, st));
-        } else {
-            WgradShape s{B, NL * C, H, L, L, 1, 1, 0, 0, 0};
-            MG_TRY(wgrad_launch(s, dh_all, cond, nullptr, LG(0, 3), scr, 1.f, 0, st));
-        }
+        else
+            MG_TRY(wgrad1x1(dh_all, cond, dWc, NL * C, H, 1.f));
     }
-    if ((LG(0, 4) && !foldc) || d->multi_speaker)
-        MG_TRY(rowsum(dh_all, 0, B, NL * C, L, LG(0, 4), d->multi_speaker ? bws + bw.dhv_all : nullptr, 1.f, st));
+    if ((dbc && !foldc) || d->multi_speaker)
+        MG_TRY(mg_rowsum(dh_all, 0, B, NL * C, L, dbc, d->multi_speaker ? bws + bw.dhv_all : nullptr, 1.f, 0, st));
 
     // ---- step-embedding MLP and per-layer step / speaker projections (tiny, per sample) --------
     const float *lay0 = packed + o.layers;
@@ -406,18 +386,18 @@ extern "C" int mg_denoiser_bwd_staged(const mg_denoiser_dims *d, const float *pa
         return e == hipSuccess ? MG_OK : (int)e;
     };
     const float *dd_all = bws + bw.dd_all;
-    if (LG(0, 2)) MG_TRY(outer(dd_all, C, (long)NL * C, ws + w.s, LG(0, 2), NL, C, C));
+    if (dWd) MG_TRY(outer(dd_all, C, (long)NL * C, ws + w.s, dWd, NL, C, C));
     MG_TRY(linear_t(lay0 + o.l_wd, (long)o.layer_stride, dd_all, C, (long)NL * C, bws + bw.ds, NL, C, C));
     if (d->multi_speaker) {
         const float *dhv = bws + bw.dhv_all;  // [B, NL*C]
-        if (LG(0, 7)) MG_TRY(outer(dhv, C, (long)NL * C, spk, LG(0, 7), NL, C, H));
+        if (dWp) MG_TRY(outer(dhv, C, (long)NL * C, spk, dWp, NL, C, H));
         if (d_spk) MG_TRY(linear_t(lay0 + o.l_wp, (long)o.layer_stride, dhv, C, (long)NL * C, d_spk, NL, C, H));
     }
-    if (grads[3]) MG_TRY(outer(bws + bw.ds, 0, C, ws + w.h1, grads[3], 1, C, 4 * C));
+    if (grads[MG_DEN_MLP2_W]) MG_TRY(outer(bws + bw.ds, 0, C, ws + w.h1, grads[MG_DEN_MLP2_W], 1, C, 4 * C));
     MG_TRY(linear_t(packed + o.mlp2, 0, bws + bw.ds, 0, C, bws + bw.dm, 1, C, 4 * C));
     hipLaunchKernelGGL(mish_bwd_kernel, dim3(mg_cdiv(B * 4 * C, 256)), dim3(256), 0, st, bws + bw.dm, ws + w.h1pre,
                        bws + bw.da, B * 4 * C);
     MG_LAUNCH_CHECK();
-    if (grads[2]) MG_TRY(outer(bws + bw.da, 0, 4 * C, ws + w.emb, grads[2], 1, 4 * C, C));
+    if (grads[MG_DEN_MLP0_W]) MG_TRY(outer(bws + bw.da, 0, 4 * C, ws + w.emb, grads[MG_DEN_MLP0_W], 1, 4 * C, C));
     return MG_OK;
 }

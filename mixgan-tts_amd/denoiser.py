@@ -36,6 +36,45 @@ def _rank_salt(dev):
     return z ^ (z >> 29)
 
 
+# The pointer table of include/mixgan_hip.h (mg_denoiser_pack's weights, mg_denoiser_bwd's gradients) in slot order:
+# (slot, parameter of the Denoiser) for the head, (slot, parameter of one ResidualBlock) per layer.
+_HEAD_SLOTS = (
+    (_lib.MG_DEN_IN_W, lambda m: m.input_projection[0].conv.weight),
+    (_lib.MG_DEN_IN_B, lambda m: m.input_projection[0].conv.bias),
+    (_lib.MG_DEN_MLP0_W, lambda m: m.mlp[0].linear.weight),
+    (_lib.MG_DEN_MLP2_W, lambda m: m.mlp[2].linear.weight),
+    (_lib.MG_DEN_SKIP_W, lambda m: m.skip_projection.conv.weight),
+    (_lib.MG_DEN_SKIP_B, lambda m: m.skip_projection.conv.bias),
+    (_lib.MG_DEN_OUT_W, lambda m: m.output_projection.conv.weight),
+    (_lib.MG_DEN_OUT_B, lambda m: m.output_projection.conv.bias),
+)
+_LAYER_SLOTS = (
+    (_lib.MG_DEN_L_CONV_W, lambda blk: blk.conv_layer.conv.weight),
+    (_lib.MG_DEN_L_CONV_B, lambda blk: blk.conv_layer.conv.bias),
+    (_lib.MG_DEN_L_DIFF_W, lambda blk: blk.diffusion_projection.linear.weight),
+    (_lib.MG_DEN_L_COND_W, lambda blk: blk.conditioner_projection.conv.weight),
+    (_lib.MG_DEN_L_COND_B, lambda blk: blk.conditioner_projection.conv.bias),
+    (_lib.MG_DEN_L_OUT_W, lambda blk: blk.output_projection.conv.weight),
+    (_lib.MG_DEN_L_OUT_B, lambda blk: blk.output_projection.conv.bias),
+    (_lib.MG_DEN_L_SPK_W, lambda blk: blk.speaker_projection.linear.weight if blk.multi_speaker else None),
+    (_lib.MG_DEN_L_RESERVED, lambda blk: None),
+)
+assert [s for s, _ in _HEAD_SLOTS] == list(range(_lib.MG_DEN_HEAD_PTRS))
+assert [s for s, _ in _LAYER_SLOTS] == list(range(_lib.MG_DEN_LAYER_PTRS))
+
+
+def _cached(cache, key, limit, make, reusable=lambda v: True):
+    """cache[key] (an OrderedDict, least recently used first), made anew when missing or not reusable; the entry
+    becomes the most recent and the cache is trimmed to `limit` entries."""
+    v = cache.get(key)
+    if v is None or not reusable(v):
+        v = cache[key] = make()
+    cache.move_to_end(key)
+    while len(cache) > limit:
+        cache.popitem(last=False)
+    return v
+
+
 def raise_if_failed(owners=(), sync=False):
     """The single-launch kernels' failure word (include/mixgan_hip.h, mg_persist_error).  Polling it is a host memory
     read; sync=True first waits for the current stream, which makes the answer exact for everything launched so far.
@@ -103,18 +142,16 @@ class Denoiser(nn.Module):
         self.after_conv3_grads = None
 
     # ------------------------------------------------------------------ packed-weight cache
+    def _slots(self):
+        """(head parameters [MG_DEN_HEAD_PTRS], per-layer kinds [MG_DEN_LAYER_PTRS]): kinds[j][l] is slot j of layer l;
+        a kind the model does not have (speaker projection, the reserved slot) is a list of None."""
+        return ([get(self) for _, get in _HEAD_SLOTS],
+                [[get(blk) for blk in self.residual_layers] for _, get in _LAYER_SLOTS])
+
     def _weight_table(self):
-        """Pointer-table order of include/mixgan_hip.h (mg_denoiser_pack)."""
-        t = [self.input_projection[0].conv.weight, self.input_projection[0].conv.bias,
-             self.mlp[0].linear.weight, self.mlp[2].linear.weight,
-             self.skip_projection.conv.weight, self.skip_projection.conv.bias,
-             self.output_projection.conv.weight, self.output_projection.conv.bias]
-        for blk in self.residual_layers:
-            t += [blk.conv_layer.conv.weight, blk.conv_layer.conv.bias, blk.diffusion_projection.linear.weight,
-                  blk.conditioner_projection.conv.weight, blk.conditioner_projection.conv.bias,
-                  blk.output_projection.conv.weight, blk.output_projection.conv.bias,
-                  blk.speaker_projection.linear.weight if self.multi_speaker else None, None]
-        return t
+        """Pointer-table order of include/mixgan_hip.h (mg_denoiser_pack): the head, then layer by layer."""
+        head, kinds = self._slots()
+        return head + [p for layer in zip(*kinds) for p in layer]
 
     def packed_weights(self, with_backward=False):
         """The MFMA-ordered weight blob: a derived cache, rebuilt when any parameter changes
@@ -123,28 +160,30 @@ class Denoiser(nn.Module):
         table = self._weight_table()
         if self.precision not in ("fp32", "bf16x3"):
             raise ValueError("Denoiser.precision must be 'fp32' or 'bf16x3'")
-        prev = self._packed_key[0] if self._packed_key is not None else 0
-        with_backward = (1 if with_backward else 0) | (prev & 1) | (2 if self.precision == "bf16x3" else 0) | (prev & 2)
+        # MG_DEN_* flags of the blob; the backward and split packs, once asked for, stay
+        BWD, SPLIT = _lib.MG_DEN_BACKWARD, _lib.MG_DEN_SPLIT
+        flags = (self._packed_key[0] & (BWD | SPLIT)) if self._packed_key is not None else 0
+        flags |= (BWD if with_backward else 0) | (SPLIT if self.precision == "bf16x3" else 0)
         # the 16x16x4-MFMA packs (16-frame tiles for single utterances / small batches): inference only -- a module
         # that trains repacks every step and never launches that width
-        if not (with_backward & 1) and self._dims.channels == 256 and self._dims.cond_channels == 256:
-            with_backward |= 4
-        key = (with_backward,) + tuple((p.data_ptr(), p._version) for p in table if p is not None)
+        if not (flags & BWD) and self._dims.channels == 256 and self._dims.cond_channels == 256:
+            flags |= _lib.MG_DEN_P16
+        key = (flags,) + tuple((p.data_ptr(), p._version) for p in table if p is not None)
         if self._packed is None or key != self._packed_key:
             L = _lib.lib()
             dev = table[0].device
             if dev.type != "cuda":
                 raise _lib.MixganHipError("Denoiser parameters are on %s: the HIP path needs them on the GPU" % dev)
-            n = L.mg_denoiser_packed_floats(ctypes.byref(self._dims), int(with_backward))
+            n = L.mg_denoiser_packed_floats(ctypes.byref(self._dims), flags)
             if self._packed is None or self._packed.numel() != n or self._packed.device != dev:
                 self._packed = torch.empty(n, device=dev, dtype=torch.float32)
             ptrs = (ctypes.c_void_p * len(table))(*[None if p is None else fptr(p.detach()).value for p in table])
             freq = self._freq_cache(dev)
             # same tensors into the same buffer as last time (only their contents changed): the job table is resident
-            jobs_key = (int(with_backward), self._packed.data_ptr(), freq.data_ptr()) + tuple(k[0] for k in key[1:])
-            resident = 8 if jobs_key == getattr(self, "_jobs_key", None) else 0
-            check(L.mg_denoiser_pack(ctypes.byref(self._dims), ptrs, fptr(freq), fptr(self._packed),
-                                     int(with_backward) | resident, stream_ptr()))
+            jobs_key = (flags, self._packed.data_ptr(), freq.data_ptr()) + tuple(k[0] for k in key[1:])
+            resident = _lib.MG_DEN_JOBS_RESIDENT if jobs_key == getattr(self, "_jobs_key", None) else 0
+            check(L.mg_denoiser_pack(ctypes.byref(self._dims), ptrs, fptr(freq), fptr(self._packed), flags | resident,
+                                     stream_ptr()))
             self._jobs_key = jobs_key
             self._packed_key = key
         return self._packed
@@ -181,16 +220,15 @@ class Denoiser(nn.Module):
         # keyed by stream too: the single-launch kernels keep their tickets and hand-off buffers in the workspace, so two
         # launches in flight on different streams must not share one
         k = (B, L, bool(save), dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-        ws = self._ws.get(k)
-        if ws is not None and not (save and getattr(ws, "_mg_busy", False)):
-            self._ws.move_to_end(k)
-            return ws
-        ws = self.new_workspace(B, L, save, dev)
-        self._ws[k] = ws
-        self._ws.move_to_end(k)
-        while len(self._ws) > 8:
-            self._ws.popitem(last=False)
-        return ws
+        return _cached(self._ws, k, 8, lambda: self.new_workspace(B, L, save, dev),
+                       lambda ws: not (save and getattr(ws, "_mg_busy", False)))
+
+    def _fwd_mode(self, packed, save=False):
+        """mg_denoiser_fwd / _psample's `mode` for a launch on `packed`."""
+        mode = _lib.MG_FWD_SAVE if save else (_lib.MG_FWD_SPLIT if self.precision == "bf16x3" else 0)
+        if self._packed_key is not None and (self._packed_key[0] & _lib.MG_DEN_P16) and packed is self._packed:
+            mode |= _lib.MG_FWD_P16      # the blob carries the 16-row packs
+        return mode
 
     # ------------------------------------------------------------------ forward
     def run(self, x_t, t, cond, spk, out=None, save=False, packed=None, ws=None):
@@ -210,12 +248,9 @@ class Denoiser(nn.Module):
             self.last_ws = ws
         if out is None:
             out = torch.empty_like(x_t)
-        mode = 1 if save else (2 if self.precision == "bf16x3" else 0)
-        if self._packed_key is not None and (self._packed_key[0] & 4) and packed is self._packed:
-            mode |= 4      # MG_FWD_P16: the blob carries the 16-row packs
         check(_lib.lib().mg_denoiser_fwd(ctypes.byref(self._dims), fptr(packed), fptr(x_t), iptr(t, torch.int64),
                                          fptr(cond), fptr(spk, not self.multi_speaker), fptr(out), fptr(ws),
-                                         ws.numel(), B, L, mode, stream_ptr()))
+                                         ws.numel(), B, L, self._fwd_mode(packed, save), stream_ptr()))
         return out
 
     def run_pair(self, x_a, t_a, x_b, t_b, cond, spk, cond_b=None, spk_b=None):
@@ -237,7 +272,7 @@ class Denoiser(nn.Module):
                                              fptr(spk_b if self.multi_speaker else None, True), fptr(out_a),
                                              fptr(out_b), fptr(ws_a),
                                              ws_a.numel(), fptr(ws_b), ws_b.numel(), Bh, L, stream_ptr())
-        if rc == -2:        # MG_ERR_SHAPE: not a shape of the single-launch kernel
+        if rc == _lib.MG_ERR_SHAPE:        # not a shape of the single-launch kernel
             return None
         check(rc)
         self._save_gen += 1
@@ -249,8 +284,7 @@ class Denoiser(nn.Module):
     def has_cond_projection(self, packed=None):
         """True when the packs hold the all-layer conditioner projection (the fp32 inference packs, C = H = 256)."""
         packed = self.packed_weights() if packed is None else packed
-        return (self.precision != "bf16x3" and self._packed_key is not None and bool(self._packed_key[0] & 4)
-                and packed is self._packed)
+        return self.precision != "bf16x3" and bool(self._fwd_mode(packed) & _lib.MG_FWD_P16)
 
     def cond_projection(self, cond, out=None, packed=None):
         """conditioner_projection(cond) of every residual layer (model/blocks.py:1150,1160) as one product:
@@ -302,9 +336,6 @@ class Denoiser(nn.Module):
             out = torch.empty_like(x_t)
         if getattr(self, "_rng_seed", None) is None:
             self._rng_seed = (int(torch.randint(0, 2 ** 62, (1,)).item()) ^ _rank_salt(x_t.device)) & (2 ** 64 - 1)
-        mode = 2 if self.precision == "bf16x3" else 0
-        if self._packed_key is not None and (self._packed_key[0] & 4) and packed is self._packed:
-            mode |= 4
         loop = None
         if cproj is not None or cproj_out is not None or step_vectors is not None:
             sv = step_vectors or (None, 0, 0)
@@ -314,7 +345,7 @@ class Denoiser(nn.Module):
             ctypes.byref(self._dims), fptr(packed), fptr(x_t), iptr(t, torch.int64), fptr(cond),
             fptr(spk, not self.multi_speaker), fptr(coef1), fptr(coef2), fptr(logvar), coef1.numel(), fptr(noise, True),
             self._rng_seed, self._noise_stream_of(ws), int(bool(clip)), fptr(out), fptr(x0_out, True),
-            loop, fptr(ws), ws.numel(), B, L, mode, stream_ptr()))
+            loop, fptr(ws), ws.numel(), B, L, self._fwd_mode(packed), stream_ptr()))
         return out
 
     @staticmethod
@@ -367,34 +398,28 @@ class Denoiser(nn.Module):
         per-layer kind for all layers (mg_denoiser_bwd writes every kind as ONE layer-major array).  A
         distributed.GradBucket laid out in this order lets the backward write straight into the all-reduce
         buffer: no per-parameter gather copy (148 small launches per step otherwise)."""
-        table = self._weight_table()
-        head = [p for p in table[:8] if p is not None]
-        per_layer = [table[8 + 9 * l: 8 + 9 * (l + 1)] for l in range(len(self.residual_layers))]
-        kinds = [[lay[j] for lay in per_layer] for j in range(9)]
+        head, kinds = self._slots()
         return head + [p for kind in kinds for p in kind if p is not None]
 
     def bind_grad_buffer(self, flat, offsets):
         """flat: fp32 buffer; offsets: {id(param): element offset}.  Used only when every kind is layer-contiguous."""
-        table = self._weight_table()
-        NL = len(self.residual_layers)
-        for j in range(9):
-            ps = [table[8 + 9 * l + j] for l in range(NL)]
+        for ps in self._slots()[1]:
             if ps[0] is None:
                 continue
-            for l in range(NL):
-                if id(ps[l]) not in offsets or offsets[id(ps[l])] != offsets[id(ps[0])] + l * ps[0].numel():
+            for l, p in enumerate(ps):
+                if id(p) not in offsets or offsets[id(p)] != offsets[id(ps[0])] + l * ps[0].numel():
                     raise _lib.MixganHipError("bind_grad_buffer: parameters are not laid out in grad_order()")
         self._grad_sink = (flat, dict(offsets))
 
     def _grad_targets(self, dev):
-        """(head grads [8], per-kind layer-major arrays [9]) -- views of the bound bucket when every parameter's
+        """(head grads, per-kind layer-major arrays), laid out as _slots() -- views of the bound bucket when every parameter's
         .grad is unset (autograd then adopts the returned views as .grad without a copy), fresh tensors otherwise
         (a second backward before zero_grad must ADD to .grad, which autograd does from a separate tensor)."""
-        table = self._weight_table()
+        head, kinds = self._slots()
         NL = len(self.residual_layers)
         sink = self._grad_sink
         use_sink = (sink is not None and sink[0].device == dev
-                    and all(p is None or (p.grad is None and id(p) in sink[1]) for p in table))
+                    and all(p is None or (p.grad is None and id(p) in sink[1]) for ps in [head] + kinds for p in ps))
         self._sink_used = use_sink
         def alloc(p, lead=()):
             if p is None:
@@ -404,7 +429,7 @@ class Denoiser(nn.Module):
                 n = p.numel() * (lead[0] if lead else 1)
                 return sink[0][off:off + n].view(*lead, *p.shape)
             return torch.empty(*lead, *p.shape, device=dev, dtype=torch.float32)
-        return [alloc(p) for p in table[:8]], [alloc(table[8 + j], (NL,)) for j in range(9)]
+        return [alloc(p) for p in head], [alloc(ps[0], (NL,)) for ps in kinds]
 
     def run_backward(self, g_out, x_t, t, cond, spk, ws, gen, want_dx, want_dcond, want_dspk):
         """Returns (d_x_t, d_cond, d_spk, [param grads in weight-table order, None entries skipped]).
@@ -420,21 +445,13 @@ class Denoiser(nn.Module):
         raise_if_failed((self,))
         packed = self.packed_weights(with_backward=True)
         k = (B, L, dev, torch.cuda.current_stream(dev).cuda_stream)
-        bws = self._bws.get(k)
-        if bws is None:
-            # transient scratch of this call only (stream-ordered), so eviction is always safe
-            # zero-filled once: the single-launch data-gradient kernel keeps its counters in here
-            bws = torch.zeros(L_.mg_denoiser_bwd_workspace_floats(ctypes.byref(d), B, L), device=dev)
-            self._bws[k] = bws
-            while len(self._bws) > 4:
-                self._bws.popitem(last=False)
-        else:
-            self._bws.move_to_end(k)
+        # transient scratch of this call only (stream-ordered), so eviction is always safe
+        # zero-filled once: the single-launch data-gradient kernel keeps its counters in here
+        bws = _cached(self._bws, k, 4,
+                      lambda: torch.zeros(L_.mg_denoiser_bwd_workspace_floats(ctypes.byref(d), B, L), device=dev))
         head, kinds = self._grad_targets(dev)
         # per-layer gradients are slices of layer-major tensors: mg_denoiser_bwd computes them for all layers at once
-        grads = list(head)
-        for l in range(NL):
-            grads += [None if a is None else a[l] for a in kinds]
+        grads = head + [None if a is None else a[l] for l in range(NL) for a in kinds]
         ptrs = (ctypes.c_void_p * len(grads))(*[None if g is None else g.data_ptr() for g in grads])
         d_x = torch.empty_like(x_t) if want_dx else None
         d_cond = torch.empty_like(cond) if want_dcond else None

@@ -8,8 +8,9 @@ import torch
 from . import _lib
 from ._lib import fptr, iptr, check, stream_ptr
 
-ACT = {None: 0, "none": 0, "relu": 1, "lrelu": 2, "tanh": 3, "lrelu_s": 4}
-PACK_PLAIN, PACK_GATE, PACK_DGRAD = 0, 1, 2
+ACT = {None: _lib.MG_ACT_NONE, "none": _lib.MG_ACT_NONE, "relu": _lib.MG_ACT_RELU, "lrelu": _lib.MG_ACT_LRELU02,
+       "tanh": _lib.MG_ACT_TANH, "lrelu_s": _lib.MG_ACT_LRELU}
+PACK_PLAIN, PACK_GATE, PACK_DGRAD = _lib.MG_PACK_PLAIN, _lib.MG_PACK_GATE, _lib.MG_PACK_DGRAD
 
 
 def pack_conv_weight(w, mode=PACK_PLAIN, out=None):

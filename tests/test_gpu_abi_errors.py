@@ -34,12 +34,12 @@ def test_workspace_and_shape_errors(mg, manifest, tmp_path):
     ws = torch.empty(need - 1, device="cuda")
     args = (ctypes.byref(den._dims), _lib.fptr(packed), _lib.fptr(x), _lib.iptr(t, torch.int64), _lib.fptr(cond), None,
             _lib.fptr(out), _lib.fptr(ws))
-    assert L.mg_denoiser_fwd(*args, ws.numel(), B, Lf, 0, None) == -3          # MG_ERR_WORKSPACE
-    assert L.mg_denoiser_fwd(*args, need, 0, Lf, 0, None) == -2                 # MG_ERR_SHAPE (B = 0)
-    assert L.mg_denoiser_fwd(*args, need, B, Lf, 3, None) == -1                 # save + split is not a valid mode
-    assert L.mg_attention_fwd(_lib.fptr(x), None, _lib.fptr(out), 1, 8, 2, 64, 0.1, None) == -2   # d_head != 128
+    assert L.mg_denoiser_fwd(*args, ws.numel(), B, Lf, 0, None) == _lib.MG_ERR_WORKSPACE
+    assert L.mg_denoiser_fwd(*args, need, 0, Lf, 0, None) == _lib.MG_ERR_SHAPE                 # B = 0
+    assert L.mg_denoiser_fwd(*args, need, B, Lf, _lib.MG_FWD_SAVE | _lib.MG_FWD_SPLIT, None) == _lib.MG_ERR_ARG   # not a valid mode
+    assert L.mg_attention_fwd(_lib.fptr(x), None, _lib.fptr(out), 1, 8, 2, 64, 0.1, None) == _lib.MG_ERR_SHAPE   # d_head != 128
     with pytest.raises(mg.MixganHipError):
-        _lib.check(-3)
+        _lib.check(_lib.MG_ERR_WORKSPACE)
     # multi-speaker denoiser without a speaker embedding is an argument error, not a crash
     _, pre2, mc2, _ = hot_path_configs(multi_speaker=True, stats_dir=str(tmp_path))
     den2 = mg.Denoiser(pre2, mc2).cuda()

@@ -27,6 +27,7 @@ import torch
 
 from helpers import GOLDEN, hot_path_configs, seeded, oracle_grads, condition_relu_kinks
 from oracle import weights as WR
+from mixgan_tts_amd import _lib
 
 pytestmark = pytest.mark.gpu
 FT, GT, PT = 2e-5, 5e-5, 1e-4
@@ -306,33 +307,34 @@ SENTINEL = 12345.0
 def _abi_backward(mg, case, ws, want_head, want_kind, want_dx, want_dcond, want_dspk, break_layer_major=False):
     """mg_denoiser_bwd through ctypes.  Every buffer exists and is pre-filled with SENTINEL; the ones not wanted are
     passed as NULL.  Returns ({name: tensor} of all buffers, set of the requested names, return code)."""
-    from mixgan_tts_amd import _lib
     den = case.den
     lib = _lib.lib()
     d = den._dims
     B, L, NL = case.B, case.L, d.n_layers
     table = den._weight_table()
+    HEAD, PER_LAYER = _lib.MG_DEN_HEAD_PTRS, _lib.MG_DEN_LAYER_PTRS
+    slot = lambda l, j: HEAD + PER_LAYER * l + j  # noqa: E731
     names = {id(p): "param/" + k for k, p in den.named_parameters()}
     full = lambda *shape: torch.full(shape, SENTINEL, device="cuda")  # noqa: E731
-    head = [full(*p.shape) for p in table[:8]]
-    kinds = [None if table[8 + j] is None else full(NL, *table[8 + j].shape) for j in range(9)]
+    head = [full(*p.shape) for p in table[:HEAD]]
+    kinds = [None if table[slot(0, j)] is None else full(NL, *table[slot(0, j)].shape) for j in range(PER_LAYER)]
     bufs, asked, ptrs = {}, set(), []
-    for i in range(8):
+    for i in range(HEAD):
         bufs[names[id(table[i])]] = head[i]
         if want_head(i):
             asked.add(names[id(table[i])])
         ptrs.append(head[i].data_ptr() if want_head(i) else None)
     for l in range(NL):
-        for j in range(9):
+        for j in range(PER_LAYER):
             if kinds[j] is None:
                 ptrs.append(None)
                 continue
-            bufs[names[id(table[8 + 9 * l + j])]] = kinds[j][l]
+            bufs[names[id(table[slot(l, j)])]] = kinds[j][l]
             if want_kind(j):
-                asked.add(names[id(table[8 + 9 * l + j])])
+                asked.add(names[id(table[slot(l, j)])])
             ptrs.append(kinds[j][l].data_ptr() if want_kind(j) else None)
     if break_layer_major:      # layer 1's conv_layer weight is not layer 0's plus one layer
-        ptrs[8 + 9 * 1 + 0] = kinds[0][2].data_ptr()
+        ptrs[slot(1, _lib.MG_DEN_L_CONV_W)] = kinds[_lib.MG_DEN_L_CONV_W][2].data_ptr()
     x, cond, go = case.x[:, 0].contiguous().cuda(), case.cond.cuda(), case.go[:, 0].contiguous().cuda()
     spk = case.spk.cuda() if case.ms else None
     bufs["d_x"], bufs["d_cond"] = full(*x.shape), full(*cond.shape)
@@ -352,16 +354,17 @@ def _abi_backward(mg, case, ws, want_head, want_kind, want_dx, want_dcond, want_
     return bufs, asked, rc
 
 
-# per-layer kinds of the pointer table: 0/1 conv_layer weight/bias, 3/4 conditioner weight/bias, 5/6 output weight/bias
+# every head slot / every per-layer kind (the header's MG_DEN_L_* names) but one
+_all, _but = (lambda i: True), (lambda kind: lambda j: j != kind)
 POINTER_SETS = [
-    ("conv3 weights, no conv3 biases (fold3 false)", lambda i: True, lambda j: j != 1, True, True, True),
-    ("conv3 biases, no conv3 weights (mg_rowsum over dz)", lambda i: True, lambda j: j != 0, True, True, True),
-    ("output-conv weights, no biases (foldo false)", lambda i: True, lambda j: j != 6, True, True, True),
-    ("output-conv biases, no weights (mg_rowsum + bias_scatter_kernel)", lambda i: True, lambda j: j != 5, True, True, True),
-    ("conditioner weights, no biases (foldc false)", lambda i: True, lambda j: j != 4, True, True, True),
-    ("conditioner biases, no weights", lambda i: True, lambda j: j != 3, True, True, True),
+    ("conv3 weights, no conv3 biases (fold3 false)", _all, _but(_lib.MG_DEN_L_CONV_B), True, True, True),
+    ("conv3 biases, no conv3 weights (mg_rowsum over dz)", _all, _but(_lib.MG_DEN_L_CONV_W), True, True, True),
+    ("output-conv weights, no biases (foldo false)", _all, _but(_lib.MG_DEN_L_OUT_B), True, True, True),
+    ("output-conv biases, no weights (mg_rowsum + bias_scatter_kernel)", _all, _but(_lib.MG_DEN_L_OUT_W), True, True, True),
+    ("conditioner weights, no biases (foldc false)", _all, _but(_lib.MG_DEN_L_COND_B), True, True, True),
+    ("conditioner biases, no weights", _all, _but(_lib.MG_DEN_L_COND_W), True, True, True),
     ("no parameter gradients, only d_x_t", lambda i: False, lambda j: False, True, False, False),
-    ("no d_x_t, no d_cond", lambda i: True, lambda j: True, False, False, True),
+    ("no d_x_t, no d_cond", _all, _all, False, False, True),
 ]
 
 
@@ -414,7 +417,7 @@ def test_layer_major_pointer_check(mg):
         got, _, rc = _abi_backward(mg, case, ws, lambda i: True, lambda j: True, True, True, True, break_layer_major=True)
     finally:
         ws._mg_busy = False
-    assert rc == -1      # MG_ERR_ARG
+    assert rc == _lib.MG_ERR_ARG
     for k, v in got.items():
         assert bool((v == SENTINEL).all()), k + " was written by a call that returned an error"
     with pytest.raises(mg.MixganHipError):

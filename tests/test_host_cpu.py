@@ -12,38 +12,105 @@ import torch
 from helpers import golden, hot_path_configs, write_stats, ROOT
 
 import mixgan_tts_amd as mg
+from mixgan_tts_amd import _lib
+
+
+def _header_code():
+    """include/mixgan_hip.h without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mixgan_hip.h")).read(), flags=re.S)
 
 
 def test_header_symbols_exported():
-    hdr = open(os.path.join(ROOT, "include", "mixgan_hip.h")).read()
-    declared = set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", hdr))
+    declared = set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", _header_code()))
     assert declared, "no declarations parsed"
     L = ctypes.CDLL(mg.library_path())
     for name in sorted(declared):
         assert hasattr(L, name), "libmixgan_hip.so does not export " + name
-    from mixgan_tts_amd import _lib
-    assert set(_lib.EXPORTS) <= declared
+    assert set(_lib.EXPORTS) == declared
     assert mg.lib().mg_version() >= 100
+
+
+def test_mirrored_constants_equal_the_header():
+    """Every MG_* integer of _lib has the header's value: `#define NAME value` or an enumerator `NAME = value`."""
+    code = _header_code()
+    header = {n: int(v) for n, v in re.findall(r"^#define[ \t]+(MG_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", code, re.M)}
+    for body in re.findall(r"\benum\s+\w+\s*\{(.*?)\}", code, re.S):
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            m = re.fullmatch(r"(MG_\w+)\s*=\s*(-?\d+)", item)
+            assert m, "enumerator without an explicit value: " + item
+            header[m[1]] = int(m[2])
+    mirrored = {k: v for k, v in vars(_lib).items() if k.startswith("MG_") and isinstance(v, int)}
+    for family, n in (("MG_ERR_", 3), ("MG_ACT_", 5), ("MG_PACK_", 6), ("MG_DEN_L_", 9), ("MG_DEN_", 23), ("MG_FWD_", 3),
+                      ("MG_PLAN_", 5), ("MG_LOSS_", 2)):
+        assert len([k for k in mirrored if k.startswith(family)]) == n, family
+    for k, v in sorted(mirrored.items()):
+        assert k in header, k + " is not a constant of the header"
+        assert v == header[k], "%s: _lib %d, header %d" % (k, v, header[k])
+
+
+def _c_class(text, is_return=False):
+    """Class of a C parameter declaration (`const float *w`, `long dy_bs`) or return type, as ctypes can tell them apart."""
+    toks = [t for t in text.replace("*", " * ").split() if t != "const"]
+    if "*" in toks:
+        return "char *" if toks[:2] == ["char", "*"] else "pointer"
+    kind = " ".join(toks if is_return else toks[:-1])      # a parameter's last token is its name
+    return {"int": "int", "int32_t": "int", "float": "float", "long": "long", "size_t": "size_t",
+            "unsigned long long": "size_t", "unsigned": "unsigned"}[kind]      # KeyError: a type this test cannot read
+
+
+def _ctypes_class(ct):
+    if ct is ctypes.c_char_p:
+        return "char *"
+    if ct is ctypes.c_void_p or issubclass(ct, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_long: "long", ctypes.c_size_t: "size_t",
+            ctypes.c_ulonglong: "size_t", ctypes.c_uint: "unsigned"}[ct]
+
+
+def test_ctypes_signatures_match_the_header_prototypes():
+    """Every prototype of the header has an entry in _lib's signature table with the same number of arguments, each of
+    the same class (pointer, int, float, long, size_t / unsigned long long, unsigned), and the same return class."""
+    code = re.sub(r"^[ \t]*#.*$", "", _header_code(), flags=re.M)                         # preprocessor lines
+    code = re.sub(r"\b(typedef\s+struct|enum)\b[^{;]*\{.*?\}[^;]*;", "", code, flags=re.S)  # struct and enum bodies
+    code = code.replace('extern "C" {', "")
+    protos = {}
+    for stmt in filter(None, (x.strip() for x in code.split(";"))):
+        if stmt == "}":      # closes extern "C"
+            continue
+        m = re.fullmatch(r"(.*?)\b(mg_\w+)\s*\((.*)\)", stmt, re.S)
+        assert m, "cannot read this declaration: " + stmt
+        args = [] if m[3].strip() == "void" else m[3].split(",")
+        protos[m[2]] = (_c_class(m[1], True), [_c_class(a) for a in args])
+    sig = _lib._signatures()
+    assert len(protos) >= 112 and set(protos) == set(sig)
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = sig[name]
+        assert _ctypes_class(res) == ret, "%s returns %s in the header" % (name, ret)
+        assert [_ctypes_class(a) for a in argtypes] == args, "%s: header %s" % (name, args)
+    # and the loaded library carries exactly these
+    L = mg.lib()
+    for name, (res, argtypes) in sig.items():
+        assert getattr(L, name).restype is res and list(getattr(L, name).argtypes) == list(argtypes), name
 
 
 def test_error_strings_and_arg_checks():
     L = mg.lib()
-    assert b"shape" in L.mg_error_string(-2)
+    assert b"shape" in L.mg_error_string(_lib.MG_ERR_SHAPE)
     assert L.mg_conv_packed_floats(512, 256, 3, 1) == 16 * (256 * 3 // 8) * 256
     assert L.mg_conv_packed_floats(512, 256, 6, 0) == 0          # unsupported kernel size
     # null pointers are rejected before any launch (no GPU needed)
-    assert L.mg_conv1d_fwd(None, None, None, None, None, None, 1, 8, 8, 8, 8, 1, 1, 0, 0, 1.0, 0, None) == -1
+    assert L.mg_conv1d_fwd(None, None, None, None, None, None, 1, 8, 8, 8, 8, 1, 1, 0, 0, 1.0, 0, None) == _lib.MG_ERR_ARG
     # the entry points added for the vocoder / aux-training / grouped-gradient rows: sizes and argument checks
     assert L.mg_conv_transpose_packed_floats(512, 256, 8) == (256 * 8 // 32) * (512 * 3 // 8) * 256
     assert L.mg_conv_transpose_packed_floats(512, 256, 3) == 0                       # stride must be 2, 4 or 8
-    assert L.mg_conv_transpose_pack(None, None, 512, 256, 8, None) == -1
-    assert L.mg_conv_transpose1d_fwd(None, None, None, None, 1, 8, 8, 8, 2, 1.0, 1.0, None) == -1
-    assert L.mg_bgemm(None, None, None, 4, 4, 4, 1, 1, 1, 4, 0, 0, 4, 1, 0, 0, 4, 0, 0, 1.0, 0, None) == -1
-    assert L.mg_softmax_rows_fwd(None, None, 1, 1, 4, 1.0, None) == -1
-    assert L.mg_layernorm_cm_bwd(None, None, None, None, None, 1.0, None, None, None, None, 1, 256, 4, 1e-5, None) == -1
-    assert L.mg_bn_stats(None, None, None, 1, 4, 4, None) == -1
-    assert L.mg_attention_fwd_f16(None, None, None, 1, 4, 2, 128, 1.0, None) == -1
-    assert L.mg_diffuse_trace_bwd(None, None, None, None, None, None, None, 4, 1, 4, 80, None) == -1
+    assert L.mg_conv_transpose_pack(None, None, 512, 256, 8, None) == _lib.MG_ERR_ARG
+    assert L.mg_conv_transpose1d_fwd(None, None, None, None, 1, 8, 8, 8, 2, 1.0, 1.0, None) == _lib.MG_ERR_ARG
+    assert L.mg_bgemm(None, None, None, 4, 4, 4, 1, 1, 1, 4, 0, 0, 4, 1, 0, 0, 4, 0, 0, 1.0, 0, None) == _lib.MG_ERR_ARG
+    assert L.mg_softmax_rows_fwd(None, None, 1, 1, 4, 1.0, None) == _lib.MG_ERR_ARG
+    assert L.mg_layernorm_cm_bwd(None, None, None, None, None, 1.0, None, None, None, None, 1, 256, 4, 1e-5, None) == _lib.MG_ERR_ARG
+    assert L.mg_bn_stats(None, None, None, 1, 4, 4, None) == _lib.MG_ERR_ARG
+    assert L.mg_attention_fwd_f16(None, None, None, 1, 4, 2, 128, 1.0, None) == _lib.MG_ERR_ARG
+    assert L.mg_diffuse_trace_bwd(None, None, None, None, None, None, None, 4, 1, 4, 80, None) == _lib.MG_ERR_ARG
     # streaming kernel (wgrad_stream.h): 256 workgroups x (tiles / 256 + 2) partial tiles of K x 128 x 128 (k=3) or
     # 128 x 256 (k=1); shapes it does not take keep the split kernel's [nsplit][G][K][Co][Ci]
     assert L.mg_conv1d_wgrad_grouped_scratch_floats(512, 256, 3, 20) == 256 * 2 * (3 * 128 * 128 + 128)   # + partial row sums
@@ -52,7 +119,7 @@ def test_error_strings_and_arg_checks():
     assert L.mg_conv1d_wgrad_grouped_scratch_floats(512, 256, 3, 400) == 256 * (3200 // 256 + 2) * (3 * 128 * 128 + 128)
     assert L.mg_conv1d_wgrad_scratch_floats(256, 80, 1) == 128 * 256 * 80                     # 2 tiles, 256-workgroup target
     assert L.mg_conv1d_wgrad_scratch_floats(512, 128, 5) == 25 * 512 * 128 * 5                # k=5: split kernel, 20 tiles
-    assert L.mg_conv1d_wgrad_grouped(None, 0, 0, None, 0, 0, None, 0, None, 2, 1, 8, 8, 8, 8, 1, 1, 0, 1.0, 0, None) == -1
+    assert L.mg_conv1d_wgrad_grouped(None, 0, 0, None, 0, 0, None, 0, None, 2, 1, 8, 8, 8, 8, 1, 1, 0, 1.0, 0, None) == _lib.MG_ERR_ARG
 
 
 def test_schedule_matches_reference_bits():

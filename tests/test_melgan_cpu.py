@@ -8,7 +8,7 @@ import torch
 
 import melgan_torch as MT
 
-MG_ERR_ARG, MG_ERR_SHAPE = -1, -2
+from mixgan_tts_amd._lib import MG_ERR_ARG, MG_ERR_SHAPE
 
 
 def test_state_dict_keys_shapes_order_match_restatement():
