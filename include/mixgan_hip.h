@@ -702,6 +702,26 @@ int mg_ds_conv2d(const float *x, const float *w, const float *bias, const float 
 int mg_ds_head(const float *x, const float *w, const float *bias, float *out, int B, int rows, int D, int O,
                void *stream);
 
+/* ------------------------------------------------------------------ corpus builder (preprocessor/preprocessor.py;
+ * csrc/corpus.hip).
+ * Beta-binomial alignment prior (:384-393 as called at :344-348), batched and padded: out [B, T, L], float32 or
+ * (out_f64) float64.  src_lens, mel_lens: device int32 [B].  For phoneme row i < src_lens[b] and frame
+ * k < mel_lens[b]: out[b, i, k] = betabinom(n = mel_len, a = s (i + 1), b = s (src_len - i)).pmf(k), evaluated in
+ * float64; every other element is 0.  The caller passes T >= max(src_lens) and L >= max(mel_lens): a length beyond
+ * them is not an error here (checking would need a host read) but is clamped, src_len to T and mel_len to L, and
+ * the row is then the distribution of the clamped lengths, not a cut of the true one.  scaling points to the HOST
+ * value s > 0, read before the launch. */
+int mg_betabinom_prior(const int *src_lens, const int *mel_lens, const double *scaling, void *out, int B, int T, int L,
+                       int out_f64, void *stream);
+/* Frame level -> phoneme level (:311-341).  values [B, L], durations int32 [B, T], n_frames / n_phon int32 [B],
+ * out [B, T]: out[b, i] = mean(values[b, pos_i : pos_i + d_i]) cut at n_frames[b], 0 where d_i == 0 or
+ * i >= n_phon[b].  pitch == 0: float32 in and out (energy).  pitch == 1: float64 in and out, and zero frames are first
+ * replaced by linear interpolation between their non-zero neighbours, the first / last non-zero value outside them; an
+ * utterance needs at least one non-zero frame.  The reference averages in place, so segments with pos_i < i read
+ * earlier results: reproduced.  T <= 2048, L <= 4096. */
+int mg_phoneme_average(const void *values, const int *durations, const int *n_frames, const int *n_phon, void *out,
+                       int B, int T, int L, int pitch, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

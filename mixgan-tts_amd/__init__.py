@@ -29,4 +29,8 @@ from . import speaker_embedder  # noqa: F401
 from .speaker_embedder import (DeepSpeakerModel, PreDefinedEmbedder, DeepSpeakerCheckpointRequired,  # noqa: F401
                                save_speaker_embeddings)
 
+from . import corpusops, preprocessor  # noqa: F401
+from .corpusops import attn_prior, phoneme_average  # noqa: F401
+from .preprocessor import Preprocessor, PitchExtractorRequired, read_textgrid  # noqa: F401
+
 __version__ = "0.1.0"

@@ -198,6 +198,8 @@ def _signatures():
         "mg_ds_fbank": (i, [vp, lg, vp, vp, vp, i, i, i, i, vp, vp, vp, i, vp, vp]),
         "mg_ds_conv2d": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]),
         "mg_ds_head": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
+        "mg_betabinom_prior": (i, [vp, vp, ctypes.POINTER(ctypes.c_double), vp, i, i, i, i, vp]),
+        "mg_phoneme_average": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp]),
     }
 
 

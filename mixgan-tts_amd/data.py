@@ -11,6 +11,11 @@ the GPU, designed for one process per GPU:
   (`train.py:34-39`, `shuffle=True`, no workers); here every rank derives the same seeded permutation per
   epoch and takes every `world`-th *group* (group = `group_size * batch_size` items, the unit
   `collate_fn` sorts inside), so all ranks see the same number of equally sized groups per epoch.
+* `Dataset(..., attn_prior="device")` -- the alignment prior is a function of (text length, mel length, scaling
+  factor) alone, and its float64 files are about 2.5 times the mel bytes.  In this mode `__getitem__` opens no
+  `attn_prior` file (the folder need not exist), collation leaves slot 10 as None, and `to_device` /
+  `PrefetchLoader` fill it on the device from the two length vectors (corpusops.attn_prior, csrc/corpus.hip) on the
+  stream they copy on.  Same slot dtype and shape: float32 [B, T, L].
 * `PrefetchLoader` -- a background thread does the `np.load`s + collation of the next groups while the
   GPU works on the current one, stages every array of a batch in pinned host memory and issues the
   host->device copies on its own HIP stream; the consumer only waits on an event.  It yields what
@@ -79,12 +84,20 @@ def _read_meta(path):
 
 
 class Dataset(torch.utils.data.Dataset):
-    """dataset.py:13-190.  Extra keyword: `text_to_sequence` (callable(text, cleaners) -> ids)."""
+    """dataset.py:13-190.  Extra keywords: `text_to_sequence` (callable(text, cleaners) -> ids); `attn_prior`,
+    "disk" (read the files, the reference's way) or "device" (computed on the GPU by to_device / PrefetchLoader)."""
 
     KINDS = ("mel", "pitch", "energy", "duration", "phones_per_word", "attn_prior")
 
     def __init__(self, filename, args, preprocess_config, model_config, train_config, sort=False, drop_last=False,
-                 text_to_sequence=None, mmap=True):
+                 text_to_sequence=None, mmap=True, attn_prior="disk"):
+        if attn_prior not in ("disk", "device"):
+            raise ValueError("attn_prior must be 'disk' or 'device', got %r" % (attn_prior,))
+        self.attn_prior = attn_prior
+        # read only where it is needed, so that "disk" takes every config it took before
+        self.prior_scaling = None if attn_prior == "disk" else float(
+            preprocess_config["preprocessing"]["aligner"]["beta_binomial_scaling_factor"])
+        self.kinds = self.KINDS if attn_prior == "disk" else tuple(k for k in self.KINDS if k != "attn_prior")
         self.model = args.model
         self.preprocess_config = preprocess_config
         self.dataset_name = preprocess_config["dataset"]
@@ -112,7 +125,7 @@ class Dataset(torch.utils.data.Dataset):
         if self._t2s is None:
             self._t2s = _default_text_to_sequence()
         basename, speaker = self.basename[idx], self.speaker[idx]
-        arrs = {k: self._load(k, speaker, basename) for k in self.KINDS}
+        arrs = {k: self._load(k, speaker, basename) for k in self.kinds}
         spker_embed = np.load(os.path.join(self.preprocessed_path, "spker_embed",
                                            "{}-spker_embed.npy".format(speaker)),
                               allow_pickle=False) if self.load_spker_embed else None
@@ -127,7 +140,7 @@ class Dataset(torch.utils.data.Dataset):
             "duration": arrs["duration"],
             "word_boundary": arrs["phones_per_word"],
             "spker_embed": spker_embed,
-            "attn_prior": arrs["attn_prior"],
+            "attn_prior": arrs.get("attn_prior"),
         }
 
     def process_meta(self, filename):
@@ -152,7 +165,7 @@ class Dataset(torch.utils.data.Dataset):
             text_w_lens,
             max(text_w_lens),
             spker_embeds,
-            pad_3D(pick("attn_prior"), len(idxs), max(text_lens), max(mel_lens)),
+            pad_3D(pick("attn_prior"), len(idxs), max(text_lens), max(mel_lens)) if self.attn_prior == "disk" else None,
             pad_2D(mels),
             mel_lens,
             max(mel_lens),
@@ -237,10 +250,28 @@ def _slot_to_device(x, kind, device, pin, non_blocking):
     return t.to(device, non_blocking=non_blocking)
 
 
-def to_device(data, device, pin=False, non_blocking=False):
-    """utils/tools.py:33-110: numpy batch tuple (17 or 10 slots) -> list / tuple with device tensors."""
+PRIOR_SLOT, TEXT_LENS_SLOT, MAX_TEXT_SLOT, MEL_LENS_SLOT, MAX_MEL_SLOT = 10, 4, 5, 12, 13
+
+
+def fill_device_prior(slots, prior_scaling):
+    """Slot 10 of a 17-slot batch whose other slots are on the GPU: the padded alignment priors, float32
+    [B, max(text_lens), max(mel_lens)], computed on the current stream."""
+    from . import corpusops
+    if prior_scaling is None:
+        raise ValueError("this batch carries no alignment prior (Dataset(attn_prior='device')): pass "
+                         "prior_scaling=dataset.prior_scaling")
+    slots[PRIOR_SLOT] = corpusops.attn_prior(slots[TEXT_LENS_SLOT], slots[MEL_LENS_SLOT], int(slots[MAX_TEXT_SLOT]),
+                                             int(slots[MAX_MEL_SLOT]), prior_scaling, torch.float32)
+
+
+def to_device(data, device, pin=False, non_blocking=False, prior_scaling=None):
+    """utils/tools.py:33-110: numpy batch tuple (17 or 10 slots) -> list / tuple with device tensors.  A 17-slot batch
+    of Dataset(attn_prior="device") has slot 10 empty: it is computed on `device` (a GPU) with `prior_scaling`."""
     if len(data) == 17:
-        return [_slot_to_device(x, k, device, pin, non_blocking) for x, k in zip(data, _SLOTS17)]
+        out = [_slot_to_device(x, k, device, pin, non_blocking) for x, k in zip(data, _SLOTS17)]
+        if data[PRIOR_SLOT] is None:
+            fill_device_prior(out, prior_scaling)
+        return out
     if len(data) == 10:
         return tuple(_slot_to_device(x, k, device, pin, non_blocking) for x, k in zip(data, _SLOTS10))
     raise ValueError("expected a 17- or 10-slot batch, got %d slots" % len(data))
@@ -322,7 +353,8 @@ class PrefetchLoader:
     def _stage(self, idxs, stream, arena):
         batchs = self.ds.collate_fn([self.ds[i] for i in idxs])
         if not self.cuda:
-            return [to_device(b, self.device) for b in batchs], None
+            return [to_device(b, self.device, prior_scaling=getattr(self.ds, "prior_scaling", None))
+                    for b in batchs], None
         # One pinned staging buffer and ONE host->device copy per group: every array of every sub-batch is
         # converted to its final dtype while it is packed (256-byte aligned) into the arena; the device
         # tensors are views into a single device buffer.  (A pin_memory() per tensor costs a hipHostMalloc
@@ -365,6 +397,14 @@ class PrefetchLoader:
                     t = dev[off:off + a.size * dt.itemsize].view(_TORCH_OF[dt.str]).view(a.shape)
                     slots.append(t)
             out.append(slots if len(b) == 17 else tuple(slots))
+        if any(len(b) == 17 and b[PRIOR_SLOT] is None for b in batchs):
+            # Dataset(attn_prior="device"): the priors follow the copy on its stream; the consumer waits for them
+            with torch.cuda.stream(stream):
+                for b, slots in zip(batchs, out):
+                    if len(b) == 17 and b[PRIOR_SLOT] is None:
+                        fill_device_prior(slots, getattr(self.ds, "prior_scaling", None))
+                ev = torch.cuda.Event()
+                ev.record(stream)
         return out, ev
 
     def __iter__(self):
