@@ -722,6 +722,35 @@ int mg_betabinom_prior(const int *src_lens, const int *mel_lens, const double *s
 int mg_phoneme_average(const void *values, const int *durations, const int *n_frames, const int *n_phon, void *out,
                        int B, int T, int L, int pitch, void *stream);
 
+/* ------------------------------------------------------------------ prepare_align (prepare_align.py,
+ * preprocessor/ljspeech.py, preprocessor/aishell3.py; csrc/resample.hip).
+ * Rational-ratio polyphase resampler over a ragged batch: what librosa.load(path, sr) does to a wav of another rate.
+ * x [B, N] with batch stride x_bs, lengths [B] device int32 (null: all N; clamped to [0, N]); y [B, M] with batch
+ * stride y_bs.  up / down is the reduced ratio target rate / source rate.  With h the centred low-pass of odd length
+ * 2 half + 1 and out_len[b] = ceil(lengths[b] up / down):
+ *   y[b, n] = up sum_k h[n down - k up + half] x[b, k]   over 0 <= k < lengths[b] with the h index in [0, 2 half],
+ * for n < min(out_len[b], M), and y[b, n] = 0 for out_len[b] <= n < M: zero extension at both ends, zero delay,
+ * scipy.signal.resample_poly(x, up, down, window=h).  Nothing at or beyond lengths[b] is read.  n down is formed in
+ * 64 bits.  up == down == 1 copies (h is not used; taps may be null).
+ * taps: the phase-major table [up, Kp] with the factor up folded in, rows ascending in the input index.  With
+ * Mh = half / up + 1 and n down = q up + r (0 <= r < up):
+ *   taps[r, j] = up h[(Mh - 1 - j) up + r + half]  (0 where that index is outside [0, 2 half]; 0 for j >= 2 Mh),
+ *   y[b, n]    = sum_{j < Kp} taps[r, j] x[b, q - Mh + 1 + j].
+ * Kp >= 2 Mh, Kp % 4 == 0, taps 16-byte aligned.  MG_ERR_SHAPE beyond the limits below; the staged input span of one
+ * tile, (MG_RESAMPLE_TILE - 1) down / up + Kp + 2 samples, must not exceed MG_RESAMPLE_MAX_SPAN. */
+#define MG_RESAMPLE_MAX_UP 1024
+#define MG_RESAMPLE_MAX_TAPS 1024 /* Kp, taps per output */
+#define MG_RESAMPLE_TILE 1024     /* consecutive outputs of one workgroup */
+#define MG_RESAMPLE_MAX_SPAN 16384
+int mg_resample_poly(const float *x, long x_bs, const int *lengths, int B, int N, const float *taps, int up, int down,
+                     int Kp, int half, float *y, long y_bs, int M, void *stream);
+/* Peak normalisation to int16 (ljspeech.py:29-34, aishell3.py:32-37): x [B, N] ragged as above, out int16 [B, N] with
+ * batch stride out_bs.  q = trunc((x / max_k |x[b, k]|) max_wav_value) in float32, in that order, saturated to
+ * [-32768, 32767] (the reference's cast wraps +32768 to -32768); an all-zero row gives zeros (the reference divides
+ * by zero); out[b, k] = 0 for k >= lengths[b]. */
+int mg_peak_normalize_i16(const float *x, long x_bs, const int *lengths, int B, int N, float max_wav_value,
+                          int16_t *out, long out_bs, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

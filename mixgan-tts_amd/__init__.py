@@ -32,5 +32,7 @@ from .speaker_embedder import (DeepSpeakerModel, PreDefinedEmbedder, DeepSpeaker
 from . import corpusops, preprocessor  # noqa: F401
 from .corpusops import attn_prior, phoneme_average  # noqa: F401
 from .preprocessor import Preprocessor, PitchExtractorRequired, read_textgrid  # noqa: F401
+from . import prepare_align  # noqa: F401
+from .audio import resample, resample_filter, peak_normalize_int16  # noqa: F401
 
 __version__ = "0.1.0"

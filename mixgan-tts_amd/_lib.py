@@ -28,6 +28,7 @@ MG_DEN_HEAD_PTRS, MG_DEN_LAYER_PTRS = 8, 9
 (MG_DEN_L_CONV_W, MG_DEN_L_CONV_B, MG_DEN_L_DIFF_W, MG_DEN_L_COND_W, MG_DEN_L_COND_B, MG_DEN_L_OUT_W, MG_DEN_L_OUT_B,
  MG_DEN_L_SPK_W, MG_DEN_L_RESERVED) = range(MG_DEN_LAYER_PTRS)
 MG_LOSS_MAX_TERMS, MG_LOSS_GROUPS = 16, 4
+MG_RESAMPLE_MAX_UP, MG_RESAMPLE_MAX_TAPS, MG_RESAMPLE_TILE, MG_RESAMPLE_MAX_SPAN = 1024, 1024, 1024, 16384
 
 
 class LossTerm(ctypes.Structure):
@@ -200,6 +201,8 @@ def _signatures():
         "mg_ds_head": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_betabinom_prior": (i, [vp, vp, ctypes.POINTER(ctypes.c_double), vp, i, i, i, i, vp]),
         "mg_phoneme_average": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp]),
+        "mg_resample_poly": (i, [vp, lg, vp, i, i, vp, i, i, i, i, vp, lg, i, vp]),
+        "mg_peak_normalize_i16": (i, [vp, lg, vp, i, i, f, vp, lg, vp]),
     }
 
 

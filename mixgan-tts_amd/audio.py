@@ -17,6 +17,15 @@ the periodic Hann window as scipy.signal.get_window computes it, centre-padded a
 the filterbank as librosa 0.8's filters.mel (Slaney scale, Slaney area normalisation).  librosa is not available to
 this project's tests, so parity with librosa itself is unverified; the restatement is checked against the
 reference's outputs through the fixtures of tests/golden/make_golden_audio.py.
+
+`resample` and `peak_normalize_int16` (csrc/resample.hip) are the arithmetic of the reference's prepare_align stage:
+what `librosa.load(path, sr)` does to a wav of another rate, and `wav / max(abs(wav)) * max_wav_value` as int16.  The
+resampler is a zero-delay polyphase FIR over a ragged batch, equal to scipy.signal.resample_poly with the window of
+`resample_filter`, the Kaiser-windowed sinc that librosa's historical `kaiser_best` describes.  Bit parity with
+librosa's own resampler (resampy, later soxr) is not claimed and cannot be checked here: its filter is a stored,
+interpolated table.  Deviation: the int16 conversion saturates, so the positive peak is 32767; the reference's
+32768.0 wraps to -32768 in numpy's cast, a full-scale click at the loudest sample of every file.  An all-zero wav is
+written as zeros (the reference divides by zero).
 """
 import ctypes
 import math
@@ -396,3 +405,119 @@ def inv_mel_spec(mel, out_filename, _stft, griffin_iters=60):
     audio = mel_to_audio(mel.unsqueeze(0), _stft, griffin_iters)
     audio = audio.squeeze().cpu().numpy()
     write(out_filename, _stft.sampling_rate, audio)
+
+
+# ---------------------------------------------------------------------------------------------
+# Resampling and peak normalisation (the arithmetic of prepare_align)
+# ---------------------------------------------------------------------------------------------
+RESAMPLE_TILE = _lib.MG_RESAMPLE_TILE      # consecutive outputs of one workgroup
+
+
+def resample_ratio(orig_sr, target_sr):
+    """(up, down): target_sr / orig_sr in lowest terms."""
+    orig_sr, target_sr = int(orig_sr), int(target_sr)
+    if orig_sr <= 0 or target_sr <= 0:
+        raise ValueError("resample: sampling rates must be positive, got %r -> %r" % (orig_sr, target_sr))
+    g = math.gcd(orig_sr, target_sr)
+    return target_sr // g, orig_sr // g
+
+
+def resample_filter(up, down, num_zeros=64, beta=14.769656459379492, rolloff=0.9475937167399596):
+    """Low-pass of the up/down resampler, float64 [2 half + 1]: with m = max(up, down), fc = rolloff / m,
+    half = num_zeros m and n = -half .. half, h = fc sinc(fc n) kaiser(2 half + 1, beta), scaled to h.sum() == 1.
+    The defaults are the parameters of librosa's historical `kaiser_best` (64 zero crossings, its beta and roll-off);
+    librosa evaluates a stored table of that window by interpolation, so the taps are not claimed equal to its."""
+    m = max(int(up), int(down))
+    half = int(num_zeros) * m
+    n = np.arange(-half, half + 1, dtype=np.float64)
+    fc = float(rolloff) / m
+    h = fc * np.sinc(fc * n) * np.kaiser(2 * half + 1, float(beta))
+    return h / h.sum()
+
+
+def polyphase_table(h, up):
+    """The tap table mg_resample_poly takes (mixgan_hip.h), float64 [up, Kp]: row r, column j holds
+    up h[(Mh - 1 - j) up + r + half] with Mh = half // up + 1, 0 where that index leaves h; Kp = 2 Mh rounded up to a
+    multiple of 4."""
+    h = np.asarray(h, dtype=np.float64)
+    if h.ndim != 1 or len(h) % 2 != 1:
+        raise ValueError("polyphase_table: the filter must have odd length, got shape %s" % (h.shape,))
+    half = (len(h) - 1) // 2
+    Mh = half // up + 1
+    Kp = -(-2 * Mh // 4) * 4
+    idx = (Mh - 1 - np.arange(Kp))[None, :] * up + np.arange(up)[:, None] + half
+    ok = (idx >= 0) & (idx <= 2 * half)
+    return np.where(ok, up * h[np.clip(idx, 0, 2 * half)], 0.0)
+
+
+_RESAMPLE_TABLES = {}
+
+
+def _resample_table(up, down, device, num_zeros=64, beta=14.769656459379492, rolloff=0.9475937167399596):
+    key = (up, down, int(num_zeros), float(beta), float(rolloff), str(device))
+    if key not in _RESAMPLE_TABLES:
+        h = resample_filter(up, down, num_zeros, beta, rolloff)
+        table = polyphase_table(h, up)
+        span = (RESAMPLE_TILE - 1) * down // up + table.shape[1] + 2
+        if up > _lib.MG_RESAMPLE_MAX_UP or table.shape[1] > _lib.MG_RESAMPLE_MAX_TAPS or span > _lib.MG_RESAMPLE_MAX_SPAN:
+            raise AudioGeometryError(
+                "resample: ratio %d:%d with %d taps per output is outside the kernel's limits (up <= %d, taps <= %d, "
+                "staged span %d <= %d)" % (up, down, table.shape[1], _lib.MG_RESAMPLE_MAX_UP,
+                                           _lib.MG_RESAMPLE_MAX_TAPS, span, _lib.MG_RESAMPLE_MAX_SPAN))
+        _RESAMPLE_TABLES[key] = (torch.from_numpy(table.astype(np.float32)).to(device), (len(h) - 1) // 2)
+    return _RESAMPLE_TABLES[key]
+
+
+def _ragged(wav, lengths, what):
+    """wav [N] or [B, N] on the GPU -> (x [B, N] contiguous fp32, host lengths int64 [B], device int32 [B] or None,
+    whether the input was 1-D)."""
+    _cuda(wav, "wav")
+    if wav.dim() not in (1, 2) or wav.shape[-1] == 0:
+        raise ValueError("%s: expected a non-empty [N] or [B, N] signal, got %s" % (what, tuple(wav.shape)))
+    x = (wav if wav.dim() == 2 else wav.unsqueeze(0)).float().contiguous()
+    B, N = x.shape
+    if lengths is None:
+        return x, np.full(B, N, dtype=np.int64), None, wav.dim() == 1
+    lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths).astype(np.int64).reshape(-1)
+    if lens.shape != (B,) or (lens < 0).any() or (lens > N).any():
+        raise ValueError("%s: lengths must be %d values in [0, %d], got %s" % (what, B, N, lens.tolist()))
+    return x, lens, torch.from_numpy(lens.astype(np.int32)).to(x.device), wav.dim() == 1
+
+
+def resample(wav, orig_sr, target_sr, lengths=None, **filter_params):
+    """wav [N] or [B, N] at orig_sr -> (out [M] or [B, M], out_lengths) at target_sr, on the device.
+
+    lengths (B ints, optional) makes the batch ragged: item b is its first lengths[b] samples, nothing beyond them is
+    read, and it equals a call on it alone.  out_lengths is a device int32 [B] (B = 1 for a 1-D wav) holding
+    ceil(lengths up / down) for the reduced ratio up / down; M is its maximum and out is 0 beyond each length.
+    filter_params go to `resample_filter`; tables are built in float64 once per (ratio, parameters, device).
+    Equal rates copy."""
+    x, lens, len_dev, squeeze = _ragged(wav, lengths, "resample")
+    up, down = resample_ratio(orig_sr, target_sr)
+    B, N = x.shape
+    out_lens = -(-lens * up // down)
+    M = max(1, int(out_lens.max()))
+    if N >= 2 ** 31 or M >= 2 ** 31:
+        raise AudioGeometryError("resample: rows of 2^31 samples or more are not supported")
+    out = torch.empty(B, M, device=x.device, dtype=torch.float32)
+    if up == down:
+        taps, half, Kp = None, 0, 0
+    else:
+        taps, half = _resample_table(up, down, x.device, **filter_params)
+        Kp = taps.shape[1]
+    check(_lib.lib().mg_resample_poly(fptr(x), N, iptr(len_dev, torch.int32, allow_none=True), B, N,
+                                      fptr(taps, allow_none=True), up, down, Kp, half, fptr(out), M, M, stream_ptr()))
+    out_len_dev = torch.from_numpy(out_lens.astype(np.int32)).to(x.device)
+    return (out[0] if squeeze else out), out_len_dev
+
+
+def peak_normalize_int16(wav, lengths=None, max_wav_value=32768.0):
+    """wav [N] or [B, N] -> int16 of the same shape: trunc(wav / max|wav| * max_wav_value) per item in float32,
+    saturated to [-32768, 32767]; the maximum is over the first lengths[b] samples, the rest is written as 0, and an
+    all-zero item stays zero."""
+    x, _, len_dev, squeeze = _ragged(wav, lengths, "peak_normalize_int16")
+    B, N = x.shape
+    out = torch.empty(B, N, device=x.device, dtype=torch.int16)
+    check(_lib.lib().mg_peak_normalize_i16(fptr(x), N, iptr(len_dev, torch.int32, allow_none=True), B, N,
+                                           float(max_wav_value), ctypes.c_void_p(out.data_ptr()), N, stream_ptr()))
+    return out[0] if squeeze else out

@@ -9,8 +9,10 @@ utterances at a time, with one device -> host copy per array kind.
 Injected, as `text_to_sequence` is in data.py:
 - `pitch_fn(wav_float64, sampling_rate, frame_period_ms) -> f0 [frames]`; the default is pyworld's dio + stonemask,
   imported when first needed (PitchExtractorRequired names the argument when pyworld is missing);
-- `load_wav(path) -> float array in [-1, 1)`; the default reads with scipy.io.wavfile and refuses a file whose rate
-  is not `sampling_rate` (the reference resamples through librosa).
+- `load_wav(path) -> float array in [-1, 1)`; the default reads with scipy.io.wavfile.  A file whose rate is not
+  `sampling_rate` raises SamplingRateMismatch, or with `resample=True` is resampled on the device by
+  audio.resample (the reference resamples silently through librosa.load; prepare_align.py is the stage that brings a
+  whole corpus to the configured rate).
 
 Deviations from the reference:
 - directory entries are visited in sorted order (the reference takes the file system's order, which also decides
@@ -43,7 +45,7 @@ class PitchExtractorRequired(MixganHipError, ImportError):
 
 
 class SamplingRateMismatch(MixganHipError, ValueError):
-    """A wav whose sampling rate is not the configured one (there is no resampler here)."""
+    """A wav whose sampling rate is not the configured one, met without resample=True."""
 
 
 class TextGridError(MixganHipError, ValueError):
@@ -230,21 +232,33 @@ def split_metadata(out, train, val, val_prior, val_size, sort_data, mel_frame_le
     return train, val
 
 
-def scipy_load_wav(sampling_rate):
-    """load_wav default: scipy.io.wavfile, integer PCM scaled to [-1, 1), channels averaged."""
+def read_wav(path):
+    """(rate, float32 mono samples) of a wav of any rate, read with scipy.io.wavfile: integer PCM scaled to [-1, 1),
+    float taken as it is, channels averaged."""
+    from scipy.io import wavfile
+    sr, x = wavfile.read(path)
+    if x.dtype == np.uint8:
+        x = (x.astype(np.float32) - 128.0) / 128.0
+    elif np.issubdtype(x.dtype, np.integer):
+        x = x.astype(np.float32) / float(2 ** (8 * x.dtype.itemsize - 1))
+    else:
+        x = x.astype(np.float32)
+    return int(sr), (x.mean(axis=1) if x.ndim == 2 else x)
+
+
+def scipy_load_wav(sampling_rate, resample=False, device="cuda"):
+    """load_wav default: `read_wav`.  A file at another rate raises SamplingRateMismatch, or with `resample` goes
+    through audio.resample on `device` (what the reference's librosa.load does silently)."""
     def load(path):
-        from scipy.io import wavfile
-        sr, x = wavfile.read(path)
+        sr, x = read_wav(path)
         if sr != sampling_rate:
-            raise SamplingRateMismatch("%s is sampled at %d Hz, the corpus is configured for %d Hz: resample it "
-                                       "first, or pass load_wav=" % (path, sr, sampling_rate))
-        if x.dtype == np.uint8:
-            x = (x.astype(np.float32) - 128.0) / 128.0
-        elif np.issubdtype(x.dtype, np.integer):
-            x = x.astype(np.float32) / float(2 ** (8 * x.dtype.itemsize - 1))
-        else:
-            x = x.astype(np.float32)
-        return x.mean(axis=1) if x.ndim == 2 else x
+            if not resample:
+                raise SamplingRateMismatch("%s is sampled at %d Hz, the corpus is configured for %d Hz: run "
+                                           "prepare_align first, pass resample=True, or pass load_wav="
+                                           % (path, sr, sampling_rate))
+            out, _ = Audio.resample(torch.from_numpy(np.ascontiguousarray(x)).to(device), sr, sampling_rate)
+            x = out.cpu().numpy()
+        return x
     return load
 
 
@@ -265,7 +279,7 @@ def pyworld_pitch(wav, sampling_rate, frame_period_ms):
 # ---------------------------------------------------------------------------------------------
 class Preprocessor:
     def __init__(self, preprocess_config, model_config, train_config, pitch_fn=None, load_wav=None,
-                 batch_utterances=16, device="cuda"):
+                 batch_utterances=16, device="cuda", resample=False):
         pp = preprocess_config["preprocessing"]
         self.preprocess_config = preprocess_config
         self.in_dir = preprocess_config["path"]["raw_path"]
@@ -291,9 +305,9 @@ class Preprocessor:
                                        pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         self.val_prior = self.val_prior_names(os.path.join(self.out_dir, "val.txt"))
         self.pitch_fn = pitch_fn or pyworld_pitch
-        self.load_wav = load_wav or scipy_load_wav(self.sampling_rate)
         self.batch_utterances = max(1, int(batch_utterances))
         self.device = torch.device(device)
+        self.load_wav = load_wav or scipy_load_wav(self.sampling_rate, resample, self.device)
         self.speaker_emb = None
         self.in_sub_dirs = [p for p in sorted(os.listdir(self.in_dir)) if os.path.isdir(os.path.join(self.in_dir, p))]
         if self.multi_speaker and pp["speaker_embedder"] != "none":
