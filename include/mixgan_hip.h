@@ -751,6 +751,43 @@ int mg_resample_poly(const float *x, long x_bs, const int *lengths, int B, int N
 int mg_peak_normalize_i16(const float *x, long x_bs, const int *lengths, int B, int N, float max_wav_value,
                           int16_t *out, long out_bs, void *stream);
 
+/* ------------------------------------------------------------------ pitch extraction (csrc/pitch.hip; stands where
+ * preprocessor.py:295-300 calls pyworld, with no claim of parity).  Both calls take ragged batches.
+ * Stage 1, YIN candidates: x [B, L] with batch stride x_bs, lengths [B] device int32 (null: all L; clamped to
+ * [0, L]); row b has lengths[b] / hop + 1 frames, frame k the MG_PITCH_N samples from k hop - MG_PITCH_N / 2 on, zero
+ * outside the row (nothing at or past lengths[b] is read).  With W = MG_PITCH_W,
+ *   d(tau) = sum_{j < W} (x_j - x_{j+tau})^2,  d'(tau) = d(tau) tau / sum_{1 <= j <= tau} d(j)  (1 at tau = 0 and where
+ * the sum is 0), and the MG_PITCH_K deepest local minima of d' over [tau_min, tau_max] (strictly below the left
+ * neighbour, not above the right one) leave in increasing lag: period [B, T, K] = lag + a three-point parabolic offset
+ * clamped to +-0.5 (0 when the second difference is not positive), cost [B, T, K] = d' at the lag; an empty slot holds
+ * period 0 and cost 1e30.  rms [B, T] is the frame's root mean square over its MG_PITCH_N samples.  Frames at or past
+ * a row's count are zero in all three.  MG_ERR_SHAPE unless 2 <= tau_min <= tau_max, tau_max + 1 <= MG_PITCH_N -
+ * MG_PITCH_W, hop >= 1 and 1 <= T <= L / hop + 1.  twiddle: the 1024 complex float32 roots exp(-2 pi i n / 1024). */
+#define MG_PITCH_N 1024
+#define MG_PITCH_W 512
+#define MG_PITCH_K 4
+int mg_yin_candidates(const float *x, long x_bs, const int *lengths, int B, int L, int hop, int tau_min, int tau_max,
+                      const float *twiddle, float *period, float *cost, float *rms, int T, void *stream);
+/* Stage 2, the track: a Viterbi pass per row over the K candidate slots and one unvoiced state, in float64, over the
+ * first n_frames[b] (device int32, clamped to [0, T]) frames of stage 1's output.  params is a host array of
+ * MG_PITCH_PARAMS doubles indexed by MG_PITCH_P_*: the sampling rate, tau_max, theta (cost of an unvoiced frame),
+ * beta (a voiced slot costs cost + beta period / tau_max), lambda (voiced to voiced costs lambda |log2 p_a - log2 p_b|),
+ * switch (voiced to unvoiced and back) and gate (frames whose rms is below gate times the row's largest have no voiced
+ * state).  Ties go to the lowest state.  f0 [B, T] float64 = rate / period on voiced frames, 0 elsewhere and past
+ * n_frames[b].  workspace: mg_pitch_track_workspace_bytes(B, T) bytes of device memory for the back-pointers;
+ * MG_ERR_WORKSPACE when it is null or smaller. */
+#define MG_PITCH_PARAMS 7
+#define MG_PITCH_P_SR 0
+#define MG_PITCH_P_TAU_MAX 1
+#define MG_PITCH_P_THETA 2
+#define MG_PITCH_P_BETA 3
+#define MG_PITCH_P_LAMBDA 4
+#define MG_PITCH_P_SWITCH 5
+#define MG_PITCH_P_GATE 6
+size_t mg_pitch_track_workspace_bytes(int B, int T);
+int mg_pitch_track(const float *period, const float *cost, const float *rms, const int *n_frames, int B, int T,
+                   const double *params, double *f0, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

@@ -29,6 +29,9 @@ MG_DEN_HEAD_PTRS, MG_DEN_LAYER_PTRS = 8, 9
  MG_DEN_L_SPK_W, MG_DEN_L_RESERVED) = range(MG_DEN_LAYER_PTRS)
 MG_LOSS_MAX_TERMS, MG_LOSS_GROUPS = 16, 4
 MG_RESAMPLE_MAX_UP, MG_RESAMPLE_MAX_TAPS, MG_RESAMPLE_TILE, MG_RESAMPLE_MAX_SPAN = 1024, 1024, 1024, 16384
+MG_PITCH_N, MG_PITCH_W, MG_PITCH_K, MG_PITCH_PARAMS = 1024, 512, 4, 7
+(MG_PITCH_P_SR, MG_PITCH_P_TAU_MAX, MG_PITCH_P_THETA, MG_PITCH_P_BETA, MG_PITCH_P_LAMBDA, MG_PITCH_P_SWITCH,
+ MG_PITCH_P_GATE) = range(MG_PITCH_PARAMS)
 
 
 class LossTerm(ctypes.Structure):
@@ -203,6 +206,9 @@ def _signatures():
         "mg_phoneme_average": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_resample_poly": (i, [vp, lg, vp, i, i, vp, i, i, i, i, vp, lg, i, vp]),
         "mg_peak_normalize_i16": (i, [vp, lg, vp, i, i, f, vp, lg, vp]),
+        "mg_yin_candidates": (i, [vp, lg, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]),
+        "mg_pitch_track_workspace_bytes": (sz, [i, i]),
+        "mg_pitch_track": (i, [vp, vp, vp, vp, i, i, ctypes.POINTER(ctypes.c_double), vp, vp, sz, vp]),
     }
 
 

@@ -8,7 +8,10 @@ utterances at a time, with one device -> host copy per array kind.
 
 Injected, as `text_to_sequence` is in data.py:
 - `pitch_fn(wav_float64, sampling_rate, frame_period_ms) -> f0 [frames]`; the default is pyworld's dio + stonemask,
-  imported when first needed (PitchExtractorRequired names the argument when pyworld is missing);
+  imported when first needed (PitchExtractorRequired names the argument when pyworld is missing).
+  `pitch_fn="native"` needs neither: the batch's wavs go to the device once, pitch.extract_f0 tracks them all in one
+  launch pair (csrc/pitch.hip, an extractor of this project's own, not pyworld's), and mel and energy read the same
+  upload;
 - `load_wav(path) -> float array in [-1, 1)`; the default reads with scipy.io.wavfile.  A file whose rate is not
   `sampling_rate` raises SamplingRateMismatch, or with `resample=True` is resampled on the device by
   audio.resample (the reference resamples silently through librosa.load; prepare_align.py is the stage that brings a
@@ -34,6 +37,7 @@ import torch
 
 from . import audio as Audio
 from . import corpusops
+from . import pitch as Pitch
 from ._lib import MixganHipError
 from .speaker_embedder import PreDefinedEmbedder, save_speaker_embeddings
 
@@ -304,7 +308,12 @@ class Preprocessor:
                                        pp["mel"]["n_mel_channels"], pp["audio"]["sampling_rate"],
                                        pp["mel"]["mel_fmin"], pp["mel"]["mel_fmax"])
         self.val_prior = self.val_prior_names(os.path.join(self.out_dir, "val.txt"))
-        self.pitch_fn = pitch_fn or pyworld_pitch
+        self.native_pitch = isinstance(pitch_fn, str)
+        if self.native_pitch:
+            if pitch_fn != "native":
+                raise ValueError("Preprocessor: pitch_fn must be a callable, None or \"native\", got %r" % (pitch_fn,))
+            Pitch.pitch_geometry(self.sampling_rate)      # a rate the kernels do not take fails here, not mid-corpus
+        self.pitch_fn = None if self.native_pitch else (pitch_fn or pyworld_pitch)
         self.batch_utterances = max(1, int(batch_utterances))
         self.device = torch.device(device)
         self.load_wav = load_wav or scipy_load_wav(self.sampling_rate, resample, self.device)
@@ -327,7 +336,8 @@ class Preprocessor:
 
     def prepare_utterance(self, speaker, basename, save_speaker_emb=False):
         """preprocessor.py:263-304: alignment, trimmed wav, raw text and f0.  None when the utterance is filtered out
-        (empty alignment, or at most one voiced frame)."""
+        (empty alignment, or at most one voiced frame).  With pitch_fn="native" the item leaves without "pitch":
+        `native_pitch_batch` adds it, and applies the voiced-frame rule, for the whole batch."""
         tiers = read_textgrid(self._tg_path(speaker, basename))
         for name in ("phones", "words"):
             if name not in tiers:
@@ -343,29 +353,59 @@ class Preprocessor:
         wav = wav[int(self.sampling_rate * start):int(self.sampling_rate * end)].astype(np.float32)
         with open(os.path.join(self.in_dir, speaker, "{}.lab".format(basename)), "r") as f:
             raw_text = f.readline().strip("\n")
-        pitch = np.asarray(self.pitch_fn(wav.astype(np.float64), self.sampling_rate,
-                                         self.hop_length / self.sampling_rate * 1000), dtype=np.float64)
-        pitch = pitch[:sum(duration)]
-        if np.sum(pitch != 0) <= 1:
-            return None
+        pitch = None
+        if not self.native_pitch:
+            pitch = np.asarray(self.pitch_fn(wav.astype(np.float64), self.sampling_rate,
+                                             self.hop_length / self.sampling_rate * 1000), dtype=np.float64)
+            pitch = pitch[:sum(duration)]
+            if np.sum(pitch != 0) <= 1:
+                return None
         return {"speaker": speaker, "basename": basename, "text": "{" + " ".join(phone) + "}", "raw_text": raw_text,
                 "duration": duration, "phones_per_word": phones_per_word, "wav": wav, "pitch": pitch,
                 "spker_embed": spker_embed}
 
     # ------------------------------------------------------------------ device stage of a batch
-    def process_batch(self, items):
+    def _upload(self, items):
+        """The batch's wavs, clipped to [-1, 1] and zero-padded to the longest: (device [B, max len], lengths)."""
+        wav_len = np.array([len(it["wav"]) for it in items], dtype=np.int64)
+        wavs = np.zeros((len(items), max(1, int(wav_len.max()))), dtype=np.float32)
+        for b, it in enumerate(items):
+            wavs[b, :wav_len[b]] = np.clip(it["wav"], -1, 1)
+        return torch.from_numpy(wavs).to(self.device), wav_len
+
+    def native_pitch_batch(self, items):
+        """pitch_fn="native": F0 of every item of the batch in one launch pair, cut to sum(duration) as the host path
+        cuts it.  Returns (kept items, dropped items, the kept rows of the upload): an item with at most one voiced
+        frame is dropped, as prepare_utterance drops it on the host path."""
+        wavs, wav_len = self._upload(items)
+        f0, _ = Pitch.extract_f0(wavs, self.sampling_rate, self.hop_length, wav_len)
+        f0 = f0.cpu().numpy()
+        kept, dropped, rows = [], [], []
+        for b, it in enumerate(items):
+            pitch = f0[b, :min(Pitch.frame_count(int(wav_len[b]), self.hop_length), sum(it["duration"]))].copy()
+            if np.sum(pitch != 0) <= 1:
+                dropped.append(it)
+                continue
+            it["pitch"] = pitch
+            kept.append(it)
+            rows.append(b)
+        if len(rows) != len(items):
+            wavs = wavs[torch.tensor(rows, dtype=torch.long, device=wavs.device)] if rows else None
+        return kept, dropped, wavs
+
+    def process_batch(self, items, wavs=None):
         """preprocessor.py:306-382 for a list of prepare_utterance results: mel, energy, phoneme averages and prior on
-        the GPU, the files, and per item (info line, kept pitch, kept energy, n frames, mel min, mel max)."""
+        the GPU, the files, and per item (info line, kept pitch, kept energy, n frames, mel min, mel max).  wavs: the
+        items' rows of `_upload`, when the caller holds them already."""
         dev, B = self.device, len(items)
         n_phon = np.array([len(it["duration"]) for it in items], dtype=np.int32)
         total = np.array([sum(it["duration"]) for it in items], dtype=np.int64)
         wav_len = np.array([len(it["wav"]) for it in items], dtype=np.int64)
-        wavs = np.zeros((B, int(wav_len.max())), dtype=np.float32)
-        for b, it in enumerate(items):
-            wavs[b, :wav_len[b]] = np.clip(it["wav"], -1, 1)
+        if wavs is None:
+            wavs, _ = self._upload(items)
         if self.STFT.mel_basis.device != dev:
             self.STFT = self.STFT.to(dev)
-        mel, energy = self.STFT.mel_spectrogram(torch.from_numpy(wavs).to(dev), wav_len)
+        mel, energy = self.STFT.mel_spectrogram(wavs, wav_len)
         mel_len = np.minimum(total, 1 + wav_len // self.hop_length).astype(np.int32)
         L, T = int(mel_len.max()), int(n_phon.max())
         mel, energy = mel[:, :, :L], energy[:, :L].contiguous()
@@ -440,9 +480,13 @@ class Preprocessor:
                         filtered_out.add(basename)
                     else:
                         items.append(item)
+                wavs = None
+                if self.native_pitch and items:
+                    items, dropped, wavs = self.native_pitch_batch(items)
+                    filtered_out.update(it["basename"] for it in dropped)
                 if not items:
                     continue
-                for item, (info, pitch, energy, n, m_min, m_max) in zip(items, self.process_batch(items)):
+                for item, (info, pitch, energy, n, m_min, m_max) in zip(items, self.process_batch(items, wavs)):
                     basename = item["basename"]
                     if self.val_prior is not None:
                         (val if basename in self.val_prior else train).append(info)
