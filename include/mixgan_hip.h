@@ -788,6 +788,47 @@ size_t mg_pitch_track_workspace_bytes(int B, int T);
 int mg_pitch_track(const float *period, const float *cost, const float *rms, const int *n_frames, int B, int T,
                    const double *params, double *f0, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ forced alignment (aligner.py; csrc/align.hip;
+ * stands where the corpus chain calls the Montreal Forced Aligner, with no claim of parity).  A monophone left-to-right
+ * HMM with one diagonal Gaussian per state; all three calls take ragged batches, read nothing at or past a row's
+ * length, use no atomics and give a row the same bits wherever it sits in the batch.
+ * Emissions: x [B, T, D] features, n_frames [B] device int32, tables A, Bm [G, D] and c [G]
+ * (A = -0.5 / var, Bm = mean / var, c = -0.5 sum_d (mean^2 / var + log(2 pi var))):
+ *   ll[b, t, g] = sum_d (A[g, d] x[b, t, d]^2 + Bm[g, d] x[b, t, d]) + c[g]   for t < n_frames[b], 0 elsewhere,
+ * accumulated in float32 over ascending d.  MG_ERR_SHAPE unless B, T >= 1, 1 <= D <= MG_ALIGN_MAX_D,
+ * 1 <= G <= MG_ALIGN_MAX_G and B T <= 65535 * 64. */
+#define MG_ALIGN_MAX_D 128
+#define MG_ALIGN_MAX_G 1024
+#define MG_ALIGN_MAX_S 2048
+#define MG_ALIGN_MAX_T 4096
+int mg_align_emissions(const float *x, const int *n_frames, int B, int T, int D, const float *A, const float *Bm,
+                       const float *c, int G, float *ll, void *stream);
+/* Viterbi: ll [B, T, G] as above, seq int32 [B, S] the Gaussian of each state (clamped to [0, G)), skip uint8 [B, S]
+ * non-zero where a state may be passed over, n_frames / n_states int32 [B] (clamped to [0, T] / [0, S]), all on the
+ * device.  With e_t(s) = ll[b, t, seq[b, s]], in float64:
+ *   delta_0(s) = e_0(s) for s = 0, and for s = 1 if skip[0]; -inf otherwise,
+ *   delta_t(s) = e_t(s) + max(delta_{t-1}(s), delta_{t-1}(s-1), skip[s-1] ? delta_{t-1}(s-2) : -inf),
+ * ties to the smallest jump (stay, then advance, then skip); the path ends in state n_states - 1, or in n_states - 2
+ * when skip[n_states - 1] and its delta is strictly larger.  A skippable state must have non-skippable neighbours:
+ * skip lives on the device, so this call cannot check it, and the Python wrapper refuses two adjacent skippable states
+ * (MG_ERR_SHAPE) before it uploads them.  durations int32 [B, S]: frames spent in each state, 0 for a state passed
+ * over and for s >= n_states[b]; score [B] float64: delta at the end; ok int32 [B]: 0, with all-zero durations and
+ * score -inf, when no path exists (fewer frames than non-skippable states, no frames, no states).
+ * 1 <= S <= MG_ALIGN_MAX_S, 1 <= T <= MG_ALIGN_MAX_T, 1 <= G <= MG_ALIGN_MAX_G.  workspace:
+ * mg_align_viterbi_workspace_bytes(B, T, S) bytes of device memory for the back-pointers, two bits each;
+ * MG_ERR_WORKSPACE when it is null or smaller. */
+size_t mg_align_viterbi_workspace_bytes(int B, int T, int S);
+int mg_align_viterbi(const float *ll, const int *seq, const uint8_t *skip, const int *n_frames, const int *n_states,
+                     int B, int T, int S, int G, int *durations, double *score, int *ok, void *workspace,
+                     size_t workspace_bytes, void *stream);
+/* Statistics of the hard-EM update: x [rows, D]; frame_index int32: the row numbers of the frames in use, stably
+ * sorted by Gaussian; offsets int32 [G + 1]: Gaussian g owns frame_index[offsets[g] : offsets[g + 1]].  sum and
+ * sumsq float64 [G, D]: the sums of x and x^2 over the Gaussian's rows, added in list order; zeros for an empty
+ * segment.  The lists live on the device: their bounds are the caller's to keep (the Python wrapper checks them).
+ * 1 <= D <= MG_ALIGN_MAX_D, 1 <= G <= MG_ALIGN_MAX_G. */
+int mg_align_stats(const float *x, const int *frame_index, const int *offsets, int G, int D, double *sum,
+                   double *sumsq, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

@@ -31,10 +31,13 @@ from .speaker_embedder import (DeepSpeakerModel, PreDefinedEmbedder, DeepSpeaker
 
 from . import corpusops, preprocessor  # noqa: F401
 from .corpusops import attn_prior, phoneme_average  # noqa: F401
-from .preprocessor import Preprocessor, PitchExtractorRequired, read_textgrid  # noqa: F401
+from .preprocessor import Preprocessor, PitchExtractorRequired, read_textgrid, write_textgrid  # noqa: F401
 from . import prepare_align  # noqa: F401
 from .audio import resample, resample_filter, peak_normalize_int16  # noqa: F401
 from . import pitch  # noqa: F401
 from .pitch import yin_candidates, pitch_track, extract_f0, native_pitch, PitchGeometryError  # noqa: F401
+from . import aligner  # noqa: F401
+from .aligner import (ForcedAligner, AlignGeometryError, emissions, viterbi_align, gaussian_stats,  # noqa: F401
+                      read_lexicon)
 
 __version__ = "0.1.0"

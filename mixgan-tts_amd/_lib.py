@@ -32,6 +32,7 @@ MG_RESAMPLE_MAX_UP, MG_RESAMPLE_MAX_TAPS, MG_RESAMPLE_TILE, MG_RESAMPLE_MAX_SPAN
 MG_PITCH_N, MG_PITCH_W, MG_PITCH_K, MG_PITCH_PARAMS = 1024, 512, 4, 7
 (MG_PITCH_P_SR, MG_PITCH_P_TAU_MAX, MG_PITCH_P_THETA, MG_PITCH_P_BETA, MG_PITCH_P_LAMBDA, MG_PITCH_P_SWITCH,
  MG_PITCH_P_GATE) = range(MG_PITCH_PARAMS)
+MG_ALIGN_MAX_D, MG_ALIGN_MAX_G, MG_ALIGN_MAX_S, MG_ALIGN_MAX_T = 128, 1024, 2048, 4096
 
 
 class LossTerm(ctypes.Structure):
@@ -209,6 +210,10 @@ def _signatures():
         "mg_yin_candidates": (i, [vp, lg, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]),
         "mg_pitch_track_workspace_bytes": (sz, [i, i]),
         "mg_pitch_track": (i, [vp, vp, vp, vp, i, i, ctypes.POINTER(ctypes.c_double), vp, vp, sz, vp]),
+        "mg_align_emissions": (i, [vp, vp, i, i, i, vp, vp, vp, i, vp, vp]),
+        "mg_align_viterbi_workspace_bytes": (sz, [i, i, i]),
+        "mg_align_viterbi": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]),
+        "mg_align_stats": (i, [vp, vp, vp, i, i, vp, vp, vp]),
     }
 
 

@@ -112,6 +112,27 @@ def read_textgrid(path, include_empty_intervals=False, encoding="utf-8"):
     return tiers
 
 
+def write_textgrid(path, tiers, xmax, encoding="utf-8"):
+    """Interval tiers {name: [(start, end, text), ...]} (or a list of such pairs, in file order) -> a long-format
+    TextGrid that `read_textgrid` reads back.  Every time is written with %r, the shortest text that gives the same
+    float again, so two boundaries written from one float compare equal after reading (`get_alignment` matches a
+    word's end to its last phone's with ==) and `round(t sampling_rate / hop)` of a time k hop / sampling_rate is k."""
+    tiers = list(tiers.items()) if isinstance(tiers, dict) else list(tiers)
+    xmax = float(xmax)
+    out = ['File type = "ooTextFile"', 'Object class = "TextGrid"', "", "xmin = 0", "xmax = %r" % xmax,
+           "tiers? <exists>", "size = %d" % len(tiers), "item []:"]
+    for t, (name, ivs) in enumerate(tiers, 1):
+        out += ["    item [%d]:" % t, '        class = "IntervalTier"', '        name = "%s"' % name.replace('"', '""'),
+                "        xmin = 0", "        xmax = %r" % xmax, "        intervals: size = %d" % len(ivs)]
+        for j, (s, e, text) in enumerate(ivs, 1):
+            if "\n" in text or "\r" in text:
+                raise TextGridError("%s: an interval text with a line break: %r" % (path, text))
+            out += ["        intervals [%d]:" % j, "            xmin = %r" % float(s), "            xmax = %r" % float(e),
+                    '            text = "%s"' % text.replace('"', '""')]
+    with open(path, "w", encoding=encoding) as f:
+        f.write("\n".join(out) + "\n")
+
+
 # ---------------------------------------------------------------------------------------------
 # Host pieces of process_utterance / build_from_path
 # ---------------------------------------------------------------------------------------------
