@@ -129,6 +129,27 @@ int mg_conv1d_fwd_split(const float *in, const float *in_vec, const float *packe
                         int pad, int dil, float in_slope, int act, float act_slope, float alpha, int accumulate,
                         float *scratch, size_t scratch_floats, void *stream);
 
+/* Which instantiation of the convolution kernel a launch runs, and on what grid: the decision the launcher itself
+ * switches on (conv_plan, csrc/conv_mfma.h).  rows: GEMM rows of the packed weight (Co; Co * u for the polyphase
+ * transposed convolution, where Lout is the input length).  scratch_floats: the split-reduction scratch of
+ * mg_conv1d_fwd_split, 0 = none.  epi: which set of instantiations the entry point has --
+ * mg_conv1d_fwd / _ex / _split, mg_conv_transpose1d_fwd and mg_conv1x1_fwd_strided are MG_CONV_EPI_PLAIN.
+ * MG_ERR_SHAPE where the launch would return it (no instantiation).  No GPU work. */
+#define MG_CONV_EPI_PLAIN 0        /* K in {1,3,5,9} (K = 5 also at stride 2); K in {3,7,11} at dil <= 5, K in {4,16} */
+#define MG_CONV_EPI_REFLECT 1      /* mg_conv1d_reflect_fwd: K = 3 at dil <= 9, K = 7 */
+#define MG_CONV_EPI_PHASES_SLICE 2 /* mg_conv_transpose1d_fwd_slice: K = 3 */
+#define MG_CONV_EPI_NEEDS_WM2 3    /* an epilogue that pairs 32-row blocks (the denoiser's gate): K in {1,3,5,9}, never
+                                    * the one-block-per-wave forms */
+typedef struct mg_conv_plan {
+    int32_t kw, stride, ck, dilmax; /* the (K, stride, chunk channels, largest dilation) case */
+    int32_t mw, wm, nnb;            /* waves along the rows, 32-row blocks and 32-frame blocks per wave:
+                                     * a workgroup tile of 32 mw wm rows x 32 (4 / mw) nnb frames */
+    int32_t ksplit;                 /* workgroups sharing a tile's reduction (1: unsplit) */
+    int32_t grid;                   /* workgroups of the convolution launch: tiles x ksplit */
+} mg_conv_plan;
+int mg_conv1d_fwd_plan(int B, int Ci, int Lout, int rows, int K, int stride, int dil, size_t scratch_floats, int epi,
+                       mg_conv_plan *out);
+
 /* ------------------------------------------------------------------ diffusion algebra (HBM-bound)
  * Schedule tables are the fp32 buffers of GaussianDiffusion (model/diffusion.py:60-83). */
 

@@ -21,6 +21,7 @@ MG_DEN_BACKWARD, MG_DEN_SPLIT, MG_DEN_P16, MG_DEN_JOBS_RESIDENT = 1, 2, 4, 8    
 MG_FWD_SAVE, MG_FWD_SPLIT, MG_FWD_P16 = 1, 2, 4                                   # mg_denoiser_fwd modes
 MG_PLAN_PER_LAYER, MG_PLAN_SINGLE = 0, 1                                          # mg_fwd_plan.path
 MG_PLAN_PERSIST, MG_PLAN_PERSIST16, MG_PLAN_TEAM16 = 0, 1, 2                      # mg_fwd_plan.family
+MG_CONV_EPI_PLAIN, MG_CONV_EPI_REFLECT, MG_CONV_EPI_PHASES_SLICE, MG_CONV_EPI_NEEDS_WM2 = range(4)   # mg_conv1d_fwd_plan
 # the denoiser's weight / gradient pointer table: head slots, then MG_DEN_LAYER_PTRS slots per residual layer
 MG_DEN_HEAD_PTRS, MG_DEN_LAYER_PTRS = 8, 9
 (MG_DEN_IN_W, MG_DEN_IN_B, MG_DEN_MLP0_W, MG_DEN_MLP2_W, MG_DEN_SKIP_W, MG_DEN_SKIP_B, MG_DEN_OUT_W,
@@ -55,6 +56,11 @@ class FwdPlan(ctypes.Structure):
     """mg_fwd_plan (include/mixgan_hip.h): which kernel the denoiser forward runs."""
     _fields_ = [(n, ctypes.c_int32) for n in ("path", "family", "nt", "waves", "solo", "team", "cproj_mode", "grid",
                                               "block")]
+
+
+class ConvPlan(ctypes.Structure):
+    """mg_conv_plan (include/mixgan_hip.h): which instantiation of the convolution kernel a launch runs."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kw", "stride", "ck", "dilmax", "mw", "wm", "nnb", "ksplit", "grid")]
 
 
 def library_path():
@@ -96,6 +102,7 @@ def _signatures():
         "mg_conv1d_fwd": (i, [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, vp]),
         "mg_conv1d_fwd_ex": (i, [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, f, f, i, vp]),
         "mg_conv1d_fwd_split": (i, [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, i, f, f, i, vp, sz, vp]),
+        "mg_conv1d_fwd_plan": (i, [i, i, i, i, i, i, i, sz, i, ctypes.POINTER(ConvPlan)]),
         "mg_upsample_zero_act": (i, [vp, vp, i, i, i, i, f, vp]),
         "mg_diffuse_trace_bwd": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_bgemm": (i, [vp, vp, vp, i, i, i, i, i] + [lg] * 11 + [f, i, vp]),

@@ -75,6 +75,26 @@ extern "C" int mg_conv_transpose_pack(const float *w, float *packed, int Ci, int
 template <>
 struct EpiWide<EpiBiasAct> { static constexpr bool value = true; };
 
+// conv_plan for an entry point's epilogue: EpiBiasAct as this file instantiates it, the MelGAN epilogues of melgan.hip
+// (EpiMelGAN 1 / 2), the denoiser's gate (EpiNeedsWM2, base cases only).
+extern "C" int mg_conv1d_fwd_plan(int B, int Ci, int Lout, int rows, int K, int stride, int dil, size_t scratch_floats,
+                                  int epi, mg_conv_plan *out)
+{
+    if (!out) return MG_ERR_ARG;
+    ConvEpiKind kind;
+    switch (epi) {
+    case MG_CONV_EPI_PLAIN: kind = conv_epi_kind<EpiBiasAct>(); break;
+    case MG_CONV_EPI_REFLECT: kind = ConvEpiKind{1, false, false}; break;
+    case MG_CONV_EPI_PHASES_SLICE: kind = ConvEpiKind{2, false, false}; break;
+    case MG_CONV_EPI_NEEDS_WM2: kind = ConvEpiKind{0, false, true}; break;
+    default: return MG_ERR_ARG;
+    }
+    mg_conv_plan p{};
+    MG_TRY(conv_plan(B, Ci, Lout, rows, K, stride, dil, scratch_floats > 0, scratch_floats, kind, &p));
+    *out = p;
+    return MG_OK;
+}
+
 extern "C" int mg_conv_transpose1d_fwd(const float *in, const float *packed, const float *bias, float *out, int B, int Ci,
                                        int Lin, int Co, int u, float in_slope, float alpha, void *stream)
 {

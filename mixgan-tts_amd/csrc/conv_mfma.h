@@ -482,9 +482,98 @@ struct ConvShape {
 
 
 
+// Which instantiations an epilogue has, as the plan sees it.
+//   EpiMelGAN (above): 1 = reflect padding, 2 = the slice-writing polyphase store -- their own, small case lists;
+//   EpiWide: also the vocoder shapes (K in {7,11,16,4}, dilations up to 5: hifigan/models.py:19-95,112-143), which only
+//       epilogues that opt in instantiate, to keep build time down;
+//   EpiNeedsWM2: the epilogue pairs two 32-row blocks of one wave (the denoiser's gate), so WM = 1 forms compute nothing.
+template <class Epi>
+struct EpiNeedsWM2 { static constexpr bool value = false; };
+template <class Epi>
+struct EpiWide { static constexpr bool value = false; };
+
+struct ConvEpiKind {
+    int melgan;
+    bool wide, needs_wm2;
+};
+template <class Epi>
+static constexpr ConvEpiKind conv_epi_kind() { return ConvEpiKind{EpiMelGAN<Epi>::value, EpiWide<Epi>::value, EpiNeedsWM2<Epi>::value}; }
+
+// The (K, stride, CK, DILMAX) cases, in matching order; CK must match mg_conv_ck().  conv_plan picks from these lists and
+// conv_launch instantiates from them.  BASE: the path's own convolutions, always instantiated.
+#define MG_CONV_CASES_BASE(X) X(1, 1, 32, 1) X(3, 1, 32, 1) X(5, 1, 16, 1) X(9, 1, 16, 1) X(5, 2, 16, 1)
+#define MG_CONV_CASES_WIDE(X) X(3, 1, 32, 5) X(7, 1, 16, 5) X(11, 1, 16, 5) X(16, 1, 16, 1) X(4, 1, 16, 1)
+#define MG_CONV_CASES_REFLECT(X) X(3, 1, 32, 9) X(7, 1, 16, 1)
+#define MG_CONV_CASES_SLICE(X) X(3, 1, 32, 1)
+
+// 256-frame tiles of the one-block form only while the slab fits the register staging (<= 32 elements per thread)
+static constexpr bool conv_big_slab(int kw, int stride, int ck, int dilmax)
+{
+    return ck * (256 * stride + (kw - 1) * dilmax) > 32 * 256;
+}
+
+// The one place the kernel's form is chosen (mg_conv1d_fwd_plan reports it; conv_launch switches on it).
+// Tile choice: the 128x128 workgroup tile unless that leaves most of the 256 CUs idle (short sequences,
+// few output channels: the JCU tail runs at L/4 frames with 128 or 1 output channels) -- then halve the
+// frame tile and/or the channel tile until there are at least 2 workgroups per CU or nothing is left to halve.
+static inline int conv_plan(int B, int Ci, int Lout, int Mrows, int K, int stride, int dil, bool has_scratch,
+                            size_t scratch_floats, ConvEpiKind e, mg_conv_plan *p)
+{
+    if (B <= 0 || Lout <= 0 || Ci <= 0 || Mrows <= 0 || dil < 1) return MG_ERR_SHAPE;
+    bool found = false;
+#define MG_CONV_PICK(KW_, ST_, CK_, DM_)                         \
+    if (!found && K == KW_ && stride == ST_ && dil <= DM_) {     \
+        p->kw = KW_, p->stride = ST_, p->ck = CK_, p->dilmax = DM_; \
+        found = true;                                            \
+    }
+    if (e.melgan == 1) {
+        MG_CONV_CASES_REFLECT(MG_CONV_PICK)
+    } else if (e.melgan == 2) {
+        MG_CONV_CASES_SLICE(MG_CONV_PICK)
+    } else {
+        MG_CONV_CASES_BASE(MG_CONV_PICK)
+        if (e.wide) {
+            MG_CONV_CASES_WIDE(MG_CONV_PICK)
+        }
+    }
+#undef MG_CONV_PICK
+    if (!found) return MG_ERR_SHAPE;
+    const int nchunks = mg_round_up(Ci, p->ck) / p->ck;
+    const bool can_wm1 = !e.needs_wm2;
+    // the packed form of <= 64 rows holds 2 blocks (WM = 1 only); wider ones are padded to 128 rows.  (A pack for a
+    // block-pairing epilogue is padded to 4 blocks whatever its rows.)
+    const bool must_wm1 = Mrows <= 64 && can_wm1;
+    auto wgs = [&](int wm, int nnb) { return (long)mg_cdiv(Mrows, 64 * wm) * mg_cdiv(Lout, 64 * nnb) * B; };
+    int mw = 2, wm = must_wm1 ? 1 : 2, nnb = 2, ksplit = 1;
+    if (Mrows <= 32 && can_wm1) {   // one 32-row block: all 4 waves along the frame axis
+        mw = 1, wm = 1;
+        nnb = !conv_big_slab(p->kw, p->stride, p->ck, p->dilmax) && (long)mg_cdiv(Lout, 256) * B >= 512 ? 2 : 1;
+    } else {
+        // Few tiles, deep reduction, scratch given: keep the large tile (16 MFMAs per k-group and wave instead of 4) and
+        // split the reduction so that about two workgroups land on every CU.
+        if (has_scratch && wgs(wm, nnb) < 256) {
+            ksplit = (int)((384 + wgs(wm, nnb) - 1) / wgs(wm, nnb));
+            if (ksplit > nchunks / 4) ksplit = nchunks / 4;   // >= 4 chunks per split: the pipeline fill is paid per split
+            if (ksplit > 8) ksplit = 8;
+        }
+        if (ksplit >= 2) {
+            ksplit = mg_cdiv(nchunks, mg_cdiv(nchunks, ksplit));   // no empty split
+            const size_t need = (size_t)wgs(wm, nnb) * ksplit * (wm * nnb * 16 * 256);
+            if (ksplit < 2 || need > scratch_floats) ksplit = 1;   // does not fit the scratch: the large tile, unsplit
+        } else {
+            ksplit = 1;
+            if (wgs(wm, nnb) < 512) nnb = 1;
+            if (wgs(wm, nnb) < 512 && wm == 2 && can_wm1) wm = 1;
+        }
+    }
+    p->mw = mw, p->wm = wm, p->nnb = nnb, p->ksplit = ksplit;
+    p->grid = (int)((long)mg_cdiv(Mrows, 32 * mw * wm) * mg_cdiv(Lout, (4 / mw) * 32 * nnb) * B * ksplit);
+    return MG_OK;
+}
+
 template <int KW, int STRIDE, int CK, int DILMAX, int MW, int WM, int NNB, class Epi>
-static int conv_launch_t(const ConvShape &s, const float *in, const float *in_vec, const float *wp,
-                         const typename Epi::Params &ep, hipStream_t st, int ksplit = 1)
+static int conv_launch_t(const ConvShape &s, const mg_conv_plan &pl, const float *in, const float *in_vec, const float *wp,
+                         const typename Epi::Params &ep, hipStream_t st)
 {
     ConvArgs a;
     a.in = in;
@@ -504,20 +593,9 @@ static int conv_launch_t(const ConvShape &s, const float *in, const float *in_ve
     a.ntiles_total = a.ntiles_per_b * s.B;
     const int mtiles = mg_cdiv(s.Mrows, 32 * MW * WM);
     a.mtiles = mtiles;
-    a.ksplit = 1;
-    a.cps = 0;
-    a.part = nullptr;
-    if (ksplit > 1) {
-        const int nchunks = a.CiP / CK;
-        const long tiles = (long)a.ntiles_total * mtiles;
-        a.cps = mg_cdiv(nchunks, ksplit);
-        ksplit = mg_cdiv(nchunks, a.cps);   // no empty split
-        const size_t need = (size_t)tiles * ksplit * (WM * NNB * 16 * 256);
-        if (ksplit > 1 && s.scratch && need <= s.scratch_floats) {
-            a.ksplit = ksplit;
-            a.part = s.scratch;
-        }
-    }
+    a.ksplit = pl.ksplit;
+    a.cps = pl.ksplit > 1 ? mg_cdiv(a.CiP / CK, pl.ksplit) : 0;
+    a.part = pl.ksplit > 1 ? s.scratch : nullptr;
     dim3 grid((unsigned)(a.ntiles_total * mtiles * a.ksplit));
     hipLaunchKernelGGL((conv_mfma_kernel<KW, STRIDE, CK, DILMAX, MW, WM, NNB, Epi>), grid, dim3(256), 0, st, a, ep);
     MG_LAUNCH_CHECK();
@@ -529,81 +607,43 @@ static int conv_launch_t(const ConvShape &s, const float *in, const float *in_ve
     return MG_OK;
 }
 
-// Tile choice: the 128x128 workgroup tile unless that leaves most of the 256 CUs idle (short sequences,
-// few output channels: the JCU tail runs at L/4 frames with 128 or 1 output channels) -- then halve the
-// frame tile and/or the channel tile until there are at least 2 workgroups per CU or nothing is left to halve.
-template <class Epi>
-struct EpiNeedsWM2 { static constexpr bool value = false; };
-
+// The planned (MW, WM, NNB) form of one (K, stride, DILMAX) case.
 template <int KW, int STRIDE, int CK, int DILMAX, class Epi>
-static int conv_launch_k(const ConvShape &s, const float *in, const float *in_vec, const float *wp,
+static int conv_launch_k(const ConvShape &s, const mg_conv_plan &pl, const float *in, const float *in_vec, const float *wp,
                          const typename Epi::Params &ep, hipStream_t st)
 {
-    const bool can_wm1 = !EpiNeedsWM2<Epi>::value;
-    // the packed form of <= 64 rows holds 2 blocks (WM = 1 only); wider ones are padded to 128 rows
-    const bool must_wm1 = s.Mrows <= 64;
-    auto wgs = [&](int wm, int nnb) { return (long)mg_cdiv(s.Mrows, 64 * wm) * mg_cdiv(s.Lout, 64 * nnb) * s.B; };
-    if (s.Mrows <= 32 && can_wm1) {   // one 32-row block: all 4 waves along the frame axis
-        // 256-frame tiles unless the slab would not fit the register staging (> 32 elements per thread)
-        constexpr bool big_slab = CK * (256 * STRIDE + (KW - 1) * DILMAX) > 32 * 256;
-        if constexpr (!big_slab) {
-            if ((long)mg_cdiv(s.Lout, 256) * s.B >= 512)
-                return conv_launch_t<KW, STRIDE, CK, DILMAX, 1, 1, 2, Epi>(s, in, in_vec, wp, ep, st);
-        }
-        return conv_launch_t<KW, STRIDE, CK, DILMAX, 1, 1, 1, Epi>(s, in, in_vec, wp, ep, st);
+#define MG_CONV_FORM(MW_, WM_, NNB_) \
+    if (pl.mw == MW_ && pl.wm == WM_ && pl.nnb == NNB_) \
+        return conv_launch_t<KW, STRIDE, CK, DILMAX, MW_, WM_, NNB_, Epi>(s, pl, in, in_vec, wp, ep, st);
+    if constexpr (!conv_big_slab(KW, STRIDE, CK, DILMAX)) {
+        MG_CONV_FORM(1, 1, 2)
     }
-    int wm = must_wm1 ? 1 : 2, nnb = 2;
-    // Few tiles, deep reduction, scratch given: keep the large tile (16 MFMAs per k-group and wave instead of 4) and
-    // split the reduction so that about two workgroups land on every CU; each split keeps >= 2 chunks.
-    if (s.scratch && wgs(wm, nnb) < 256) {
-        const int nchunks = mg_round_up(s.Ci, CK) / CK;
-        int ksplit = (int)((384 + wgs(wm, nnb) - 1) / wgs(wm, nnb));
-        if (ksplit > nchunks / 4) ksplit = nchunks / 4;   // >= 4 chunks per split: the pipeline fill is paid per split
-        if (ksplit > 8) ksplit = 8;
-        if (ksplit >= 2) {
-            if (wm == 2) return conv_launch_t<KW, STRIDE, CK, DILMAX, 2, 2, 2, Epi>(s, in, in_vec, wp, ep, st, ksplit);
-            return conv_launch_t<KW, STRIDE, CK, DILMAX, 2, 1, 2, Epi>(s, in, in_vec, wp, ep, st, ksplit);
-        }
-    }
-    if (wgs(wm, nnb) < 512) nnb = 1;
-    if (wgs(wm, nnb) < 512 && wm == 2 && can_wm1) wm = 1;
-    if (wm == 2)
-        return nnb == 2 ? conv_launch_t<KW, STRIDE, CK, DILMAX, 2, 2, 2, Epi>(s, in, in_vec, wp, ep, st)
-                        : conv_launch_t<KW, STRIDE, CK, DILMAX, 2, 2, 1, Epi>(s, in, in_vec, wp, ep, st);
-    return nnb == 2 ? conv_launch_t<KW, STRIDE, CK, DILMAX, 2, 1, 2, Epi>(s, in, in_vec, wp, ep, st)
-                    : conv_launch_t<KW, STRIDE, CK, DILMAX, 2, 1, 1, Epi>(s, in, in_vec, wp, ep, st);
+    MG_CONV_FORM(1, 1, 1)
+    MG_CONV_FORM(2, 1, 1)
+    MG_CONV_FORM(2, 1, 2)
+    MG_CONV_FORM(2, 2, 1)
+    MG_CONV_FORM(2, 2, 2)
+#undef MG_CONV_FORM
+    return MG_ERR_SHAPE;
 }
-
-// Dispatch on (K, stride, dilation); CK must match mg_conv_ck().  The path's own convolutions (K in
-// {1,3,5,9}, dilation 1) are always instantiated; the vocoder shapes (K in {7,11,16,4}, dilations up to 5:
-// hifigan/models.py:19-95,112-143) only for epilogues that opt in (EpiWide), to keep build time down.
-template <class Epi>
-struct EpiWide { static constexpr bool value = false; };
 
 template <class Epi>
 static int conv_launch(const ConvShape &s, const float *in, const float *in_vec, const float *wp,
                        const typename Epi::Params &ep, hipStream_t st)
 {
-    if (s.B <= 0 || s.Lout <= 0 || s.Ci <= 0 || s.Mrows <= 0 || s.dil < 1) return MG_ERR_SHAPE;
+    mg_conv_plan pl;
+    MG_TRY(conv_plan(s.B, s.Ci, s.Lout, s.Mrows, s.K, s.stride, s.dil, s.scratch != nullptr, s.scratch_floats,
+                     conv_epi_kind<Epi>(), &pl));
 #define MG_CONV_CASE(KW_, ST_, CK_, DM_) \
-    if (s.K == KW_ && s.stride == ST_ && s.dil <= DM_) return conv_launch_k<KW_, ST_, CK_, DM_, Epi>(s, in, in_vec, wp, ep, st);
+    if (pl.kw == KW_ && pl.stride == ST_ && pl.dilmax == DM_) return conv_launch_k<KW_, ST_, CK_, DM_, Epi>(s, pl, in, in_vec, wp, ep, st);
     if constexpr (EpiMelGAN<Epi>::value == 1) {
-        MG_CONV_CASE(3, 1, 32, 9)
-        MG_CONV_CASE(7, 1, 16, 1)
+        MG_CONV_CASES_REFLECT(MG_CONV_CASE)
     } else if constexpr (EpiMelGAN<Epi>::value == 2) {
-        MG_CONV_CASE(3, 1, 32, 1)
+        MG_CONV_CASES_SLICE(MG_CONV_CASE)
     } else {
-        MG_CONV_CASE(1, 1, 32, 1)
-        MG_CONV_CASE(3, 1, 32, 1)
-        MG_CONV_CASE(5, 1, 16, 1)
-        MG_CONV_CASE(9, 1, 16, 1)
-        MG_CONV_CASE(5, 2, 16, 1)
+        MG_CONV_CASES_BASE(MG_CONV_CASE)
         if constexpr (EpiWide<Epi>::value) {
-            MG_CONV_CASE(3, 1, 32, 5)
-            MG_CONV_CASE(7, 1, 16, 5)
-            MG_CONV_CASE(11, 1, 16, 5)
-            MG_CONV_CASE(16, 1, 16, 1)
-            MG_CONV_CASE(4, 1, 16, 1)
+            MG_CONV_CASES_WIDE(MG_CONV_CASE)
         }
     }
 #undef MG_CONV_CASE
