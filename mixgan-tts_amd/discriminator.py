@@ -73,6 +73,10 @@ class JCUDiscriminator(nn.Module):
         # replays each backward on the stream its forward ran on, so the two backward chains overlap as well.
         overlap = (self.branch_overlap and os.environ.get("MG_JCU_OVERLAP", "1") != "0" and x.is_cuda
                    and not torch.cuda.is_current_stream_capturing())
+        # The unconditional tail is recorded first on BOTH paths: autograd runs the later-recorded nodes first and adds
+        # the gradients that meet at x in the order they arrive.  Recorded cond-first, the one-stream path would sum
+        # (.. + d_uncond) + d_cond where the two-stream path sums (.. + d_cond) + d_uncond: fp32 addition is not
+        # associative, so every gradient below x could differ in its last bits between the two paths.
         if overlap:
             main = torch.cuda.current_stream(dev)
             if self._side is None or self._side.device != dev:
@@ -85,15 +89,15 @@ class JCUDiscriminator(nn.Module):
                     x_uncond = self._lrelu_conv(layer, x_uncond)
                     x_uncond.record_stream(main)          # consumed (losses, backward) on the main stream
                     uncond_feats.append(x_uncond)
+        else:
+            for layer in self.uncond_conv_block:
+                x_uncond = self._lrelu_conv(layer, x_uncond)
+                uncond_feats.append(x_uncond)
         for i, layer in enumerate(self.cond_conv_block):
             x_cond = self._lrelu_conv(layer, x_cond, step if i == 0 else None)    # (x + step[:, :, None]) fused
             cond_feats.append(x_cond)
         if overlap:
             main.wait_stream(side)
-        else:
-            for layer in self.uncond_conv_block:
-                x_uncond = self._lrelu_conv(layer, x_uncond)
-                uncond_feats.append(x_uncond)
         return cond_feats, uncond_feats
 
     branch_overlap = True     # False: both tails on the caller's stream, one after the other

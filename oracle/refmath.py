@@ -4,7 +4,8 @@ Every function takes `W`, a `{reference state_dict key: tensor}` mapping (option
 key prefix `p`), so the checkpoint key names of SURVEY.md section 5 are spelled out where
 they are used.  Autograd works through all of it (used for the gradient fixtures).
 
-Test infrastructure (see oracle/__init__.py); fp32 throughout like the reference.
+Test infrastructure (see oracle/__init__.py); fp32 like the reference, unless the weights handed in are float64 (the
+denoiser and the JCU discriminator follow the dtype of their weights).
 """
 import math
 
@@ -238,15 +239,41 @@ JCU_KERNELS = (3, 5, 5, 5, 3)
 JCU_STRIDES = (1, 2, 2, 1, 1)
 
 
-def jcu_forward(W, x_ts, x_t_prevs, s, t, kernels=JCU_KERNELS, strides=JCU_STRIDES, n_layer=3):
-    """model/mixgantts.py:256-288.  Returns (cond_feats[5], uncond_feats[5])."""
+def _jcu_act(pre, mask):
+    """leaky_relu(pre, 0.2), or with the sign pattern given: pre * where(mask, 1, 0.2)."""
+    if mask is None:
+        return F.leaky_relu(pre, 0.2)
+    one = torch.ones((), dtype=pre.dtype, device=pre.device)
+    return pre * torch.where(mask, one, 0.2 * one)
+
+
+def jcu_forward(W, x_ts, x_t_prevs, s, t, kernels=JCU_KERNELS, strides=JCU_STRIDES, n_layer=3, masks=None, taps=None):
+    """model/mixgantts.py:256-288.  Returns (cond_feats[5], uncond_feats[5]).
+
+    Runs in the dtype of its weights (the step embedding keeps its fp32-rounded values, widened).
+    `masks`: (cond list, uncond list) of one bool tensor per returned map; where given, layer i multiplies its
+    pre-activation by where(mask, 1, 0.2) instead of applying leaky_relu -- the sign pattern of another run of the same
+    network, so that an element which two precisions put on different sides of zero does not change the gradient
+    through it by a factor of 5.  The first n_layer maps are shared by both lists; their mask is taken from the cond list.
+    `taps`: a dict that receives every pre-activation ("cond%d" / "uncond%d", detached; the shared ones under both)."""
+    w0 = W["mlp.0.linear.weight"]
+    mc, mu = (None, None) if masks is None else masks
+    m = lambda lst, i: None if lst is None else lst[i]
+
+    def tap(names, pre):
+        if taps is not None:
+            for n in names:
+                taps[n] = pre.detach()
+
     x = _lin(W, "input_projection", torch.cat([x_t_prevs, x_ts], dim=-1)).transpose(1, 2)
-    e = step_embedding(t, W["mlp.0.linear.weight"].shape[1])
+    e = step_embedding(t, w0.shape[1], w0.dtype)
     e = _lin(W, "mlp.2", mish(_lin(W, "mlp.0", e))).unsqueeze(-1)
     cond_feats, uncond_feats = [], []
     for i in range(n_layer):
         k = kernels[i]
-        x = F.leaky_relu(_conv(W, "conv_block.%d" % i, x, strides[i], (k - 1) // 2), 0.2)
+        pre = _conv(W, "conv_block.%d" % i, x, strides[i], (k - 1) // 2)
+        tap(("cond%d" % i, "uncond%d" % i), pre)
+        x = _jcu_act(pre, m(mc, i))
         cond_feats.append(x)
         uncond_feats.append(x)
     xc = x + e
@@ -257,12 +284,16 @@ def jcu_forward(W, x_ts, x_t_prevs, s, t, kernels=JCU_KERNELS, strides=JCU_STRID
     for j in range(n_tail):
         k = kernels[n_layer + j]
         st = strides[n_layer + j]
-        xc = F.leaky_relu(_conv(W, "cond_conv_block.%d" % j, xc, st, (k - 1) // 2), 0.2)
+        pre = _conv(W, "cond_conv_block.%d" % j, xc, st, (k - 1) // 2)
+        tap(("cond%d" % (n_layer + j),), pre)
+        xc = _jcu_act(pre, m(mc, n_layer + j))
         cond_feats.append(xc)
     for j in range(n_tail):
         k = kernels[n_layer + j]
         st = strides[n_layer + j]
-        xu = F.leaky_relu(_conv(W, "uncond_conv_block.%d" % j, xu, st, (k - 1) // 2), 0.2)
+        pre = _conv(W, "uncond_conv_block.%d" % j, xu, st, (k - 1) // 2)
+        tap(("uncond%d" % (n_layer + j),), pre)
+        xu = _jcu_act(pre, m(mu, n_layer + j))
         uncond_feats.append(xu)
     return cond_feats, uncond_feats
 

@@ -97,6 +97,33 @@ def condition_relu_kinks(W64, x, t, cond, spk, go, band, gen, chunk=4):
     return redrawn, len(frames)
 
 
+def jcu_oracle_grads(W, x_ts, x_t_prevs, s, t, cot, dtype, masks=None):
+    """The ten maps of refmath.jcu_forward in `dtype` and every gradient of sum_i <cond_i, cot[0][i]> + <uncond_i, cot[1][i]>
+    by torch.autograd (the three shared maps appear in both lists and get both cotangents).  `W`: leaves of `dtype` that
+    require grad; `masks`: see jcu_forward.  Keys: "cond%d" / "uncond%d", "pre/..." (the pre-activations), "d_x_ts",
+    "d_x_t_prevs", "d_s" (multi-speaker), "param/<state_dict key>"."""
+    for w in W.values():
+        w.grad = None
+    leaf = lambda v: v.detach().to(dtype, copy=True).requires_grad_()     # never the caller's tensor
+    a, b = leaf(x_ts), leaf(x_t_prevs)
+    ss = None if s is None else leaf(s)
+    taps = {}
+    c, u = refmath.jcu_forward(W, a, b, ss, t, masks=masks, taps=taps)
+    loss = sum((m * g.to(dtype)).sum() for m, g in zip(c, cot[0])) + sum((m * g.to(dtype)).sum() for m, g in zip(u, cot[1]))
+    loss.backward()
+    ref = {"d_x_ts": a.grad, "d_x_t_prevs": b.grad}
+    if ss is not None:
+        ref["d_s"] = ss.grad
+    for i in range(len(c)):
+        ref["cond%d" % i], ref["uncond%d" % i] = c[i].detach(), u[i].detach()
+    for k, v in taps.items():
+        ref["pre/" + k] = v
+    for k, w in W.items():
+        ref["param/" + k] = w.grad
+        w.grad = None
+    return ref
+
+
 def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
