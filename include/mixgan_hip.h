@@ -582,12 +582,23 @@ typedef struct MgLossTerm {
 size_t mg_multi_loss_scratch_floats(void);
 int mg_multi_loss_fwd(const MgLossTerm *terms, int nterms, float *scratch, float *out, void *stream);
 int mg_multi_loss_bwd(const MgLossTerm *terms, int nterms, const float *g, void *stream);
+/* The same two launches with den[k] (host array, one entry per term) in place of n_k as the divisor -- in the per-term
+ * "means" of out and in da_k = g[0] * weight_k / den_k * {...}; n_k stays the number of elements the term reads.  A
+ * rank of a sharded batch passes the denominators of the WHOLE batch, so the ranks' totals add up to the single-process
+ * loss.  MG_ERR_ARG for a NULL den or den[k] <= 0.  den[k] == n_k returns the bits of mg_multi_loss_fwd / _bwd. */
+int mg_multi_loss_fwd_den(const MgLossTerm *terms, int nterms, const double *den, float *scratch, float *out,
+                          void *stream);
+int mg_multi_loss_bwd_den(const MgLossTerm *terms, int nterms, const double *den, const float *g, void *stream);
 /* Masked mel L1 (loss.py:229-242,255-259) over rows = B*L frames of M bins, pad uint8 [rows] (1 = pad):
  * out2 = {sum |p-t| over counted rows, M * #counted rows}; the loss is out2[0]/out2[1]. */
 int mg_mel_l1_fwd(const float *pred, const float *targ, const uint8_t *pad, int rows, int M, float *out2,
                   void *stream);
 int mg_mel_l1_bwd(const float *pred, const float *targ, const uint8_t *pad, int rows, int M,
                   const float *g, const float *den, float *dpred, void *stream);
+/* out[0] (device int64) = the number of rows mg_mel_l1_fwd counts: unpadded and with a non-zero entry in targ.  An
+ * integer, so a SUM all-reduce of it over ranks is exact.  MG_ERR_ARG for a NULL targ / out (pad may be NULL),
+ * MG_ERR_SHAPE for rows <= 0 or M <= 0. */
+int mg_mel_count_rows(const float *targ, const uint8_t *pad, int rows, int M, int64_t *out, void *stream);
 
 /* ------------------------------------------------------------------ FFT blocks (shallow / aux coarse mel)
  * Multi-head self-attention of transformer/SubLayers.py:29-57 + Modules.py:16-23 without the

@@ -150,6 +150,8 @@ def _signatures():
         "mg_multi_loss_scratch_floats": (sz, []),
         "mg_multi_loss_fwd": (i, [vp, i, vp, vp, vp]),
         "mg_multi_loss_bwd": (i, [vp, i, vp, vp]),
+        "mg_multi_loss_fwd_den": (i, [vp, i, vp, vp, vp, vp]),
+        "mg_multi_loss_bwd_den": (i, [vp, i, vp, vp, vp]),
         "mg_grad_norm_scratch_floats": (sz, []),
         "mg_grad_norm": (i, [vp, sz, f, vp, vp, vp]),
         "mg_adam_flat": (i, [vp, vp, vp, vp, sz, f, f, f, f, f, lg, vp, vp]),
@@ -157,6 +159,7 @@ def _signatures():
         "mg_loss_grad": (i, [vp, vp, f, i, vp, f, sz, vp, vp]),
         "mg_mel_l1_fwd": (i, [vp, vp, vp, i, i, vp, vp]),
         "mg_mel_l1_bwd": (i, [vp, vp, vp, i, i, vp, vp, vp, vp]),
+        "mg_mel_count_rows": (i, [vp, vp, i, i, vp, vp]),
         "mg_attention_fwd": (i, [vp, vp, vp, i, i, i, i, f, vp]),
         "mg_attention_fwd_f16": (i, [vp, vp, vp, i, i, i, i, f, vp]),
         "mg_layernorm_cm_fwd": (i, [vp, vp, vp, vp, vp, vp, i, i, i, f, vp]),

@@ -142,6 +142,46 @@ extern "C" int mg_mel_l1_bwd(const float *pred, const float *targ, const uint8_t
     return MG_OK;
 }
 
+// The number of rows mel_l1_kernel counts (unpadded, non-zero target), as an integer: ranks of a sharded batch
+// all-reduce it exactly and divide by the global count (16 ranks x 16 x 4000 x 80 is past 2^24, so the count
+// travels as int64 and becomes fp32 once).  Same row predicate, same wave-per-row sweep as mel_l1_kernel; integer
+// adds commute, so the result does not depend on scheduling.
+__global__ __launch_bounds__(256) void mel_count_rows_kernel(const float *__restrict__ targ, const uint8_t *__restrict__ pad,
+                                                             int rows, int M, unsigned long long *__restrict__ out)
+{
+    __shared__ int red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int acc = 0;
+    for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+        const bool padded = pad && pad[row];
+        const float *t = targ + (size_t)row * M;
+        float tabs = 0.f;
+        for (int m = lane; m < M; m += 64) tabs += fabsf(padded ? 0.f : t[m]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) tabs += __shfl_xor(tabs, o, 64);
+        acc += tabs != 0.f ? 1 : 0;
+    }
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int s = red[0] + red[1] + red[2] + red[3];
+        if (s) atomicAdd(out, (unsigned long long)s);
+    }
+}
+
+extern "C" int mg_mel_count_rows(const float *targ, const uint8_t *pad, int rows, int M, int64_t *out, void *stream)
+{
+    if (!targ || !out) return MG_ERR_ARG;
+    if (rows <= 0 || M <= 0) return MG_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(int64_t), st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mel_count_rows_kernel, dim3(min(mg_cdiv(rows, 4), 512)), dim3(256), 0, st, targ, pad, rows, M,
+                       reinterpret_cast<unsigned long long *>(out));
+    MG_LAUNCH_CHECK();
+    return MG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Weighted sum of up to MG_LOSS_MAX_TERMS mean-reduced terms in ONE launch (and ONE for its gradient).
 // The adversarial + feature-matching part of the generator loss is ten such terms (model/loss.py:12-30,221-227);
@@ -151,6 +191,7 @@ extern "C" int mg_mel_l1_bwd(const float *pred, const float *targ, const uint8_t
 // ---------------------------------------------------------------------------------------------
 struct MultiLossArgs {
     MgLossTerm t[MG_LOSS_MAX_TERMS];
+    float div[MG_LOSS_MAX_TERMS];   // each term's divisor: (float)n, or the caller's denominator (the _den entry points)
     int first_block[MG_LOSS_MAX_TERMS + 1];
     int nterms;
     float *partial;      // [total blocks]
@@ -195,7 +236,7 @@ __global__ __launch_bounds__(256) void multi_loss_fwd_kernel(MultiLossArgs a)
             float sj = 0.f;
             for (int b = a.first_block[j]; b < a.first_block[j + 1]; ++b)
                 sj += __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float mean = a.t[j].n ? sj / (float)a.t[j].n : 0.f;
+            const float mean = a.t[j].n ? sj / a.div[j] : 0.f;
             a.out[1 + MG_LOSS_GROUPS + j] = mean;
             total = a.t[j].weight * mean;
         }
@@ -225,16 +266,21 @@ __global__ __launch_bounds__(256) void multi_loss_bwd_kernel(MultiLossArgs a)
     const MgLossTerm t = a.t[k];
     if (!t.da) return;
     const int nb = a.first_block[k + 1] - a.first_block[k], lb = blockIdx.x - a.first_block[k];
-    const float kk = a.g[0] * t.weight / (float)t.n;
+    const float kk = a.g[0] * t.weight / a.div[k];
     for (size_t i = (size_t)lb * 256 + threadIdx.x; i < t.n; i += (size_t)nb * 256) {
         const float d = t.mode == 0 ? t.a[i] - t.c : t.a[i] - t.b[i];
         t.da[i] = t.mode == 0 ? 2.f * kk * d : (d > 0.f ? kk : (d < 0.f ? -kk : 0.f));
     }
 }
 
-static int multi_loss_fill(MultiLossArgs &a, const MgLossTerm *terms, int nterms, int max_blocks_per_term)
+// den: NULL = every term divides by its own n (a mean); else one positive divisor per term
+static int multi_loss_fill(MultiLossArgs &a, const MgLossTerm *terms, int nterms, int max_blocks_per_term,
+                           const double *den = nullptr)
 {
     if (!terms || nterms < 1 || nterms > MG_LOSS_MAX_TERMS) return MG_ERR_ARG;
+    if (den)
+        for (int k = 0; k < nterms; ++k)
+            if (!(den[k] > 0.0)) return MG_ERR_ARG;
     int at = 0;
     for (int k = 0; k < nterms; ++k) {
         const MgLossTerm &t = terms[k];
@@ -242,6 +288,7 @@ static int multi_loss_fill(MultiLossArgs &a, const MgLossTerm *terms, int nterms
             return MG_ERR_ARG;
         if (t.n == 0) return MG_ERR_SHAPE;
         a.t[k] = t;
+        a.div[k] = den ? (float)den[k] : (float)t.n;
         a.first_block[k] = at;
         const size_t want = (t.n + 2047) / 2048;   // ~8 elements per thread
         at += (int)(want < 1 ? 1 : (want > (size_t)max_blocks_per_term ? (size_t)max_blocks_per_term : want));
@@ -253,11 +300,12 @@ static int multi_loss_fill(MultiLossArgs &a, const MgLossTerm *terms, int nterms
 
 extern "C" size_t mg_multi_loss_scratch_floats(void) { return (size_t)MG_LOSS_MAX_TERMS * 64 + 1; }
 
-extern "C" int mg_multi_loss_fwd(const MgLossTerm *terms, int nterms, float *scratch, float *out, void *stream)
+static int multi_loss_fwd(const MgLossTerm *terms, int nterms, const double *den, float *scratch, float *out,
+                          void *stream)
 {
     if (!scratch || !out) return MG_ERR_ARG;
     MultiLossArgs a;
-    MG_TRY(multi_loss_fill(a, terms, nterms, 64));
+    MG_TRY(multi_loss_fill(a, terms, nterms, 64, den));
     a.partial = scratch;
     a.ticket = reinterpret_cast<unsigned *>(scratch + (size_t)MG_LOSS_MAX_TERMS * 64);
     a.out = out;
@@ -267,11 +315,11 @@ extern "C" int mg_multi_loss_fwd(const MgLossTerm *terms, int nterms, float *scr
     return MG_OK;
 }
 
-extern "C" int mg_multi_loss_bwd(const MgLossTerm *terms, int nterms, const float *g, void *stream)
+static int multi_loss_bwd(const MgLossTerm *terms, int nterms, const double *den, const float *g, void *stream)
 {
     if (!g) return MG_ERR_ARG;
     MultiLossArgs a;
-    MG_TRY(multi_loss_fill(a, terms, nterms, 256));
+    MG_TRY(multi_loss_fill(a, terms, nterms, 256, den));
     a.partial = nullptr;
     a.ticket = nullptr;
     a.out = nullptr;
@@ -279,4 +327,29 @@ extern "C" int mg_multi_loss_bwd(const MgLossTerm *terms, int nterms, const floa
     hipLaunchKernelGGL(multi_loss_bwd_kernel, dim3(a.first_block[nterms]), dim3(256), 0, (hipStream_t)stream, a);
     MG_LAUNCH_CHECK();
     return MG_OK;
+}
+
+extern "C" int mg_multi_loss_fwd(const MgLossTerm *terms, int nterms, float *scratch, float *out, void *stream)
+{
+    return multi_loss_fwd(terms, nterms, nullptr, scratch, out, stream);
+}
+
+extern "C" int mg_multi_loss_bwd(const MgLossTerm *terms, int nterms, const float *g, void *stream)
+{
+    return multi_loss_bwd(terms, nterms, nullptr, g, stream);
+}
+
+// ... with den[k] in place of n_k as the divisor (n_k stays the element count): the numerators of one rank's shard
+// over the denominators of the whole batch.  den[k] == n_k gives the bits of the entry points above.
+extern "C" int mg_multi_loss_fwd_den(const MgLossTerm *terms, int nterms, const double *den, float *scratch, float *out,
+                                     void *stream)
+{
+    if (!den) return MG_ERR_ARG;
+    return multi_loss_fwd(terms, nterms, den, scratch, out, stream);
+}
+
+extern "C" int mg_multi_loss_bwd_den(const MgLossTerm *terms, int nterms, const double *den, const float *g, void *stream)
+{
+    if (!den) return MG_ERR_ARG;
+    return multi_loss_bwd(terms, nterms, den, g, stream);
 }

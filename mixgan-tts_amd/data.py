@@ -16,6 +16,9 @@ the GPU, designed for one process per GPU:
   `attn_prior` file (the folder need not exist), collation leaves slot 10 as None, and `to_device` /
   `PrefetchLoader` fill it on the device from the two length vectors (corpusops.attn_prior, csrc/corpus.hip) on the
   stream they copy on.  Same slot dtype and shape: float32 [B, T, L].
+* `pad_batch_to` / `PrefetchLoader(shape_group=...)` -- for HotPathTrainer(exact_shards=True): every rank's batch
+  padded to the longest rank's mel length, with the whole batch's `BatchShape` attached, agreed over a process
+  group of the loader's own while the previous step trains.
 * `PrefetchLoader` -- a background thread does the `np.load`s + collation of the next groups while the
   GPU works on the current one, stages every array of a batch in pinned host memory and issues the
   host->device copies on its own HIP stream; the consumer only waits on an event.  It yields what
@@ -264,6 +267,41 @@ def fill_device_prior(slots, prior_scaling):
                                              int(slots[MAX_MEL_SLOT]), prior_scaling, torch.float32)
 
 
+# slot -> its mel-frame axis (the alignment prior [B, T, L] and the mel [B, L, M])
+_MEL_AXIS = {PRIOR_SLOT: 2, 11: 1}
+
+
+def _pad_axis(x, axis, length):
+    if x is None or x.shape[axis] == length:
+        return x
+    if x.shape[axis] > length:
+        raise ValueError("pad_batch_to: slot has %d mel frames, more than %d" % (x.shape[axis], length))
+    shape = list(x.shape)
+    shape[axis] = length - x.shape[axis]
+    if torch.is_tensor(x):
+        return torch.cat([x, x.new_zeros(shape)], axis)
+    return np.concatenate([x, np.zeros(shape, dtype=x.dtype)], axis)
+
+
+def pad_batch_to(batch, max_mel_len, in_place=False):
+    """A 17-slot batch (numpy or tensors) with every slot that has a mel-frame axis -- the mels and the alignment
+    priors -- zero-padded to max_mel_len frames and slot 13 (max_mel_len) set to it; the lengths stay untouched, so
+    masks made from them mark the new frames as padding.  What a rank of HotPathTrainer(exact_shards=True) runs on
+    when another rank's batch is longer.  Returns a list (the batch itself with in_place=True, which needs a list)."""
+    if len(batch) != 17:
+        raise ValueError("pad_batch_to: expected a 17-slot batch, got %d slots" % len(batch))
+    out = batch if in_place else list(batch)
+    for slot, axis in _MEL_AXIS.items():
+        out[slot] = _pad_axis(out[slot], axis, int(max_mel_len))
+    out[MAX_MEL_SLOT] = int(max_mel_len)
+    return out
+
+
+class StagedBatch(list):
+    """A 17-slot device batch with the whole batch's `shape` (distributed.BatchShape) attached."""
+    shape = None
+
+
 def to_device(data, device, pin=False, non_blocking=False, prior_scaling=None):
     """utils/tools.py:33-110: numpy batch tuple (17 or 10 slots) -> list / tuple with device tensors.  A 17-slot batch
     of Dataset(attn_prior="device") has slot 10 empty: it is computed on `device` (a GPU) with `prior_scaling`."""
@@ -334,13 +372,22 @@ class PrefetchLoader:
     workers -- threads doing np.load + collate.  One is the measured optimum with a warm page cache (a second
                Python thread mostly fights the training thread for the GIL: tests/perf_configs.py data); raise
                it only when the files come from slow storage.
+    shape_group -- a process group (gloo, made with dist.new_group and used by nothing else, so that its collectives
+               cannot interleave with the trainer's): the worker exchanges (items, max mel length) of all sub-batches
+               of a group over it in one collective before packing, pads the mel-frame slots to the longest rank's
+               length while it packs (no extra launch), and yields StagedBatch lists whose `.shape` is the whole
+               batch's BatchShape -- what HotPathTrainer(exact_shards=True) takes as shape=.  Needs workers == 1
+               (two threads' collectives on one group could pair up differently on different ranks).
     """
 
     _DONE = object()
 
-    def __init__(self, dataset, sampler, device, depth=2, workers=1):
+    def __init__(self, dataset, sampler, device, depth=2, workers=1, shape_group=None):
         self.ds, self.sampler, self.device = dataset, sampler, torch.device(device)
         self.depth, self.workers = max(1, depth), max(1, workers)
+        if shape_group is not None and self.workers != 1:
+            raise ValueError("PrefetchLoader(shape_group=...) needs workers == 1")
+        self.shape_group = shape_group
         self.cuda = self.device.type == "cuda"
         # pinned staging (2 per worker) and copy streams live as long as the loader: pinning host memory costs
         # tens of milliseconds per buffer, far more than loading a group
@@ -352,33 +399,57 @@ class PrefetchLoader:
 
     def _stage(self, idxs, stream, arena):
         batchs = self.ds.collate_fn([self.ds[i] for i in idxs])
+        shapes = [None] * len(batchs)
+        if self.shape_group is not None:
+            from .distributed import exchange_batch_shapes
+            if any(len(b) != 17 for b in batchs):
+                raise ValueError("PrefetchLoader(shape_group=...) stages 17-slot training batches")
+            shapes = exchange_batch_shapes([(len(b[MEL_LENS_SLOT]), int(b[MAX_MEL_SLOT])) for b in batchs],
+                                           self.shape_group)
+            # the padded length travels in slot 13; the arrays themselves are padded while they are packed below
+            batchs = [list(b[:MAX_MEL_SLOT]) + [int(sh.max_len)] + list(b[MAX_MEL_SLOT + 1:])
+                      for b, sh in zip(batchs, shapes)]
         if not self.cuda:
-            return [to_device(b, self.device, prior_scaling=getattr(self.ds, "prior_scaling", None))
-                    for b in batchs], None
+            out = []
+            for b, sh in zip(batchs, shapes):
+                if sh is not None:
+                    b = pad_batch_to(b, sh.max_len)
+                d = to_device(b, self.device, prior_scaling=getattr(self.ds, "prior_scaling", None))
+                if sh is not None:
+                    d = StagedBatch(d)
+                    d.shape = sh
+                out.append(d)
+            return out, None
         # One pinned staging buffer and ONE host->device copy per group: every array of every sub-batch is
         # converted to its final dtype while it is packed (256-byte aligned) into the arena; the device
         # tensors are views into a single device buffer.  (A pin_memory() per tensor costs a hipHostMalloc
         # each -- slower than the synchronous loop it is meant to beat.)
         plan, total = [], 0
-        for b in batchs:
+        for b, sh in zip(batchs, shapes):
             kinds = _SLOTS17 if len(b) == 17 else _SLOTS10
             row = []
-            for x, kind in zip(b, kinds):
+            for slot, (x, kind) in enumerate(zip(b, kinds)):
                 if kind == "py" or x is None:
                     row.append(None)
                     continue
                 x = np.asarray(x)
                 dt = x.dtype if kind is None else _NP_OF[kind]
-                row.append((total, x, np.dtype(dt)))
-                total += (x.size * np.dtype(dt).itemsize + 255) // 256 * 256
+                shape = list(x.shape)
+                if sh is not None and slot in _MEL_AXIS:
+                    shape[_MEL_AXIS[slot]] = sh.max_len
+                row.append((total, x, np.dtype(dt), tuple(shape)))
+                total += (int(np.prod(shape)) * np.dtype(dt).itemsize + 255) // 256 * 256
             plan.append(row)
         host = arena.get(max(total, 256))
         hview = host.numpy()
         for row in plan:
             for ent in row:
                 if ent is not None:
-                    off, x, dt = ent
-                    dst = hview[off:off + x.size * dt.itemsize].view(dt).reshape(x.shape)
+                    off, x, dt, shape = ent
+                    dst = hview[off:off + int(np.prod(shape)) * dt.itemsize].view(dt).reshape(shape)
+                    if shape != x.shape:      # padded to the longest rank's length: zeros past this rank's frames
+                        dst[...] = 0
+                        dst = dst[tuple(slice(0, n) for n in x.shape)]
                     np.copyto(dst, x, casting="unsafe")
         with torch.cuda.stream(stream):
             dev = torch.empty(max(total, 256), dtype=torch.uint8, device=self.device)
@@ -387,15 +458,18 @@ class PrefetchLoader:
             ev.record(stream)
         arena.mark(ev)
         out = []
-        for b, row in zip(batchs, plan):
+        for b, row, sh in zip(batchs, plan, shapes):
             slots = []
             for x, ent in zip(b, row):
                 if ent is None:
                     slots.append(x)
                 else:
-                    off, a, dt = ent
-                    t = dev[off:off + a.size * dt.itemsize].view(_TORCH_OF[dt.str]).view(a.shape)
+                    off, a, dt, shape = ent
+                    t = dev[off:off + int(np.prod(shape)) * dt.itemsize].view(_TORCH_OF[dt.str]).view(shape)
                     slots.append(t)
+            if sh is not None:
+                slots = StagedBatch(slots)
+                slots.shape = sh
             out.append(slots if len(b) == 17 else tuple(slots))
         if any(len(b) == 17 and b[PRIOR_SLOT] is None for b in batchs):
             # Dataset(attn_prior="device"): the priors follow the copy on its stream; the consumer waits for them

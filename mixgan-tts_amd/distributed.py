@@ -9,6 +9,8 @@ A single flat bucket per optimizer keeps the collective large (xGMI rings are pe
 fewer, larger messages), and lets the D all-reduce overlap the start of the G phase on a side
 stream when `async_op=True`.
 """
+import collections
+
 import torch
 import torch.distributed as dist
 
@@ -95,12 +97,19 @@ class GradBucket:
         self._pending = tuple(self._pending) + ((work, lo, hi),)
         return True
 
-    def all_reduce_mean(self, group=None, async_op=False):
-        """SUM all-reduce of the flat gradient (the parts not already in flight), then divide by the world size."""
+    def all_reduce_sum(self, group=None, async_op=False):
+        """all_reduce_mean without the division: the exchange of exact-shard training, where every rank's loss is
+        already divided by the denominators of the whole batch and the SUM of the gradients is the single-process
+        gradient (HotPathTrainer(exact_shards=True))."""
+        return self.all_reduce_mean(group, async_op, mean=False)
+
+    def all_reduce_mean(self, group=None, async_op=False, mean=True):
+        """SUM all-reduce of the flat gradient (the parts not already in flight), then divide by the world size
+        (mean=False: leave the sum)."""
         self.gather()
         if not self.exchanging():
             return None
-        world = dist.get_world_size(group)
+        world = dist.get_world_size(group) if mean else 1
         pending, self._pending = self._pending, ()
         if pending and self.flat.is_cuda:
             # what the chunks did not cover, in as few collectives as possible
@@ -117,14 +126,16 @@ class GradBucket:
                           for (lo, hi) in cuts]
             for w in works:
                 w.wait()                             # stream-level wait on the GPU, no host block
-            self.flat.div_(world)
+            if mean:
+                self.flat.div_(world)
             return None
         if self.stub:
             return None
         work = dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group, async_op=async_op)
         if async_op:
             return _Pending(work, self.flat, world)
-        self.flat.div_(world)
+        if mean:
+            self.flat.div_(world)
         return None
 
 
@@ -134,7 +145,8 @@ class _Pending:
 
     def wait(self):
         self.work.wait()
-        self.flat.div_(self.world)
+        if self.world != 1:
+            self.flat.div_(self.world)
 
 
 def shard_batch(n_items, rank=None, world=None):
@@ -146,3 +158,108 @@ def shard_batch(n_items, rank=None, world=None):
     per = (n_items + world - 1) // world
     lo = min(n_items, rank * per)
     return lo, min(n_items, lo + per)
+
+
+# ------------------------------------------------------------------ exact steps on ragged shards
+# A term of the whole-batch loss is w_k * (sum over ranks of S_k,r) / D_k with D_k a count over the WHOLE batch.  A rank
+# that divides its numerators by the global D_k holds a share of the loss; the shares add up to the single-process loss
+# and the SUM of the gradients (GradBucket.all_reduce_sum) is the single-process gradient, for any split of the batch.
+# What the ranks have to agree on: the number of items and the padded length (host integers, known before the step),
+# and the data-dependent counts (device integers, exchanged while the D phase runs).
+BatchShape = collections.namedtuple("BatchShape", "n_total max_len world")
+
+
+def _collective_device(group=None):
+    return torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+
+
+def exchange_batch_shapes(pairs, group=None):
+    """[(n_items, length), ...] of this rank, the same number of pairs on every rank -> [BatchShape, ...]: the item
+    counts summed and the lengths maximised over the ranks, all in ONE collective (an all-gather of 2 * len(pairs)
+    integers), returned as host integers -- the caller waits for the collective."""
+    pairs = [(int(n), int(length)) for n, length in pairs]
+    if not is_distributed():
+        return [BatchShape(n, length, 1) for n, length in pairs]
+    world = dist.get_world_size(group)
+    mine = torch.tensor(pairs, dtype=torch.int64, device=_collective_device(group)).reshape(-1)
+    every = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(every, mine, group=group)
+    table = torch.stack(every).cpu().reshape(world, len(pairs), 2)
+    return [BatchShape(int(table[:, k, 0].sum()), int(table[:, k, 1].max()), world) for k in range(len(pairs))]
+
+
+def exchange_batch_shape(n_items, length, group=None):
+    """BatchShape(n_total, max_len, world) of one step: this rank's item count and padded length, SUM / MAX over the
+    ranks in one small collective; its arguments on a single process."""
+    return exchange_batch_shapes([(n_items, length)], group)[0]
+
+
+class ShardCounts:
+    """The data-dependent counts of one step as ONE int64 device vector -- counted mel rows, valid word positions,
+    valid phoneme positions, sum of ilen * olen for guided attention -- integers, so that their SUM all-reduce is exact
+    (16 ranks x 16 x 4000 x 80 is past 2^24: they become fp32 once, after the exchange).  `all_reduce_async` puts the
+    collective behind an event on a side stream (the hand-off of GradBucket.all_reduce_chunk_async), `wait` makes the
+    current stream wait for it right before the first term that divides by a count; nothing is read on the host.
+    `n_items` is the host-known item count of the whole batch (BatchShape.n_total)."""
+
+    FIELDS = ("mel_rows", "words", "phonemes", "attn_cells")
+    always_exchange = False
+    _side = {}
+
+    def __init__(self, device, n_items=None):
+        self.vec = torch.zeros(len(self.FIELDS), dtype=torch.int64, device=device)
+        self.n_items = n_items
+        self._work = self._done = None
+        self._started = False
+
+    def slot(self, name):
+        """The one-element view a producer writes its local count into (before all_reduce_async)."""
+        k = self.FIELDS.index(name)
+        return self.vec[k:k + 1]
+
+    def put(self, name, value):
+        self.slot(name).copy_(torch.as_tensor(value).reshape(1))
+
+    def all_reduce_async(self, group=None):
+        """Start the SUM all-reduce of the vector; no-op on a single process.  Once per step."""
+        if self._started:
+            raise RuntimeError("ShardCounts: the counts were exchanged already")
+        self._started = True
+        if not (dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or self.always_exchange)):
+            return False
+        if not self.vec.is_cuda:
+            self._work = dist.all_reduce(self.vec, op=dist.ReduceOp.SUM, group=group, async_op=True)
+            return True
+        dev = self.vec.device
+        if dev not in ShardCounts._side:
+            ShardCounts._side[dev] = torch.cuda.Stream(device=dev)
+        side = ShardCounts._side[dev]
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(dev))
+        side.wait_event(ready)
+        with torch.cuda.stream(side):          # c10d orders the collective behind the CURRENT stream: the side one
+            self._work = dist.all_reduce(self.vec, op=dist.ReduceOp.SUM, group=group, async_op=True)
+            self._work.wait()                  # stream-level: the side stream waits, the host does not
+            self._done = torch.cuda.Event()
+            self._done.record(side)
+        self.vec.record_stream(side)
+        return True
+
+    def wait(self):
+        if self._done is not None:
+            torch.cuda.current_stream(self.vec.device).wait_event(self._done)
+            self._done = self._work = None
+        elif self._work is not None:
+            self._work.wait()
+            self._work = None
+
+    def __getitem__(self, name):
+        """The global count: `n_items` as a host integer, the others as 0-dim int64 device tensors (waits first)."""
+        if name == "n_items":
+            if self.n_items is None:
+                raise KeyError("ShardCounts: n_items was not given")
+            return self.n_items
+        if not self._started:
+            raise RuntimeError("ShardCounts: read before all_reduce_async -- these would be one rank's counts")
+        self.wait()
+        return self.vec[self.FIELDS.index(name)]

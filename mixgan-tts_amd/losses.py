@@ -29,23 +29,28 @@ class _MseConstFn(torch.autograd.Function):
 
 
 class _L1Fn(torch.autograd.Function):
-    """F.l1_loss(target, pred) with gradient to `pred` only (the reference detaches the real maps)."""
+    """F.l1_loss(target, pred) with gradient to `pred` only (the reference detaches the real maps).
+    den (host number, optional): the divisor in place of pred.numel() -- the element count of the WHOLE batch when
+    `pred` is one rank's shard of it."""
 
     @staticmethod
-    def forward(ctx, pred, target):
+    def forward(ctx, pred, target, den=None):
         pred, target = pred.contiguous(), target.detach().contiguous()
+        if den is not None and not den > 0:
+            raise ValueError("den must be positive")
         out = torch.empty(1, device=pred.device)
         check(_lib.lib().mg_loss_sum(fptr(pred), fptr(target), 0.0, 1, pred.numel(), fptr(out), stream_ptr()))
         ctx.save_for_backward(pred, target)
-        return out[0] / pred.numel()
+        ctx.den = pred.numel() if den is None else den
+        return out[0] / ctx.den
 
     @staticmethod
     def backward(ctx, g):
         pred, target = ctx.saved_tensors
         d = torch.empty_like(pred)
         check(_lib.lib().mg_loss_grad(fptr(pred), fptr(target), 0.0, 1, fptr(g.reshape(1).contiguous()),
-                                      1.0 / pred.numel(), pred.numel(), fptr(d), stream_ptr()))
-        return d, None
+                                      1.0 / ctx.den, pred.numel(), fptr(d), stream_ptr()))
+        return d, None, None
 
 
 _SCRATCH = {}
@@ -129,11 +134,13 @@ class _RangeMeansFn(torch.autograd.Function):
     the a-range only).  The trainer runs D(fake) and D(real) as one pass over 2B items; slicing the maps apart for the
     losses made autograd rebuild every map's gradient from two zero-padded halves (a fill, a copy and an add per half
     and map: ~55 launches per step).  Here the maps go in whole, and the backward is one zero-fill of one flat buffer
-    plus one launch that writes every term's gradient into its range."""
+    plus one launch that writes every term's gradient into its range.
+    spec.den (a _Spec, optional): one host denominator per term in place of the term's element count."""
 
     @staticmethod
     def forward(ctx, spec, *tensors):
         nt = len(spec)
+        den = getattr(spec, "den", None)
         if nt < 1 or nt > _lib.MG_LOSS_MAX_TERMS:
             raise ValueError("1..%d terms per call" % _lib.MG_LOSS_MAX_TERMS)
         xs = [t.contiguous() for t in tensors]
@@ -149,7 +156,11 @@ class _RangeMeansFn(torch.autograd.Function):
                                      float(c), float(w), int(mode), int(grp))
         dev = xs[0].device
         out = torch.empty(1 + _lib.MG_LOSS_GROUPS + nt, device=dev, dtype=torch.float32)
-        check(_lib.lib().mg_multi_loss_fwd(terms, nt, fptr(_multi_scratch(dev)), fptr(out), stream_ptr()))
+        if den is None:
+            check(_lib.lib().mg_multi_loss_fwd(terms, nt, fptr(_multi_scratch(dev)), fptr(out), stream_ptr()))
+        else:
+            check(_lib.lib().mg_multi_loss_fwd_den(terms, nt, _den_array(den, nt), fptr(_multi_scratch(dev)), fptr(out),
+                                                   stream_ptr()))
         ctx.spec = spec
         ctx.save_for_backward(*xs)
         return out
@@ -173,26 +184,59 @@ class _RangeMeansFn(torch.autograd.Function):
             da = (fptr(grads[ti]).value + 4 * a_lo * per) if grads[ti] is not None else None
             terms[k] = _lib.LossTerm(base + 4 * a_lo * per, (base + 4 * b_lo * per) if mode == 1 else None, da,
                                      (a_hi - a_lo) * per, float(c), float(w), int(mode), int(grp))
-        check(_lib.lib().mg_multi_loss_bwd(terms, nt, fptr(g[:1].contiguous()), stream_ptr()))
+        den = getattr(spec, "den", None)
+        if den is None:
+            check(_lib.lib().mg_multi_loss_bwd(terms, nt, fptr(g[:1].contiguous()), stream_ptr()))
+        else:
+            check(_lib.lib().mg_multi_loss_bwd_den(terms, nt, _den_array(den, nt), fptr(g[:1].contiguous()),
+                                                   stream_ptr()))
         return (None, *grads)
 
 
-def _range_means(spec, tensors):
-    """spec entries (tensor index, mode, c, weight, group, a_lo, a_hi, b_lo); no two terms may write the same rows."""
-    return _RangeMeansFn.apply(tuple(spec), *tensors)
+class _Spec(tuple):
+    """The spec tuple of _RangeMeansFn with the optional per-term denominators riding along."""
+    den = None
 
 
-def d_loss_total_2b(logit_cond, logit_uncond, B):
-    """d_loss_total on the last maps of ONE discriminator pass over [fake (rows 0..B-1); real (rows B..2B-1)]."""
-    out = _range_means([(0, 0, 1.0, 0.5, 0, B, 2 * B, 0), (1, 0, 1.0, 0.5, 0, B, 2 * B, 0),
-                        (0, 0, 0.0, 0.5, 1, 0, B, 0), (1, 0, 0.0, 0.5, 1, 0, B, 0)], [logit_cond, logit_uncond])
+def _den_array(den, nt):
+    import ctypes
+    if len(den) != nt:
+        raise ValueError("one denominator per term: %d for %d terms" % (len(den), nt))
+    return (ctypes.c_double * nt)(*[float(d) for d in den])
+
+
+def _range_means(spec, tensors, den=None):
+    """spec entries (tensor index, mode, c, weight, group, a_lo, a_hi, b_lo); no two terms may write the same rows.
+    den: one host denominator per term (mg_multi_loss_fwd_den); None = each term's own element count (a mean)."""
+    spec = _Spec(spec)
+    if den is not None:
+        spec.den = tuple(float(d) for d in den)
+    return _RangeMeansFn.apply(spec, *tensors)
+
+
+def _global_den(spec, tensors, B, n_total):
+    """The denominators of the whole batch for terms that each cover B of its n_total items: the term's element count
+    per item times n_total."""
+    if n_total is None:
+        return None
+    return [tensors[e[0]][0].numel() * (e[6] - e[5]) // B * n_total for e in spec]
+
+
+def d_loss_total_2b(logit_cond, logit_uncond, B, n_total=None):
+    """d_loss_total on the last maps of ONE discriminator pass over [fake (rows 0..B-1); real (rows B..2B-1)].
+    n_total: the item count of the whole batch when these B items are one rank's shard of it -- every mean then divides
+    by the whole batch's element count (the maps of all ranks have the same length), and the result is the rank's share."""
+    spec = [(0, 0, 1.0, 0.5, 0, B, 2 * B, 0), (1, 0, 1.0, 0.5, 0, B, 2 * B, 0),
+            (0, 0, 0.0, 0.5, 1, 0, B, 0), (1, 0, 0.0, 0.5, 1, 0, B, 0)]
+    tensors = [logit_cond, logit_uncond]
+    out = _range_means(spec, tensors, _global_den(spec, tensors, B, n_total))
     return out[0], out[1], out[2]
 
 
-def g_adv_fm_total_2b(cond_maps, uncond_maps, B, lambda_fm, n_layers=5):
+def g_adv_fm_total_2b(cond_maps, uncond_maps, B, lambda_fm, n_layers=5, n_total=None):
     """g_adv_fm_total on the maps of ONE discriminator pass over [fake; real]: LSGAN on the fake rows of the last maps,
     feature matching |fake - real| on the others (gradient to the fake rows only, as model/loss.py:221-227 with the real
-    maps as targets)."""
+    maps as targets).  n_total: as in d_loss_total_2b."""
     w = lambda_fm * (4.0 / (n_layers + 1)) * 0.5
     nm = len(cond_maps)
     tensors = list(cond_maps) + list(uncond_maps)
@@ -200,7 +244,7 @@ def g_adv_fm_total_2b(cond_maps, uncond_maps, B, lambda_fm, n_layers=5):
     for j in range(nm - 1):
         spec.append((j, 1, 0.0, w, 1, 0, B, B))
         spec.append((nm + j, 1, 0.0, w, 1, 0, B, B))
-    out = _range_means(spec, tensors)
+    out = _range_means(spec, tensors, _global_den(spec, tensors, B, n_total))
     return out[0], out[1], out[2]
 
 
@@ -259,13 +303,15 @@ def get_fm_loss(D_real_cond, D_real_uncond, D_fake_cond, D_fake_uncond, n_layers
 
 class _MelL1Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, pad):
+    def forward(ctx, pred, target, pad, den=None):
         pred, target = pred.contiguous(), target.detach().contiguous()
         B, L, M = pred.shape
         pad8 = pad.to(torch.uint8).contiguous()
         out = torch.empty(2, device=pred.device)
         check(_lib.lib().mg_mel_l1_fwd(fptr(pred), fptr(target), iptr(pad8, torch.uint8), B * L, M, fptr(out),
                                        stream_ptr()))
+        if den is not None:      # the whole batch's M * counted rows: out[1] is this shard's
+            out = torch.stack([out[0], den.detach().to(torch.float32).reshape(())])
         ctx.save_for_backward(pred, target, pad8, out)
         return out[0] / out[1]
 
@@ -277,22 +323,40 @@ class _MelL1Fn(torch.autograd.Function):
         check(_lib.lib().mg_mel_l1_bwd(fptr(pred), fptr(target), iptr(pad8, torch.uint8), B * L, M,
                                        fptr(g.reshape(1).contiguous()), fptr(out[1:2].contiguous()), fptr(d),
                                        stream_ptr()))
-        return d, None, None
+        return d, None, None, None
 
 
-def get_mel_loss(mel_predictions, mel_targets, mel_masks_fill):
+def get_mel_loss(mel_predictions, mel_targets, mel_masks_fill, den=None):
     """model/loss.py:229-242: masked_fill(pad, 0) on both, L1 weighted by non-zero target rows.
-    mel_masks_fill: bool [B, L], True = pad."""
-    return _MelL1Fn.apply(mel_predictions, mel_targets, mel_masks_fill)
+    mel_masks_fill: bool [B, L], True = pad.  den: a device scalar that replaces the denominator (M * the counted rows
+    of THIS tensor) -- M * the counted rows of the whole batch (mel_count_rows, summed over the ranks) when the tensors
+    are one rank's shard; both the value and the gradient divide by it, without a host read."""
+    if den is None:
+        return _MelL1Fn.apply(mel_predictions, mel_targets, mel_masks_fill)
+    return _MelL1Fn.apply(mel_predictions, mel_targets, mel_masks_fill, den)
+
+
+def mel_count_rows(mel_targets, mel_masks_fill, out=None):
+    """The number of rows get_mel_loss counts in mel_targets [B, L, M] (unpadded, with a non-zero entry), as a
+    one-element int64 device tensor (`out`, e.g. ShardCounts.slot("mel_rows"), or a new one)."""
+    target = mel_targets.detach().contiguous()
+    B, L, M = target.shape
+    pad8 = mel_masks_fill.to(torch.uint8).contiguous() if mel_masks_fill is not None else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.int64, device=target.device)
+    check(_lib.lib().mg_mel_count_rows(fptr(target), iptr(pad8, torch.uint8, True), B * L, M, iptr(out, torch.int64),
+                                       stream_ptr()))
+    return out
 
 
 # --------------------------------------------------------------------------------------------------
 # the linguistic encoder's terms of recon_loss (model/loss.py:128-195): small masked means, a guided-attention mask
 # and a CTC dynamic program -- device-side torch, vectorised over the batch (no per-utterance host loop).
 # --------------------------------------------------------------------------------------------------
-def guided_attention_loss(att, ilens, olens, sigma, alpha):
+def guided_attention_loss(att, ilens, olens, sigma, alpha, den=None):
     """GuidedAttentionLoss (model/loss.py:261-352) on att [B, T_out, T_in]: alpha * mean over the valid (out, in)
-    cells of att * (1 - exp(-(in/ilen - out/olen)^2 / (2 sigma^2)))."""
+    cells of att * (1 - exp(-(in/ilen - out/olen)^2 / (2 sigma^2))).  den: the number of valid cells of the whole
+    batch (sum of ilen * olen) when att is one rank's shard: the sum over this shard's cells divided by it."""
     B, To, Ti = att.shape
     il = ilens.to(att.device, torch.float32)[:, None, None]
     ol = olens.to(att.device, torch.float32)[:, None, None]
@@ -300,16 +364,18 @@ def guided_attention_loss(att, ilens, olens, sigma, alpha):
     i = torch.arange(Ti, device=att.device, dtype=torch.float32)[None, None, :]
     mask = (o < ol) & (i < il)
     g = 1.0 - torch.exp(-((i / il - o / ol) ** 2) / (2 * sigma ** 2))
-    return alpha * (g * att).masked_select(mask).mean()
+    cells = (g * att).masked_select(mask)
+    return alpha * (cells.mean() if den is None else cells.sum() / den)
 
 
-def forward_sum_loss(attn_logprob, in_lens, out_lens, blank_logprob=-1.0):
+def forward_sum_loss(attn_logprob, in_lens, out_lens, blank_logprob=-1.0, den=None):
     """ForwardSumLoss (model/loss.py:420-447) on attn_logprob [B, 1, T_out, T_in]: a blank column of `blank_logprob`
     in front, log_softmax over the first in_len + 1 columns, CTC against 1..in_len (zero_infinity, mean over the
     target length), then the batch mean.  Columns past in_len + 1 are filled with -1e4 rather than cut (one batched
     call): exp(-1e4 - max) is exactly 0 in fp32, so the value is the reference's, and unlike -inf the filler gives
     the CTC backward finite gradients there (at -inf it returns NaN, which the log_softmax backward would spread over
-    the whole row).  The padded keys' -inf scores all lie in those columns."""
+    the whole row).  The padded keys' -inf scores all lie in those columns.  den: the item count of the whole batch
+    when these B items are one rank's shard (sum / den instead of the mean)."""
     B, _, To, Ti = attn_logprob.shape
     dev = attn_logprob.device
     il = in_lens.to(dev, torch.int64)
@@ -320,7 +386,8 @@ def forward_sum_loss(attn_logprob, in_lens, out_lens, blank_logprob=-1.0):
     lp = torch.log_softmax(lp, -1).transpose(0, 1)                                       # [To, B, Ti + 1]
     targets = (torch.arange(1, Ti + 1, device=dev)[None, :].expand(B, Ti) * (cols[None, 1:] <= il[:, None]))
     per = torch.nn.functional.ctc_loss(lp, targets, ol, il, blank=0, reduction="none", zero_infinity=True)
-    return (per / il.clamp(min=1).to(per.dtype)).mean()
+    per = per / il.clamp(min=1).to(per.dtype)
+    return per.mean() if den is None else per.sum() / den
 
 
 class LinguisticEncoderLoss:
@@ -348,8 +415,20 @@ class LinguisticEncoderLoss:
             self.ctc_weight_start, self.ctc_weight_end = al["ctc_weight_start"], al["ctc_weight_end"]
         self.last = None
 
-    def terms(self, batch, output, step):
-        """batch: the reference's batch list (pitch / energy targets at 14 / 15); output: MixGANTTS.forward's 16 slots."""
+    @staticmethod
+    def local_counts(output):
+        """This shard's data-dependent denominators, as 0-dim int64 tensors: what goes into distributed.ShardCounts
+        (slots "words", "phonemes", "attn_cells") before its all-reduce."""
+        src_masks, src_lens, mel_lens, src_w_masks = output[8], output[10], output[11], output[14]
+        return {"words": src_w_masks.sum(), "phonemes": src_masks.sum(),
+                "attn_cells": (src_lens.to(torch.int64) * mel_lens.to(torch.int64).to(src_lens.device)).sum()}
+
+    def terms(self, batch, output, step, counts=None):
+        """batch: the reference's batch list (pitch / energy targets at 14 / 15); output: MixGANTTS.forward's 16 slots.
+        counts: the denominators of the WHOLE batch when `batch` is one rank's shard of it -- a mapping (a
+        distributed.ShardCounts after its all-reduce, or a dict) with "n_items", "words", "phonemes" and "attn_cells"
+        (the sum of ilen * olen).  Every masked mean then becomes masked sum / global count, the CTC batch mean sum / N,
+        and the returned terms are this rank's SHARES: summed over the ranks they are `terms` on the whole batch."""
         p_pred, e_pred, logd_pred, d_rounded = output[4], output[5], output[6], output[7]
         src_masks, src_lens, mel_lens = output[8], output[10], output[11]
         alignments, logprobs, src_w_masks = output[12], output[13], output[14]
@@ -357,18 +436,26 @@ class LinguisticEncoderLoss:
         zero = torch.zeros((), device=dev)
         t = {"duration_loss": zero, "pitch_loss": zero, "energy_loss": zero, "helper_loss": zero}
         if self.model != "shallow":
-            mse = torch.nn.functional.mse_loss
-            logd_tgt = torch.log(d_rounded.float() + 1)
-            t["duration_loss"] = mse(logd_pred.masked_select(src_w_masks), logd_tgt.masked_select(src_w_masks))
-            t["pitch_loss"] = mse(p_pred.masked_select(src_masks), batch[14].to(dev).masked_select(src_masks))
-            t["energy_loss"] = mse(e_pred.masked_select(src_masks), batch[15].to(dev).masked_select(src_masks))
+            if counts is None:
+                mse = lambda a, b, key: torch.nn.functional.mse_loss(a, b)  # noqa: E731
+            else:
+                mse = lambda a, b, key: (a - b).pow(2).sum() / counts[key]  # noqa: E731
+            ga_den = None if counts is None else counts["attn_cells"]
+            n_items = None if counts is None else counts["n_items"]
+            logd_tgt = torch.log(d_rounded.to(logd_pred.dtype) + 1)
+            t["duration_loss"] = mse(logd_pred.masked_select(src_w_masks), logd_tgt.masked_select(src_w_masks),
+                                     "words")
+            t["pitch_loss"] = mse(p_pred.masked_select(src_masks), batch[14].to(dev).masked_select(src_masks),
+                                  "phonemes")
+            t["energy_loss"] = mse(e_pred.masked_select(src_masks), batch[15].to(dev).masked_select(src_masks),
+                                   "phonemes")
             if self.helper_type == "dga":
-                attn = sum(guided_attention_loss(a, src_lens, mel_lens, self.guided_sigma, self.guided_lambda)
+                attn = sum(guided_attention_loss(a, src_lens, mel_lens, self.guided_sigma, self.guided_lambda, ga_den)
                            for a in alignments[1])
                 t["attn_loss"] = attn
                 t["helper_loss"] = self.guided_weight * attn
             elif self.helper_type == "ctc":
-                ctc = sum(forward_sum_loss(lp, src_lens, mel_lens) for lp in logprobs)
+                ctc = sum(forward_sum_loss(lp, src_lens, mel_lens, den=n_items) for lp in logprobs)
                 t["ctc_loss"] = ctc
                 w = self.ctc_weight_start if step <= self.ctc_step else self.ctc_weight_end
                 t["helper_loss"] = w * ctc
@@ -376,7 +463,7 @@ class LinguisticEncoderLoss:
                       self.lambda_e * t["energy_loss"] + t["helper_loss"])
         return t
 
-    def __call__(self, batch, output, step):
-        t = self.terms(batch, output, step)
+    def __call__(self, batch, output, step, counts=None):
+        t = self.terms(batch, output, step, counts)
         self.last = {k: v.detach() for k, v in t.items()}
         return t["total"]

@@ -7,7 +7,10 @@ given conditioner, discriminator = JCUDiscriminator), with the reference's quirk
     adv + mel L1 + lambda_fm * FM, backward, clip, optG.step(), zero_grad.  The G-phase backward
     therefore also deposits gradients into D's parameters, which are NOT cleared before the next
     D-phase backward (SURVEY.md section 3.1 "D-grad leak") -- reproduced.
-  * multi-GPU: gradients are all-reduced (mean) per optimizer before clipping (distributed.py).
+  * multi-GPU: gradients are all-reduced (mean) per optimizer before clipping (distributed.py).  That is the
+    single-process step only when every rank holds the same number of items with the same lengths;
+    `exact_shards=True` makes it the single-process step on ragged shards too (every rank runs at the longest
+    rank's padded length and divides its loss terms by the whole batch's counts; gradients are SUMMED).
 
 The linguistic encoder is upstream of the path: `cond` is whatever produced
 the [B, L, 256] conditioner; its gradient is returned to the caller's graph as usual.
@@ -17,20 +20,31 @@ import os
 import torch
 
 from . import losses
-from .distributed import GradBucket
+from .distributed import GradBucket, ShardCounts, exchange_batch_shape, is_distributed
 from .optimizer import FlatAdam
 
 
 class HotPathTrainer:
     def __init__(self, diffusion, discriminator, train_config, model_config, extra_g_params=(), g_param_order=None,
-                 resume=None, first_step=1):
+                 resume=None, first_step=1, exact_shards=False):
         """extra_g_params: generator parameters outside `diffusion` that the G optimizer also steps (the injected
         linguistic encoder, decoder ...).  g_param_order: the list the reference builds optG over (`model.parameters()`,
         utils/model.py:33) so that `optG.state_dict()` indexes parameters the same way (default: diffusion's, then the
         extras).  resume: (optG, optD, sdlG, sdlD) as returned by `get_model(..., train=True)` -- their restored state
         (moments, step counts, learning rates, scheduler epochs) is taken over.  first_step: train.py's `step` of the
-        first call (args.restore_step + 1, train.py:67); it only matters for grad_acc_step > 1 (train.py:80)."""
+        first call (args.restore_step + 1, train.py:67); it only matters for grad_acc_step > 1 (train.py:80).
+        exact_shards: the multi-rank step computes the single-process step on the concatenated batch even when the
+        ranks hold different numbers of items of different lengths.  step / step_from_model /
+        evaluate_step / evaluate_from_model then take `shape=` (distributed.BatchShape: the whole batch's item count
+        and padded length; PrefetchLoader(shape_group=...) attaches one to every batch) -- without it they exchange it
+        themselves, which costs one host round trip per step.  Inputs shorter than shape.max_len are padded here
+        (mel, cond, coarse mel with zeros, the pad mask with True); every loss term is this rank's numerator over the
+        whole batch's denominator, so the returned losses are this rank's SHARES (log_scalars sums them over the
+        ranks) and the gradient exchange is a SUM.  With grad_acc_step > 1 every micro-step is normalised over its own
+        global micro-batch, as a single process would.  `extra_loss` is taken as is: pass shares
+        (LinguisticEncoderLoss.terms(counts=...))."""
         self.G, self.D = diffusion, discriminator
+        self.exact_shards = bool(exact_shards)
         oc = train_config["optimizer"]
         self.grad_clip = oc["grad_clip_thresh"]
         self.lambda_fm = train_config["loss"]["lambda_fm" if diffusion.model != "shallow" else "lambda_fm_shallow"]
@@ -88,7 +102,11 @@ class HotPathTrainer:
     grad_hook = None      # optional callable(name, bucket) after the gradient exchange, before clipping (tests, logging)
 
     def _update(self, bucket, opt):
-        bucket.all_reduce_mean()                      # no-op on one process; waits for chunks already in flight
+        # no-op on one process; waits for chunks already in flight
+        if self.exact_shards:
+            bucket.all_reduce_sum()                   # the losses were divided by the whole batch's counts already
+        else:
+            bucket.all_reduce_mean()
         if self.grad_hook is not None:
             self.grad_hook("G" if bucket is self.bucketG else "D", bucket)
         if isinstance(opt, FlatAdam):
@@ -125,6 +143,9 @@ class HotPathTrainer:
             raise RuntimeError("capture() needs the GPU trainer (FlatAdam optimizers)")
         if self.bucketG.exchanging() or self.grad_acc != 1 or self.grad_hook is not None or self.G.t_fn or self.G.noise_fn:
             raise RuntimeError("capture(): single process, grad_acc_step = 1, no hooks")
+        if self.exact_shards:
+            raise RuntimeError("capture() is single-process: exact_shards has nothing to do there, build the trainer "
+                               "without it")
         dev = mel.device
         static = [None if a is None else a.detach().clone() for a in (mel, cond, spk, mel_pad_mask, coarse_mel)]
         self.optG.enable_device_hyper()
@@ -182,25 +203,69 @@ class HotPathTrainer:
         return cond_maps, uncond_maps, B
 
     # ------------------------------------------------------------------ the two phases on given generator outputs
-    def _d_loss(self, x_ts, x_prevs, x_prev_preds, spk, t):
+    # ------------------------------------------------------------------ exact_shards: what a step shares with the ranks
+    @staticmethod
+    def _pad_frames(x, L, value=0):
+        """x [B, l, ...] -> [B, L, ...], filled with `value` past l (autograd passes through)."""
+        if x is None or x.shape[1] == L:
+            return x
+        if x.shape[1] > L:
+            raise ValueError("exact_shards: %d frames, but the whole batch's padded length is %d" % (x.shape[1], L))
+        fill = x.new_full((x.shape[0], L - x.shape[1]) + tuple(x.shape[2:]), value)
+        return torch.cat([x, fill], 1)
+
+    def _exact_begin(self, shape, n_items, length, device, counts=None):
+        """The step's shard context: the whole batch's shape (exchanged here when the caller has none: one host round
+        trip) and the device vector of its data-dependent counts (the caller's, with the encoder's counts in it, or a
+        new one)."""
+        if not self.fused_losses:
+            raise RuntimeError("exact_shards runs the fused losses (fused_losses = True)")
+        if shape is None:
+            shape = exchange_batch_shape(n_items, length)
+        if counts is None:
+            counts = ShardCounts(device, shape.n_total)
+        elif counts.n_items is None:
+            counts.n_items = shape.n_total
+        return _Shard(shape.n_total, shape.max_len, counts)
+
+    def _exact_inputs(self, shape, counts, mel, cond, mel_pad_mask, *more):
+        """_exact_begin + the inputs padded to the whole batch's length + the count of mel rows under way."""
+        ex = self._exact_begin(shape, mel_pad_mask.shape[0], mel_pad_mask.shape[1], mel_pad_mask.device, counts)
+        L = ex.max_len
+        padded = [self._pad_frames(x, L) for x in (mel, cond)] + [self._pad_frames(mel_pad_mask, L, True)]
+        padded += [self._pad_frames(x, L) for x in more]
+        return ex, padded
+
+    def _exact_count(self, ex, target, mel_pad_mask):
+        """Count the rows the mel L1 will count on `target` and start the exchange of the step's counts: from here on
+        the collective runs next to whatever the step does until the first term that divides by a count."""
+        losses.mel_count_rows(target, mel_pad_mask, out=ex.counts.slot("mel_rows"))
+        ex.counts.all_reduce_async()
+
+    def _d_loss(self, x_ts, x_prevs, x_prev_preds, spk, t, ex=None):
         """train.py:135-144 / evaluate.py:80-88: everything the generator produced is detached."""
         det = lambda a: None if a is None else a.detach()  # noqa: E731
         if self.fused_losses:      # the maps go into the loss whole: no slicing for autograd to undo
             cm, um, B = self._d_both(det(x_ts), det(x_prev_preds), det(x_prevs), det(spk), t)
-            return losses.d_loss_total_2b(cm[-1], um[-1], B)[0]
+            return losses.d_loss_total_2b(cm[-1], um[-1], B, n_total=ex.n_total if ex is not None else None)[0]
         f_c, f_u, r_c, r_u = self._d_fake_and_real(det(x_ts), det(x_prev_preds), det(x_prevs), det(spk), t)
         d_real, d_fake = self.d_loss_fn(r_c[-1], r_u[-1], f_c[-1], f_u[-1])
         return d_real + d_fake
 
-    def _g_loss(self, x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss):
+    def _g_loss(self, x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss, ex=None):
         """train.py:156-182 with model/loss.py:153-167,196-199: adv + mel L1 (+ postnet L1 in shallow) + lambda_fm * FM
-        (+ the caller's upstream terms).  Returns (g_loss, dict of the parts)."""
+        (+ the caller's upstream terms).  Returns (g_loss, dict of the parts).  ex (exact_shards): every term divides
+        by the whole batch's denominator; the counted mel rows come from the step's exchanged counts."""
         G = self.G
         target = coarse_mel.detach() if G.model == "shallow" else mel
-        mel_loss = losses.get_mel_loss(G.denorm_spec(x0), target, mel_pad_mask)
+        mel_den = None
+        if ex is not None:      # int64 on the device until here: fp32 once, after the exchange
+            mel_den = (ex.counts["mel_rows"] * target.shape[-1]).to(torch.float32)
+        mel_loss = losses.get_mel_loss(G.denorm_spec(x0), target, mel_pad_mask, den=mel_den)
         if self.fused_losses:
             cm, um, B = self._d_both(x_ts, x_prev_preds, x_prevs, spk, t)
-            adv_fm, adv, fm = losses.g_adv_fm_total_2b(cm, um, B, self.lambda_fm, self.n_layers)
+            adv_fm, adv, fm = losses.g_adv_fm_total_2b(cm, um, B, self.lambda_fm, self.n_layers,
+                                                       n_total=ex.n_total if ex is not None else None)
             g_loss = adv_fm + mel_loss
         else:
             f_c, f_u, r_c, r_u = self._d_fake_and_real(x_ts, x_prev_preds, x_prevs, spk, t)
@@ -210,7 +275,8 @@ class HotPathTrainer:
         parts = {"adv_loss": adv.detach(), "mel_loss": mel_loss.detach(),
                  "fm_loss": fm.detach() if torch.is_tensor(fm) else fm}
         if G.model == "shallow" and coarse_mel is not None and (coarse_mel.requires_grad or not torch.is_grad_enabled()):
-            postnet_loss = losses._L1Fn.apply(coarse_mel, mel[:, :coarse_mel.shape[1], :].contiguous())
+            postnet_den = None if ex is None else ex.n_total * coarse_mel.shape[1] * coarse_mel.shape[2]
+            postnet_loss = losses._L1Fn.apply(coarse_mel, mel[:, :coarse_mel.shape[1], :].contiguous(), postnet_den)
             g_loss = g_loss + postnet_loss
             parts["postnet_loss"] = postnet_loss.detach()
         if extra_loss is not None:
@@ -219,7 +285,7 @@ class HotPathTrainer:
 
     # ------------------------------------------------------------------ train.py:131-184 on a given conditioner
     def step(self, mel, cond, spk, mel_pad_mask, coarse_mel=None, extra_loss=None, cond_d=None, spk_d=None,
-             coarse_mel_d=None):
+             coarse_mel_d=None, shape=None, counts=None, _ex=None):
         """One D phase + one G phase on a batch.  mel [B,L,M]; cond [B,L,H]; mel_pad_mask True = pad.
         cond_d / spk_d / coarse_mel_d: the D phase's generator inputs when they differ from the G phase's -- the
         reference calls `model(*(batch[2:]))` once per phase (train.py:133,153), i.e. the train-mode linguistic encoder
@@ -233,8 +299,17 @@ class HotPathTrainer:
         Random draws: the D-phase forward's (t, three noises), then the G-phase forward's.  With pair_forwards (one
         launch for both forwards) the G-phase set is drawn right behind the D-phase set; the caller has produced both
         conditioners before this call either way, so relative to train.py only the encoder's second-pass draws have
-        moved in front of the first diffusion draws (step_from_model(pair=False) keeps train.py's order exactly)."""
+        moved in front of the first diffusion draws (step_from_model(pair=False) keeps train.py's order exactly).
+
+        exact_shards only -- shape: the whole batch's distributed.BatchShape (exchanged here when None: one host round
+        trip); counts: a distributed.ShardCounts the caller has put the encoder's local counts into, not yet reduced
+        (the trainer adds the mel rows and starts the one all-reduce); the inputs may be shorter than shape.max_len."""
         G = self.G
+        ex = self._step_shard(_ex, shape, counts)
+        if ex is True:
+            ex, (mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d) = self._exact_inputs(
+                shape, counts, mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d)
+            self._exact_count(ex, coarse_mel if G.model == "shallow" else mel, mel_pad_mask)
         cd = cond if cond_d is None else cond_d
         sd = spk if spk_d is None else spk_d
         cmd = coarse_mel if coarse_mel_d is None else coarse_mel_d
@@ -252,15 +327,50 @@ class HotPathTrainer:
         finally:
             G.pair_forward = False
             G.pair_inputs = None
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, sd, t)
+        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, sd, t, ex)
         self._model_update(d_loss, self.bucketD, self.optD)
         # ---------------- G phase (train.py:153-184)
         x0, x_ts, x_prevs, x_prev_preds, t = G(mel, cond, spk, mel_pad_mask, coarse_mel)
-        g_loss, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss)
+        g_loss, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss,
+                                   ex)
         self._model_update(g_loss, self.bucketG, self.optG)
         self.step_no += 1
         out["d_loss"] = d_loss.detach()
         return out
+
+    def _step_shard(self, ex, shape, counts):
+        """None off exact mode (which takes no shape), the caller's context, or True: build one."""
+        if not self.exact_shards:
+            if shape is not None or counts is not None or ex is not None:
+                raise ValueError("shape= / counts= belong to HotPathTrainer(exact_shards=True)")
+            return None
+        return ex if ex is not None else True
+
+    def _exact_batch(self, batch, shape, counts):
+        """exact_shards around a whole model: the 17-slot batch padded to the whole batch's length (data.pad_batch_to),
+        the step's counts filled from the batch's length vectors -- valid word and phoneme positions, sum of
+        ilen * olen -- and, unless the mel L1's target is only known after the generator ran (shallow: the coarse mel),
+        the mel rows counted and the exchange started.  Returns the shard context."""
+        from .data import pad_batch_to, MEL_LENS_SLOT, MAX_MEL_SLOT, TEXT_LENS_SLOT
+        ex = self._exact_begin(shape, len(batch[MEL_LENS_SLOT]), int(batch[MAX_MEL_SLOT]), batch[11].device, counts)
+        pad_batch_to(batch, ex.max_len, in_place=True)
+        if counts is None:
+            text_lens, mel_lens = batch[TEXT_LENS_SLOT].to(torch.int64), batch[MEL_LENS_SLOT].to(torch.int64)
+            ex.counts.put("words", batch[7].to(torch.int64).sum())
+            ex.counts.put("phonemes", text_lens.sum())
+            ex.counts.put("attn_cells", (text_lens * mel_lens).sum())
+        if self.G.model != "shallow":
+            pad = torch.arange(ex.max_len, device=batch[11].device)[None, :] >= batch[MEL_LENS_SLOT][:, None]
+            self._exact_count(ex, batch[11], pad)
+        return ex
+
+    @staticmethod
+    def _upstream(upstream_loss, batch, output, step_no, ex):
+        if upstream_loss is None:
+            return None
+        if ex is None:
+            return upstream_loss(batch, output, step_no)
+        return upstream_loss(batch, output, step_no, counts=ex.counts)      # shares: see LinguisticEncoderLoss
 
     # ------------------------------------------------------------------ train.py:131-184 around a whole model
     @staticmethod
@@ -269,7 +379,7 @@ class HotPathTrainer:
         (x_ts, x_prevs, x_prev_preds), spk, t, mel_pad_mask = output[1], output[2], output[3], output[9]
         return output[0], x_ts, x_prevs, x_prev_preds, spk, t, mel_pad_mask, output[15]
 
-    def step_from_model(self, model, batch, upstream_loss=None, pair=False):
+    def step_from_model(self, model, batch, upstream_loss=None, pair=False, shape=None, counts=None):
         """train.py:131-184 verbatim around `model` (mixgan_tts_amd.MixGANTTS whose .diffusion is this trainer's
         generator; the linguistic encoder injected): `model(*(batch[2:]))` for the D phase, D update,
         `model(*(batch[2:]))` again for the G phase (a train-mode encoder gives a different conditioner and consumes
@@ -277,29 +387,39 @@ class HotPathTrainer:
         G update.  upstream_loss(batch, output, step_no) -> tensor | None supplies model/loss.py:195's duration / pitch /
         energy / helper terms of the linguistic encoder (losses.LinguisticEncoderLoss for the native one).
         pair=True launches both generator forwards together: the encoder then runs twice up front, which moves its
-        second-pass draws ahead of the first diffusion draws (statistically the same step, not draw-for-draw)."""
+        second-pass draws ahead of the first diffusion draws (statistically the same step, not draw-for-draw).
+
+        exact_shards: `batch` (a list) is padded in place to shape.max_len, the step's counts are taken from its length
+        vectors, and upstream_loss is called with `counts=` (the step's ShardCounts) and must return this rank's share
+        (LinguisticEncoderLoss does).  shallow: the mel L1's target is the G phase's coarse mel, so its rows are counted
+        and exchanged after that forward, not under the D phase."""
         if getattr(model, "diffusion", None) is not self.G:
             raise ValueError("step_from_model: model.diffusion is not this trainer's generator")
+        ex = self._step_shard(None, shape, counts)
+        if ex is True:
+            ex = self._exact_batch(batch, shape, counts)
         if pair:
-            return self._step_from_model_paired(model, batch, upstream_loss)
+            return self._step_from_model_paired(model, batch, upstream_loss, ex)
         with torch.no_grad():                    # every D-phase use is detached (train.py:135-137)
             output, *_ = model(*(batch[2:]))
         _, x_ts, x_prevs, x_prev_preds, spk, t, _, _ = self._unpack(output)
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, spk, t)
+        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, spk, t, ex)
         self._model_update(d_loss, self.bucketD, self.optD)
         output, p_targets, coarse_mels = model(*(batch[2:]))
         batch[9] = p_targets                     # train.py:155
         x0, x_ts, x_prevs, x_prev_preds, spk, t, mel_pad_mask, slot15 = self._unpack(output)
         mel = batch[11][:, :mel_pad_mask.shape[1], :]
-        extra = upstream_loss(batch, output, self.step_no) if upstream_loss is not None else None
+        if ex is not None and self.G.model == "shallow":
+            self._exact_count(ex, slot15, mel_pad_mask)
+        extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
         g_loss, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask,
-                                   slot15 if self.G.model == "shallow" else None, extra)
+                                   slot15 if self.G.model == "shallow" else None, extra, ex)
         self._model_update(g_loss, self.bucketG, self.optG)
         self.step_no += 1
         out["d_loss"] = d_loss.detach()
         return out
 
-    def _step_from_model_paired(self, model, batch, upstream_loss):
+    def _step_from_model_paired(self, model, batch, upstream_loss, ex=None):
         """Both encoder passes first (the second with grad), then step() with the two conditioners: one launch for both
         generator forwards.  Runs model.forward with its diffusion swapped for a recorder, so the encoder-side code
         is the model's own."""
@@ -316,47 +436,70 @@ class HotPathTrainer:
             model.diffusion = real
         batch[9] = p_targets
         mel, cond, spk, pad, coarse = g_in
-        extra = upstream_loss(batch, output, self.step_no) if upstream_loss is not None else None
         slot15 = output[15] if self.G.model == "shallow" else None
+        if ex is not None and self.G.model == "shallow":
+            self._exact_count(ex, slot15 if slot15 is not None else coarse, pad)
+        extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
         return self.step(mel, cond, spk, pad, slot15 if slot15 is not None else coarse, extra,
-                         cond_d=d_in[1], spk_d=d_in[2], coarse_mel_d=d_in[4])
+                         cond_d=d_in[1], spk_d=d_in[2], coarse_mel_d=d_in[4], _ex=ex)
 
     @torch.no_grad()
     def evaluate_step(self, mel, cond, spk, mel_pad_mask, coarse_mel=None, extra_loss=None, cond_d=None, spk_d=None,
-                      coarse_mel_d=None):
+                      coarse_mel_d=None, shape=None, counts=None):
         """The validation step of evaluate.py:70-120 for the path: the same two generator forwards and four
-        discriminator passes as step(), under no_grad, no update; returns the same loss dict."""
+        discriminator passes as step(), under no_grad, no update; returns the same loss dict (exact_shards: the
+        rank's shares, with shape= / counts= as in step())."""
         G = self.G
+        ex = self._step_shard(None, shape, counts)
+        if ex is True:
+            ex, (mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d) = self._exact_inputs(
+                shape, counts, mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d)
+            self._exact_count(ex, coarse_mel if G.model == "shallow" else mel, mel_pad_mask)
         cd = cond if cond_d is None else cond_d
         sd = spk if spk_d is None else spk_d
         cmd = coarse_mel if coarse_mel_d is None else coarse_mel_d
         _, x_ts, x_prevs, x_prev_preds, t = G(mel, cd, sd, mel_pad_mask, cmd)
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, sd, t)
+        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, sd, t, ex)
         x0, x_ts, x_prevs, x_prev_preds, t = G(mel, cond, spk, mel_pad_mask, coarse_mel)
-        _, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss)
+        _, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss, ex)
         out["d_loss"] = d_loss
         return out
 
     @torch.no_grad()
-    def evaluate_from_model(self, model, batch, upstream_loss=None):
-        """evaluate.py:76-120 around `model`: two `model(*(batch[2:]))` calls, losses only."""
+    def evaluate_from_model(self, model, batch, upstream_loss=None, shape=None, counts=None):
+        """evaluate.py:76-120 around `model`: two `model(*(batch[2:]))` calls, losses only (exact_shards: as
+        step_from_model)."""
+        ex = self._step_shard(None, shape, counts)
+        if ex is True:
+            ex = self._exact_batch(batch, shape, counts)
         output, *_ = model(*(batch[2:]))
         _, x_ts, x_prevs, x_prev_preds, spk, t, _, _ = self._unpack(output)
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, spk, t)
+        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, spk, t, ex)
         output, p_targets, coarse_mels = model(*(batch[2:]))
         batch[9] = p_targets
         x0, x_ts, x_prevs, x_prev_preds, spk, t, mel_pad_mask, slot15 = self._unpack(output)
         mel = batch[11][:, :mel_pad_mask.shape[1], :]
-        extra = upstream_loss(batch, output, self.step_no) if upstream_loss is not None else None
+        if ex is not None and self.G.model == "shallow":
+            self._exact_count(ex, slot15, mel_pad_mask)
+        extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
         _, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask,
-                              slot15 if self.G.model == "shallow" else None, extra)
+                              slot15 if self.G.model == "shallow" else None, extra, ex)
         out["d_loss"] = d_loss
         return out
 
     def log_scalars(self, out):
         """The host's read-back of a step's losses (train.py:198-199 `.item()`s): one synchronisation, after which the
         single-launch kernels' failure word is exact -- raises MixganHipError if a hand-off timed out in this step
-        (its gradients were NaN then)."""
+        (its gradients were NaN then).  exact_shards: `out` holds this rank's shares; they are summed over the ranks in
+        ONE collective before the read-back, so every rank logs the whole batch's losses -- and every rank has to call
+        this at the same steps."""
+        if self.exact_shards and is_distributed():
+            import torch.distributed as dist
+            keys = sorted(k for k, v in out.items() if torch.is_tensor(v))
+            if keys:
+                vec = torch.stack([out[k].detach().reshape(()).to(torch.float32) for k in keys])
+                dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+                out = dict(out, **{k: vec[i] for i, k in enumerate(keys)})
         vals = {k: (float(v) if torch.is_tensor(v) else v) for k, v in out.items()}
         self.check(sync=False)
         return vals
@@ -369,6 +512,13 @@ class HotPathTrainer:
     def end_epoch(self):
         self.sdlG.step()
         self.sdlD.step()
+
+
+class _Shard:
+    """What one exact_shards step knows about the whole batch: item count, padded length, exchanged counts."""
+
+    def __init__(self, n_total, max_len, counts):
+        self.n_total, self.max_len, self.counts = n_total, max_len, counts
 
 
 class _GraphedStep:
@@ -411,6 +561,8 @@ class AuxTrainer:
     mae(postnet_output, mel) + sum_t masked-L1(denorm(trace_t), mel)) -> backward -> gradient all-reduce ->
     clip_grad_norm_ -> ScheduledOptim (model/optimizer.py).  The linguistic encoder's own loss terms
     (duration / pitch / energy / alignment helper, out of scope) enter through `extra_loss`.
+    Multi-rank: gradients are averaged (GradBucket.all_reduce_mean), exact on equal shards only; the exact_shards
+    normalisation of HotPathTrainer is not implemented for this step.
 
     model: a module with `.coarse_mel(cond, pad_mask)` and `.diffusion` (mixgan_tts_amd.MixGANTTS built with
     args.model == "aux"); `params` defaults to model.parameters() (include the linguistic encoder's there)."""
