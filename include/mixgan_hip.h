@@ -861,6 +861,33 @@ int mg_align_viterbi(const float *ll, const int *seq, const uint8_t *skip, const
 int mg_align_stats(const float *x, const int *frame_index, const int *offsets, int G, int D, double *sum,
                    double *sumsq, void *stream);
 
+/* ------------------------------------------------------------------ objective synthesis metrics (metrics.py;
+ * csrc/dtw.hip): mel-cepstral distortion along a dynamic-time-warping path.  All calls take ragged batches with device
+ * int32 length arrays (clamped to the padded length), read nothing at or past a row's length, use no atomics and give
+ * a pair the same bits wherever it sits in the batch and on every run.
+ * Cepstra: mel [B, T, M] natural-log mel, n_frames [B]; out [B, T, n_coef] holds the coefficients 1 .. n_coef of the
+ * orthonormal DCT-II over the M bins (c0, the energy term, is left out):
+ *   out[b, t, k - 1] = sqrt(2 / M) sum_m mel[b, t, m] cos(pi / M (m + 1/2) k)   for t < n_frames[b], 0 elsewhere,
+ * accumulated in float32 over ascending m.  MG_ERR_SHAPE unless 1 <= B <= 65535, T >= 1 and
+ * 1 <= n_coef < M <= MG_CEPSTRA_MAX_M. */
+#define MG_CEPSTRA_MAX_M 128
+#define MG_DTW_MAX_T 4096
+#define MG_DTW_MAX_D 64
+int mg_mel_cepstra(const float *mel, const int *n_frames, int B, int T, int M, int n_coef, float *out, void *stream);
+/* DTW: a [B, Ta, D], b [B, Tb, D], a_len / b_len [B].  With c(i, j) = sqrt(sum_d (a[i, d] - b[j, d])^2) in float32,
+ *   Dacc(0, 0) = c(0, 0),  Dacc(i, j) = c(i, j) + min(Dacc(i-1, j-1), Dacc(i-1, j), Dacc(i, j-1))
+ * over the predecessors that exist; ties go to the diagonal, then to (i-1, j), then to (i, j-1).  total [B] float32:
+ * Dacc(a_len - 1, b_len - 1); path_len [B] int32: the cells on the back-traced path; path [B, Ta + Tb - 1, 2] int32,
+ * may be null: the (i, j) cells in ascending order, -1 in the rows past path_len.  A pair with a_len or b_len 0 gives
+ * total 0, path_len 0 and a path of -1.  MG_ERR_SHAPE unless B >= 1, 1 <= Ta, Tb <= MG_DTW_MAX_T and
+ * 1 <= D <= MG_DTW_MAX_D.  workspace: mg_dtw_workspace_bytes(B, Ta, Tb) bytes of device memory,
+ *   4 B (ceil(Tb / 16) Ta + MG_DTW_MAX_D (Ta + Tb)):
+ * the back-pointers, two bits a cell, and a feature-major copy of both operands (sized for the largest D, so that
+ * the query needs none); MG_ERR_WORKSPACE when it is null or smaller.  Every error returns before any launch. */
+size_t mg_dtw_workspace_bytes(int B, int Ta, int Tb);
+int mg_dtw(const float *a, const float *b, const int *a_len, const int *b_len, int B, int Ta, int Tb, int D,
+           float *total, int *path_len, int *path, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

@@ -39,5 +39,8 @@ from .pitch import yin_candidates, pitch_track, extract_f0, native_pitch, PitchG
 from . import aligner  # noqa: F401
 from .aligner import (ForcedAligner, AlignGeometryError, emissions, viterbi_align, gaussian_stats,  # noqa: F401
                       read_lexicon)
+from . import metrics  # noqa: F401
+from .metrics import (DtwGeometryError, mel_cepstra, dtw, mel_cepstral_distortion, f0_metrics,  # noqa: F401
+                      synthesis_report, evaluate_model)
 
 __version__ = "0.1.0"

@@ -34,6 +34,7 @@ MG_PITCH_N, MG_PITCH_W, MG_PITCH_K, MG_PITCH_PARAMS = 1024, 512, 4, 7
 (MG_PITCH_P_SR, MG_PITCH_P_TAU_MAX, MG_PITCH_P_THETA, MG_PITCH_P_BETA, MG_PITCH_P_LAMBDA, MG_PITCH_P_SWITCH,
  MG_PITCH_P_GATE) = range(MG_PITCH_PARAMS)
 MG_ALIGN_MAX_D, MG_ALIGN_MAX_G, MG_ALIGN_MAX_S, MG_ALIGN_MAX_T = 128, 1024, 2048, 4096
+MG_CEPSTRA_MAX_M, MG_DTW_MAX_T, MG_DTW_MAX_D = 128, 4096, 64
 
 
 class LossTerm(ctypes.Structure):
@@ -224,6 +225,9 @@ def _signatures():
         "mg_align_viterbi_workspace_bytes": (sz, [i, i, i]),
         "mg_align_viterbi": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]),
         "mg_align_stats": (i, [vp, vp, vp, i, i, vp, vp, vp]),
+        "mg_mel_cepstra": (i, [vp, vp, i, i, i, i, vp, vp]),
+        "mg_dtw_workspace_bytes": (sz, [i, i, i]),
+        "mg_dtw": (i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]),
     }
 
 
