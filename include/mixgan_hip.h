@@ -352,7 +352,15 @@ int mg_denoiser_fwd_pair(const mg_denoiser_dims *dims, const float *packed, cons
  * discard the workspaces in use (their sticky words stay set).  Test hooks, read per call: MG_PERSIST_SPIN_LIMIT (polls
  * before giving up), MG_PERSIST_FLAGS bit 1 (a tile withholds one hand-off). */
 unsigned mg_persist_error(int clear);
-/* Copies the single-launch forward's counter words {ticket, error, launches, workgroups done} of a (B, L, no-save)
+/* Order of the counter words that mg_denoiser_persist_status and mg_denoiser_bwd_status write to host_out4. */
+enum mg_status_word {
+    MG_STATUS_TICKET = 0,   /* tickets handed out by the running launch (0 between launches) */
+    MG_STATUS_ERROR = 1,    /* sticky: code of a hand-off that timed out, or 0                */
+    MG_STATUS_LAUNCHES = 2, /* single launches completed on the workspace                    */
+    MG_STATUS_DONE = 3,     /* workgroups of the running launch that have exited             */
+    MG_STATUS_WORDS = 4
+};
+/* Copies the single-launch forward's counter words (MG_STATUS_*: ticket, error, launches, workgroups done) of a (B, L, no-save)
  * workspace to host_out4 and synchronises the stream: error != 0 means a neighbour hand-off timed out (the launch
  * drained instead of hanging; its output is NaN). */
 int mg_denoiser_persist_status(const mg_denoiser_dims *d, const float *workspace, int B, int L, unsigned *host_out4,
@@ -372,7 +380,7 @@ int mg_denoiser_bwd(const mg_denoiser_dims *d, const float *packed, const float 
                     const float *x_t, const float *cond, const float *spk, float *workspace,
                     float *bwd_workspace, size_t bwd_workspace_floats, float *const *grads,
                     float *d_x_t, float *d_cond, float *d_spk, int B, int L, void *stream);
-/* Copies the single-launch data-gradient kernel's counter words {ticket, error, launches, workgroups done} of a (B, L)
+/* Copies the single-launch data-gradient kernel's counter words (MG_STATUS_*: ticket, error, launches, workgroups done) of a (B, L)
  * backward workspace to host_out4 and synchronises the stream.  launches counts the single launches completed on this
  * workspace (the launch-per-layer path leaves it alone); error != 0: a hand-off timed out (sticky). */
 int mg_denoiser_bwd_status(const mg_denoiser_dims *d, const float *bwd_workspace, int B, int L, unsigned *host_out4,

@@ -21,6 +21,7 @@ MG_DEN_BACKWARD, MG_DEN_SPLIT, MG_DEN_P16, MG_DEN_JOBS_RESIDENT = 1, 2, 4, 8    
 MG_FWD_SAVE, MG_FWD_SPLIT, MG_FWD_P16 = 1, 2, 4                                   # mg_denoiser_fwd modes
 MG_PLAN_PER_LAYER, MG_PLAN_SINGLE = 0, 1                                          # mg_fwd_plan.path
 MG_PLAN_PERSIST, MG_PLAN_PERSIST16, MG_PLAN_TEAM16 = 0, 1, 2                      # mg_fwd_plan.family
+MG_STATUS_TICKET, MG_STATUS_ERROR, MG_STATUS_LAUNCHES, MG_STATUS_DONE, MG_STATUS_WORDS = range(5)   # mg_denoiser_*_status
 MG_CONV_EPI_PLAIN, MG_CONV_EPI_REFLECT, MG_CONV_EPI_PHASES_SLICE, MG_CONV_EPI_NEEDS_WM2 = range(4)   # mg_conv1d_fwd_plan
 # the denoiser's weight / gradient pointer table: head slots, then MG_DEN_LAYER_PTRS slots per residual layer
 MG_DEN_HEAD_PTRS, MG_DEN_LAYER_PTRS = 8, 9

@@ -18,6 +18,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 // ------------------------------------------------------------------------------------------ epilogues
 struct EpiCond {
@@ -340,7 +341,6 @@ extern "C" size_t mg_denoiser_workspace_floats(const mg_denoiser_dims *d, int B,
 // ------------------------------------------------------------------------------------------ profiling
 // HIP-event brackets around the dominant kernel (the k=3 gated conv), recorded on the launch
 // stream inside mg_denoiser_fwd while a profile session is open.  Host-side state only.
-#include <vector>
 static thread_local std::vector<hipEvent_t> g_prof_ev;  // 2 per bracket
 static thread_local int g_prof_used = 0, g_prof_cap = 0, g_prof_every = 1, g_prof_seen = 0, g_prof_open = 0;
 
@@ -669,12 +669,14 @@ extern "C" int mg_denoiser_persist_status(const mg_denoiser_dims *d, const float
 {
     if (den_check(d) != MG_OK || !ws || !host_out4 || B <= 0 || L <= 0) return MG_ERR_ARG;
     const DenWs w = den_ws(d, B, L, 0);
-    hipError_t e = hipMemcpyAsync(host_out4, ws + w.sync, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(host_out4, ws + w.sync, MG_STATUS_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     return e == hipSuccess ? MG_OK : (int)e;
 }
 
-// Philox normal fill + posterior for the launch-per-layer path (same generator and element indexing as the fused tail)
+// Philox normal fill + posterior for the launch-per-layer path (same generator and element indexing as the fused tail).
+// The timestep lookup stays spelled out here (dp_posterior_at is the single-launch kernels'): this kernel reads its
+// coefficients per element, behind the noise draw, and with the shared lookup its instruction stream changes.
 __global__ void psample_tail_kernel(const float *__restrict__ x0, const float *__restrict__ x_t, const int64_t *__restrict__ t,
                                     const float *__restrict__ coef1, const float *__restrict__ coef2,
                                     const float *__restrict__ logvar, const float *__restrict__ noise,
@@ -690,9 +692,9 @@ __global__ void psample_tail_kernel(const float *__restrict__ x0, const float *_
         const float sg = tb == 0 ? 0.f : __expf(0.5f * logvar[tb]);
         float v = x0[e];
         if (x0_out && x0_out != x0) x0_out[e] = v;
-        if (clip) v = fminf(fmaxf(v, -1.f), 1.f);
+        v = dp_clip_x0(v, clip);
         const float nz = noise ? noise[e] : dp_normal(seed, off, e);
-        out[e] = fmaf(sg, nz, fmaf(coef1[tb], v, coef2[tb] * x_t[e]));
+        out[e] = dp_posterior(DpPosterior{coef1[tb], coef2[tb], sg}, v, x_t[e], nz);
     }
 }
 
@@ -704,17 +706,14 @@ static int psample_tail(const PostSample &ps, const float *x0, const float *x_t,
     const size_t per = (size_t)M * L, n = per * B;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(psample_tail_kernel, dim3(blocks), dim3(256), 0, st, x0, x_t, t, ps.coef1, ps.coef2, ps.logvar,
-                       ps.noise, ps.seed, ps.noise_stream, sync + 2, out, ps.x0_out, ps.n_steps, ps.clip, per, n);
+                       ps.noise, ps.seed, ps.noise_stream, sync + DP_SYNC_LAUNCHES, out, ps.x0_out, ps.n_steps, ps.clip, per, n);
     MG_LAUNCH_CHECK();
     if (!ps.noise) {   // the launch counter is the Philox offset: one fresh stream per call
-        hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, sync + 2);
+        hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, sync + DP_SYNC_LAUNCHES);
         MG_LAUNCH_CHECK();
     }
     return MG_OK;
 }
-
-extern "C" int mg_denoiser_cond_project(const mg_denoiser_dims *d, const float *packed, const float *cond, float *cproj, int B,
-                                        int L, void *stream);
 
 // ------------------------------------------------------------------------------------------ kernel choice
 // What the forward runs for (B, L, mode) on `cus` CUs: the public mg_fwd_plan and what the launch needs besides

@@ -167,7 +167,7 @@ extern "C" int mg_denoiser_bwd_status(const mg_denoiser_dims *d, const float *bw
 {
     if (den_check(d) != MG_OK || !bws || !host_out4 || B <= 0 || L <= 0) return MG_ERR_ARG;
     const DenBws bw = den_bws(d, B, L);
-    hipError_t e = hipMemcpyAsync(host_out4, bws + bw.sync, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(host_out4, bws + bw.sync, MG_STATUS_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     return e == hipSuccess ? MG_OK : (int)e;
 }

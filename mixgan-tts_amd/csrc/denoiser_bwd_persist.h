@@ -28,7 +28,7 @@ struct BwdPersistArgs {
     float *dx_all;           // [B][(NL+1)*C][L]: slot l receives the dx layer l produces (/sqrt2)
     float *dh_all;           // [B][NL*C][L]
     dp_u64 *gran;            // [2 parity][tiles][2 sides][512]
-    unsigned *sync;          // as in the forward: [0] ticket, [1] error (sticky), [2] launches completed, [3] done
+    unsigned *sync;          // the DP_SYNC_* words, as in the forward (one ticket queue)
     unsigned *host_err;      // pinned host word (or NULL)
     unsigned spin_limit;
     int B, L, NL, tiles_per_b;
@@ -64,11 +64,7 @@ __global__ __launch_bounds__(512, 2) void denoiser_bwd_persist_kernel(BwdPersist
     const int hh = lane >> 5, c32 = lane & 31;
     const int L = a.L, NL = a.NL;
     const int n_tiles = a.tiles_per_b * a.B;
-    if (tid == 0) {
-        s_tile = __hip_atomic_fetch_add(a.sync, 1u, DP_RLX_AGENT);   // tickets in START order
-        s_launch = __hip_atomic_load(a.sync + 2, DP_RLX_AGENT);     // advanced only after every workgroup has exited
-        s_dead = 0u;
-    }
+    dp_take_ticket(tid, a.sync, s_tile, s_launch, s_dead);
     __syncthreads();
     const int tile = (int)(s_tile % (unsigned)n_tiles);
     const unsigned launch_no = s_launch;
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(512, 2) void denoiser_bwd_persist_kernel(BwdPersist
 
     for (int l = NL - 1; l >= 0; --l) {
         const float *bp = a.blayers + (size_t)l * a.blayer_stride;
-        const unsigned epoch = launch_no * ((unsigned)NL + 1u) + (unsigned)(NL - 1 - l) + 1u;   // never repeats on a workspace
+        const unsigned epoch = DP_EPOCH(launch_no, NL, NL - 1 - l);
         const int par = l & 1;
         // saved sigmoid / tanh of this wave's channels: loaded now, used after GEMM A
         float sg[16], th[16];
@@ -235,12 +231,5 @@ __global__ __launch_bounds__(512, 2) void denoiser_bwd_persist_kernel(BwdPersist
 #pragma unroll
         for (int r = 0; r < 16; ++r) ob[(size_t)row_of(r) * L + f] = bad ? __builtin_nanf("") : dxs[r];
     }
-    if (tid == 0) {
-        const unsigned done = __hip_atomic_fetch_add(a.sync + 3, 1u, DP_RLX_AGENT);
-        if (done == (unsigned)n_tiles - 1u) {
-            __hip_atomic_store(a.sync + 3, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync, 0u, DP_RLX_AGENT);
-            __hip_atomic_fetch_add(a.sync + 2, 1u, DP_RLX_AGENT);
-        }
-    }
+    dp_retire<false>(tid, a.sync, n_tiles);
 }

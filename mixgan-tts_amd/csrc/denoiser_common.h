@@ -25,6 +25,21 @@ static inline bool den_persist_allowed(int NL, int tiles_per_b, int chain_cap)
     return !(pe && pe[0] == '0') && NL >= 3 && tiles_per_b <= chain_cap;
 }
 
+// The counter words of DenWs::sync / DenBws::sync, as the four single-launch kernels and the host name them.  All zero
+// when a workspace is first used; the last workgroup out of a launch re-arms the tickets and the done count.
+enum DpSyncWord {
+    DP_SYNC_TICKET = 0,      // ticket queue A: tiles are dealt in START order
+    DP_SYNC_ERROR = 1,       // sticky: code of a hand-off that timed out
+    DP_SYNC_LAUNCHES = 2,    // launches completed on this workspace: hand-off tags and the Philox offset derive from it
+    DP_SYNC_DONE = 3,        // workgroups of the running launch that have exited
+    DP_SYNC_TICKET_B = 16,   // ticket queue B (denoiser_persist_kernel's two roles), a cache line away from the rest
+    DP_SYNC_WORDS = 64       // what the workspace layouts reserve
+};
+static_assert(DP_SYNC_TICKET_B < DP_SYNC_WORDS, "every counter word lies inside the reserved block");
+// mg_denoiser_persist_status / mg_denoiser_bwd_status copy the block's first MG_STATUS_WORDS words as they lie
+static_assert((int)DP_SYNC_TICKET == MG_STATUS_TICKET && (int)DP_SYNC_ERROR == MG_STATUS_ERROR && (int)DP_SYNC_LAUNCHES == MG_STATUS_LAUNCHES &&
+              (int)DP_SYNC_DONE == MG_STATUS_DONE && MG_STATUS_DONE + 1 == MG_STATUS_WORDS, "one contiguous copy");
+
 // ------------------------------------------------------------------------------------------ packed blob
 struct DenLayout {
     // offsets in floats into the packed blob
@@ -199,7 +214,7 @@ static inline DenWs den_ws(const mg_denoiser_dims *d, int B, int L, int save)
     w.sig = save ? take(act * nact) : 0;
     w.tnh = save ? take(act * nact) : 0;
     w.conds = take(act);  // frame-major bf16 hi/lo planes of the conditioner (split-precision path)
-    w.sync = take(64);
+    w.sync = take(DP_SYNC_WORDS);
     w.gran = take(2 * den_persist_tiles(B, L) * 2 * C * 2);
     // [2 parities][tiles][256][18 + 16] granules when the launch is small enough for the team kernel to be considered
     w.team = take(den_persist_tiles(B, L) <= 128 && C == 256 ? 2 * den_persist_tiles(B, L) * 256 * (18 + 16) * 2 : 0);
@@ -257,7 +272,7 @@ static inline DenBws den_bws(const mg_denoiser_dims *d, int B, int L)
     w.ds = take(B * C);
     w.dm = take(B * 4 * C);
     w.da = take(B * 4 * C);
-    w.sync = take(64);
+    w.sync = take(DP_SYNC_WORDS);
     w.gran = take(2 * den_persist_tiles(B, L) * 2 * (2 * C) * 2);
     w.total = p;
     return w;

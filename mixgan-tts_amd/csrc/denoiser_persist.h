@@ -31,10 +31,11 @@
 // timeout sets the workspace's sticky error word and a host-visible one (pinned memory, mg_persist_error), the kernel
 // drains, and every workgroup that finishes with the error word set writes NaN instead of its output tile -- a failed
 // launch cannot be mistaken for a result.
-// Hand-off tags and the Philox offset derive from the launch counter kept IN the workspace (sync[2]), so a captured
+// Hand-off tags and the Philox offset derive from the launch counter kept IN the workspace (DP_SYNC_LAUNCHES), so a captured
 // graph's replays get fresh tags and fresh noise without any host-side argument changing.
 #pragma once
 #include "common.h"
+#include "denoiser_common.h"
 #include "resblock_fused.h"
 
 #define DP_SPIN_LIMIT (1u << 21)   // x ~2 us per poll: seconds, then the error word is set and the kernel drains
@@ -69,8 +70,8 @@ struct PersistArgs {
     float *x0_out;                        // optional [B, M, L]: the pre-clamp x_0 when post != 0
     dp_u64 *gran;                         // [2 parity][tiles][2 sides][256] {tag << 32 | float bits}
     dp_u64 *team;                         // denoiser_team16.h: the teams' gather buffers (same granules), or NULL
-    unsigned *sync;                       // [0] / [16] tickets, [1] error (sticky), [2] launches completed, [3] workgroups done;
-                                          // zero once at allocation: the last workgroup out re-arms [0], [16] and [3]
+    unsigned *sync;                       // the DP_SYNC_* words (denoiser_common.h): tickets, error (sticky), launches completed,
+                                          // workgroups done; zero once at allocation: dp_retire re-arms tickets and done
     unsigned *host_err;                   // pinned host word (or NULL): receives the error code at system scope
     unsigned spin_limit;                  // polls before a hand-off wait gives up (DP_SPIN_LIMIT; tests shrink it)
     // SAVE instantiation (training forward): what mg_denoiser_bwd consumes, all [B, 256, L]
@@ -231,7 +232,7 @@ __device__ __forceinline__ float dp_normal(unsigned long long seed, unsigned lon
 // and make both visible before this workgroup sends anything computed from the halo it never got.
 __device__ __forceinline__ void dp_fail(unsigned *sync, unsigned *host_err, unsigned code)
 {
-    __hip_atomic_store(sync + 1, code, DP_RLX_AGENT);
+    __hip_atomic_store(sync + DP_SYNC_ERROR, code, DP_RLX_AGENT);
     if (host_err) __hip_atomic_store(host_err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 }
@@ -240,8 +241,57 @@ __device__ __forceinline__ void dp_fail(unsigned *sync, unsigned *host_err, unsi
 __device__ __forceinline__ bool dp_failed(unsigned *sync)
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return __hip_atomic_load(sync + 1, DP_RLX_AGENT) != 0u;
+    return __hip_atomic_load(sync + DP_SYNC_ERROR, DP_RLX_AGENT) != 0u;
 }
+// Start of a workgroup: thread 0 takes the next ticket (handed out in START order), reads the launches completed on this
+// workspace (advanced only after every workgroup of a launch has exited) and clears the workgroup's timed-out flag.
+__device__ __forceinline__ void dp_take_ticket(int tid, unsigned *sync, unsigned &s_ticket, unsigned &s_launch, unsigned &s_dead)
+{
+    if (tid == 0) {
+        s_ticket = __hip_atomic_fetch_add(sync + DP_SYNC_TICKET, 1u, DP_RLX_AGENT);
+        s_launch = __hip_atomic_load(sync + DP_SYNC_LAUNCHES, DP_RLX_AGENT);
+        s_dead = 0u;
+    }
+}
+// End of a workgroup: the last of the launch's n_slots workgroups out re-arms the tickets for the next launch and counts
+// this one.  QUEUE_B: the workspace's second ticket queue is in use (the forward kernels).
+template <bool QUEUE_B>
+__device__ __forceinline__ void dp_retire(int tid, unsigned *sync, int n_slots)
+{
+    if (tid == 0) {
+        const unsigned done = __hip_atomic_fetch_add(sync + DP_SYNC_DONE, 1u, DP_RLX_AGENT);
+        if (done == (unsigned)n_slots - 1u) {
+            __hip_atomic_store(sync + DP_SYNC_DONE, 0u, DP_RLX_AGENT);
+            __hip_atomic_store(sync + DP_SYNC_TICKET, 0u, DP_RLX_AGENT);
+            if (QUEUE_B) __hip_atomic_store(sync + DP_SYNC_TICKET_B, 0u, DP_RLX_AGENT);
+            __hip_atomic_fetch_add(sync + DP_SYNC_LAUNCHES, 1u, DP_RLX_AGENT);
+        }
+    }
+}
+// Tag of hand-off `step` (0 .. NL) of launch number launch_no: never repeats on a workspace.  A macro on purpose: the
+// layer loops hoist the loop-invariant part of exactly this expression, and written as an inline function it changes the
+// instruction stream of every forward kernel (tools/isa_diff.py against the inline text).
+#define DP_EPOCH(launch_no, NL, step) ((launch_no) * ((unsigned)(NL) + 1u) + (unsigned)(step) + 1u)
+
+// p_sample's posterior (model/diffusion.py:113-129) in three pieces, so that a caller can keep the order "x_0 out, clamp,
+// select against the poison" its code was built with: the coefficients of utterance b's (clamped) timestep ...
+struct DpPosterior { float c1, c2, sg; };   // x_{t-1} = c1 clamp(x_0) + c2 x_t + sg noise;  sg = 0 at t == 0
+__device__ __forceinline__ DpPosterior dp_posterior_at(const PersistArgs &a, int b)
+{
+    long tb = (long)a.t[b];
+    tb = tb < 0 ? 0 : (tb >= a.n_steps ? a.n_steps - 1 : tb);
+    const float c1 = a.coef1[tb], c2 = a.coef2[tb];
+    const float sg = tb == 0 ? 0.f : __expf(0.5f * a.logvar[tb]);
+    return {c1, c2, sg};
+}
+// ... the clamp of the predicted x_0 ...
+__device__ __forceinline__ float dp_clip_x0(float x0, int clip)
+{
+    if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    return x0;
+}
+// ... and the sample itself from the clamped x_0, x_t and one N(0,1) draw
+__device__ __forceinline__ float dp_posterior(const DpPosterior &p, float x0, float xt, float nz) { return fmaf(p.sg, nz, fmaf(p.c1, x0, p.c2 * xt)); }
 #define DP_STAMP(k) do { if (TIMING && tid == 64 * a.dbg_wave) a.dbg[((size_t)tile * (a.NL + 2) + stamp_row) * 12 + (k)] = clock64(); } while (0)
 
 // A reading step's conditioner projections (PersistArgs.cproj) come through LDS: wave w fetches the NT columns of its own
@@ -323,15 +373,15 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
     if (tid == 0) {
         const int nA = (TWO_PER_CU && (a.flags & DP_F_ROLES)) ? (a.B / 2) * a.tiles_per_b : n_tiles;   // queue 0: tiles [0, nA)
         const int n_mine = role == 0 ? nA : n_tiles - nA;
-        unsigned tk = __hip_atomic_fetch_add(a.sync + (role ? 16 : 0), 1u, DP_RLX_AGENT);   // tickets in START order
+        unsigned tk = __hip_atomic_fetch_add(a.sync + (role ? DP_SYNC_TICKET_B : DP_SYNC_TICKET), 1u, DP_RLX_AGENT);   // tickets in START order
         int tl;
         if ((int)tk < n_mine) tl = (role == 0 ? 0 : nA) + (int)tk;
         else {   // this role's queue is empty: the other one has exactly as many tiles left as such workgroups
-            tk = __hip_atomic_fetch_add(a.sync + (role ? 0 : 16), 1u, DP_RLX_AGENT);
+            tk = __hip_atomic_fetch_add(a.sync + (role ? DP_SYNC_TICKET : DP_SYNC_TICKET_B), 1u, DP_RLX_AGENT);
             tl = (role == 0 ? nA : 0) + (int)tk;
         }
         s_tile = (unsigned)tl;
-        s_launch = __hip_atomic_load(a.sync + 2, DP_RLX_AGENT);      // advanced only after every workgroup has exited
+        s_launch = __hip_atomic_load(a.sync + DP_SYNC_LAUNCHES, DP_RLX_AGENT);   // advanced only after every workgroup has exited
         s_dead = 0u;
     }
     __syncthreads();
@@ -422,7 +472,6 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) st[i][j][r] = fmaxf(acc[i][j][r], 0.f);
     }
-    (void)0;
     DP_STAMP(1);
     bool fvalid[NNB];   // this lane's frame of n-block j exists
     const size_t bbase = (size_t)b * RB_C * L;
@@ -449,7 +498,7 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
         const size_t vrows = a.vec_rows ? (size_t)a.vec_rows : (size_t)Bp;
         const float *hv = (second ? a.hvec2 : a.hvec) + ((size_t)l * vrows + b) * RB_C;
         const float *dv = (second ? a.dvec2 : a.dvec) + ((size_t)l * vrows + b) * RB_C;
-        const unsigned epoch = launch_no * ((unsigned)a.NL + 1u) + (unsigned)l + 1u;   // never repeats on a workspace
+        const unsigned epoch = DP_EPOCH(launch_no, a.NL, l);
         const int par = l & 1;
         stamp_row = l + 1;
         DP_STAMP(0);
@@ -759,10 +808,7 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
             }
         } else {
             // p_sample tail (model/diffusion.py:113-129): clamp, posterior mean, + sigma * noise unless t == 0
-            long tb = (long)a.t[b];
-            tb = tb < 0 ? 0 : (tb >= a.n_steps ? a.n_steps - 1 : tb);
-            const float c1 = a.coef1[tb], c2 = a.coef2[tb];
-            const float sg = tb == 0 ? 0.f : __expf(0.5f * a.logvar[tb]);
+            const DpPosterior ps = dp_posterior_at(a, b);
             const unsigned long long seed = a.seed, off = (a.noise_stream << 32) | (unsigned long long)launch_no;
             const int fc = min(f, L - 1);
             float xt[16], nz[16];
@@ -780,21 +826,13 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
                     const size_t e = bo + (size_t)row * L + f;
                     float x0 = o[0][0][r];
                     if (a.x0_out) a.x0_out[e] = x0;
-                    if (a.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                    a.out[e] = bad ? poison : fmaf(sg, nz[r], fmaf(c1, x0, c2 * xt[r]));
+                    x0 = dp_clip_x0(x0, a.clip);
+                    a.out[e] = bad ? poison : dp_posterior(ps, x0, xt[r], nz[r]);
                 }
             }
         }
     }
     DP_STAMP(1);
     // ---------------------------------------------------------------- last workgroup out re-arms the tickets for the next launch
-    if (tid == 0) {
-        const unsigned done = __hip_atomic_fetch_add(a.sync + 3, 1u, DP_RLX_AGENT);
-        if (done == (unsigned)n_tiles - 1u) {
-            __hip_atomic_store(a.sync + 3, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync + 16, 0u, DP_RLX_AGENT);
-            __hip_atomic_fetch_add(a.sync + 2, 1u, DP_RLX_AGENT);
-        }
-    }
+    dp_retire<true>(tid, a.sync, n_tiles);
 }

@@ -71,6 +71,42 @@ __device__ __forceinline__ void d16_store_block(float *T, int ch0, int col, int 
     for (int r = 0; r < 4; ++r) base[4 * r] = val(r);
 }
 
+// Rows 16 rb + 4 g .. + 3 of frame f (column of this lane; fvalid: f < L) of the output projection `o` to memory: the
+// predicted x_0, or (a.post) the p_sample tail (model/diffusion.py:113-129) of it.  A hand-off timed out somewhere in this
+// launch (or an earlier one on this workspace): NaN instead -- no tile may look like a result.
+__device__ __forceinline__ void d16_emit(const PersistArgs &a, const f32x4 &o, int rb, int g, int b, int f, bool fvalid,
+                                         unsigned launch_no)
+{
+    const int L = a.L;
+    const size_t bo = (size_t)b * a.M * L;
+    const bool bad = dp_failed(a.sync);
+    const float poison = __builtin_nanf("");
+    if (!a.post) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * rb + 4 * g + r;
+            if (row < a.M && fvalid) a.out[bo + (size_t)row * L + f] = bad ? poison : o[r];
+        }
+    } else {
+        const DpPosterior ps = dp_posterior_at(a, b);
+        const unsigned long long seed = a.seed, off = (a.noise_stream << 32) | (unsigned long long)launch_no;
+        const int fc = min(f, L - 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * rb + 4 * g + r;
+            const size_t e = bo + (size_t)min(row, a.M - 1) * L + fc;
+            const float xt = a.x_t[e];
+            const float nz = a.noise ? a.noise[e] : dp_normal(seed, off, e);
+            if (row < a.M && fvalid) {
+                float x0 = o[r];
+                if (a.x0_out) a.x0_out[e] = x0;
+                x0 = dp_clip_x0(x0, a.clip);
+                a.out[e] = bad ? poison : dp_posterior(ps, x0, xt, nz);
+            }
+        }
+    }
+}
+
 // SOLO: built for one workgroup per CU (one wave per SIMD, up to 512 registers: 298 used, nothing spilled) -- for launches of
 // at most one tile per CU whose utterances' chains fit in a quarter of those slots; otherwise the two-per-CU build.
 template <bool VEC4, bool SOLO = false>
@@ -86,11 +122,7 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void denoiser_persist16_kernel(P
     const int g = lane >> 4, c16 = lane & 15;
     const int L = a.L;
     const int n_tiles = a.tiles_per_b * a.B;
-    if (tid == 0) {
-        s_tile = __hip_atomic_fetch_add(a.sync, 1u, DP_RLX_AGENT);   // tickets in START order
-        s_launch = __hip_atomic_load(a.sync + 2, DP_RLX_AGENT);
-        s_dead = 0u;
-    }
+    dp_take_ticket(tid, a.sync, s_tile, s_launch, s_dead);
     __syncthreads();
     const int tile = (int)(s_tile % (unsigned)n_tiles);
     const unsigned launch_no = s_launch;   // launches completed on this workspace: hand-off tags and the noise offset
@@ -176,7 +208,7 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void denoiser_persist16_kernel(P
         const size_t vrows = a.vec_rows ? (size_t)a.vec_rows : (size_t)a.B;
         const float *hv = a.hvec + ((size_t)l * vrows + b) * RB_C;
         const float *dv = a.dvec + ((size_t)l * vrows + b) * RB_C;
-        const unsigned epoch = launch_no * ((unsigned)a.NL + 1u) + (unsigned)l + 1u;
+        const unsigned epoch = DP_EPOCH(launch_no, a.NL, l);
         const int par = l & 1;
 
         // ------------------------------------------------------------ GEMM 1: h = Wc cond + bc + x + (Wd s [+ Wp spk])
@@ -346,44 +378,7 @@ __global__ __launch_bounds__(256, SOLO ? 1 : 2) void denoiser_persist16_kernel(P
         }
         const f32x4 *const ap[1] = {blk(a.out_w, rb, 32)};
         d16_mfma_loop<1, NC, D16IterK1>(o, ap, condT + c16 * 16 + g * 4);
-        const size_t bo = (size_t)b * a.M * L;
-        const bool bad = dp_failed(a.sync);   // a hand-off timed out: no tile of this launch may look like a result
-        const float poison = __builtin_nanf("");
-        if (!a.post) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * rb + 4 * g + r;
-                if (row < a.M && fvalid) a.out[bo + (size_t)row * L + f] = bad ? poison : o[0][r];
-            }
-        } else {   // p_sample tail (model/diffusion.py:113-129)
-            long tb = (long)a.t[b];
-            tb = tb < 0 ? 0 : (tb >= a.n_steps ? a.n_steps - 1 : tb);
-            const float c1 = a.coef1[tb], c2 = a.coef2[tb];
-            const float sg = tb == 0 ? 0.f : __expf(0.5f * a.logvar[tb]);
-            const unsigned long long seed = a.seed, off = (a.noise_stream << 32) | (unsigned long long)launch_no;
-            const int fc = min(f, L - 1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * rb + 4 * g + r;
-                const size_t e = bo + (size_t)min(row, a.M - 1) * L + fc;
-                const float xt = a.x_t[e];
-                const float nz = a.noise ? a.noise[e] : dp_normal(seed, off, e);
-                if (row < a.M && fvalid) {
-                    float x0 = o[0][r];
-                    if (a.x0_out) a.x0_out[e] = x0;
-                    if (a.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                    a.out[e] = bad ? poison : fmaf(sg, nz, fmaf(c1, x0, c2 * xt));
-                }
-            }
-        }
+        d16_emit(a, o[0], rb, g, b, f, fvalid, launch_no);
     }
-    if (tid == 0) {
-        const unsigned done = __hip_atomic_fetch_add(a.sync + 3, 1u, DP_RLX_AGENT);
-        if (done == (unsigned)n_tiles - 1u) {
-            __hip_atomic_store(a.sync + 3, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync + 16, 0u, DP_RLX_AGENT);
-            __hip_atomic_fetch_add(a.sync + 2, 1u, DP_RLX_AGENT);
-        }
-    }
+    dp_retire<true>(tid, a.sync, n_tiles);
 }

@@ -137,11 +137,7 @@ __global__ __launch_bounds__(1024 / TEAM, TEAM == 4 ? 1 : 2) void denoiser_team1
     const int L = a.L;
     const int n_tiles = a.tiles_per_b * a.B;
     const int n_slots = n_tiles * TEAM;
-    if (tid == 0) {
-        s_slot = __hip_atomic_fetch_add(a.sync, 1u, DP_RLX_AGENT);   // tickets in START order
-        s_launch = __hip_atomic_load(a.sync + 2, DP_RLX_AGENT);
-        s_dead = 0u;
-    }
+    dp_take_ticket(tid, a.sync, s_slot, s_launch, s_dead);
     __syncthreads();
     // ticket -> (tile, member).  Consecutive workgroups go to consecutive XCDs (8 of them): the members of a tile are
     // tickets t, t+8, ... of a run of 8 * TEAM, so that a team shares one XCD when dispatch follows ticket order.
@@ -248,7 +244,7 @@ __global__ __launch_bounds__(1024 / TEAM, TEAM == 4 ? 1 : 2) void denoiser_team1
         const size_t vrows = a.vec_rows ? (size_t)a.vec_rows : (size_t)a.B;
         const float *hv = a.hvec + ((size_t)l * vrows + b) * RB_C;
         const float *dv = a.dvec + ((size_t)l * vrows + b) * RB_C;
-        const unsigned epoch = launch_no * ((unsigned)a.NL + 1u) + (unsigned)l + 1u;
+        const unsigned epoch = DP_EPOCH(launch_no, a.NL, l);
         const int par = l & 1;
 
         // ------------------------------------------------------------ GEMM 1: h = Wc cond + bc + x + (Wd s [+ Wp spk])
@@ -345,7 +341,7 @@ __global__ __launch_bounds__(1024 / TEAM, TEAM == 4 ? 1 : 2) void denoiser_team1
     }
 
     // ---------------------------------------------------------------- tail: sum(skip)/sqrt(NL) -> skip_projection -> ReLU -> output_projection
-    const unsigned epochT = launch_no * ((unsigned)a.NL + 1u) + (unsigned)a.NL + 1u;   // one tag for both tail exchanges
+    const unsigned epochT = DP_EPOCH(launch_no, a.NL, a.NL);   // one tag for both tail exchanges
     const int parT = a.NL & 1;
     {
         dp_gu64 *mine = Gbuf + (size_t)parT * g_par + (size_t)tile * RB_C * NG;
@@ -388,44 +384,7 @@ __global__ __launch_bounds__(1024 / TEAM, TEAM == 4 ? 1 : 2) void denoiser_team1
         const f32x4 *const ap[1] = {blk(a.out_w, rb, 32)};
         d16_preload<1, D16IterK1>(ringA, ap);
         d16_mfma_loop_deep<1, NH, D16IterK1>(o, ap, hT + (1 + c16) * 16 + g * 4, ringA);
-        const size_t bo = (size_t)b * a.M * L;
-        const bool bad = dp_failed(a.sync);   // a hand-off timed out: no tile of this launch may look like a result
-        const float poison = __builtin_nanf("");
-        if (!a.post) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * rb + 4 * g + r;
-                if (row < a.M && fvalid) a.out[bo + (size_t)row * L + f] = bad ? poison : o[0][r];
-            }
-        } else {   // p_sample tail (model/diffusion.py:113-129)
-            long tb = (long)a.t[b];
-            tb = tb < 0 ? 0 : (tb >= a.n_steps ? a.n_steps - 1 : tb);
-            const float c1 = a.coef1[tb], c2 = a.coef2[tb];
-            const float sg = tb == 0 ? 0.f : __expf(0.5f * a.logvar[tb]);
-            const unsigned long long seed = a.seed, off = (a.noise_stream << 32) | (unsigned long long)launch_no;
-            const int fc = min(f, L - 1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * rb + 4 * g + r;
-                const size_t e = bo + (size_t)min(row, a.M - 1) * L + fc;
-                const float xt = a.x_t[e];
-                const float nz = a.noise ? a.noise[e] : dp_normal(seed, off, e);
-                if (row < a.M && fvalid) {
-                    float x0 = o[0][r];
-                    if (a.x0_out) a.x0_out[e] = x0;
-                    if (a.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-                    a.out[e] = bad ? poison : fmaf(sg, nz, fmaf(c1, x0, c2 * xt));
-                }
-            }
-        }
+        d16_emit(a, o[0], rb, g, b, f, fvalid, launch_no);
     }
-    if (tid == 0) {   // last workgroup out re-arms the tickets for the next launch
-        const unsigned done = __hip_atomic_fetch_add(a.sync + 3, 1u, DP_RLX_AGENT);
-        if (done == (unsigned)n_slots - 1u) {
-            __hip_atomic_store(a.sync + 3, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync, 0u, DP_RLX_AGENT);
-            __hip_atomic_store(a.sync + 16, 0u, DP_RLX_AGENT);
-            __hip_atomic_fetch_add(a.sync + 2, 1u, DP_RLX_AGENT);
-        }
-    }
+    dp_retire<true>(tid, a.sync, n_slots);
 }

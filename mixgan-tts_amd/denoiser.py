@@ -75,6 +75,12 @@ def _cached(cache, key, limit, make, reusable=lambda v: True):
     return v
 
 
+def _status_dict(host):
+    """The MG_STATUS_* words of a status export by name."""
+    return {"ticket": host[_lib.MG_STATUS_TICKET], "error": host[_lib.MG_STATUS_ERROR],
+            "launches": host[_lib.MG_STATUS_LAUNCHES], "done": host[_lib.MG_STATUS_DONE]}
+
+
 def raise_if_failed(owners=(), sync=False):
     """The single-launch kernels' failure word (include/mixgan_hip.h, mg_persist_error).  Polling it is a host memory
     read; sync=True first waits for the current stream, which makes the answer exact for everything launched so far.
@@ -359,9 +365,9 @@ class Denoiser(nn.Module):
         """{ticket, error, launches, done} of the single-launch forward's counters for this shape (synchronises);
         error != 0: a neighbour hand-off timed out and that launch's output is invalid."""
         ws = self._workspace(B, L, False, next(self.parameters()).device) if ws is None else ws
-        host = (ctypes.c_uint * 4)()
+        host = (ctypes.c_uint * _lib.MG_STATUS_WORDS)()
         check(_lib.lib().mg_denoiser_persist_status(ctypes.byref(self._dims), fptr(ws), B, L, host, stream_ptr()))
-        return {"ticket": host[0], "error": host[1], "launches": host[2], "done": host[3]}
+        return _status_dict(host)
 
     def backward_status(self, B, L):
         """{ticket, error, launches, done} of the single-launch data-gradient kernel's counters in the cached backward
@@ -370,10 +376,10 @@ class Denoiser(nn.Module):
         All zero when no backward workspace of this shape is cached (none has run, or the cache evicted it)."""
         dev = next(self.parameters()).device
         bws = self._bws.get((B, L, dev, torch.cuda.current_stream(dev).cuda_stream))
-        host = (ctypes.c_uint * 4)()
+        host = (ctypes.c_uint * _lib.MG_STATUS_WORDS)()
         if bws is not None:
             check(_lib.lib().mg_denoiser_bwd_status(ctypes.byref(self._dims), fptr(bws), B, L, host, stream_ptr()))
-        return {"ticket": host[0], "error": host[1], "launches": host[2], "done": host[3]}
+        return _status_dict(host)
 
     def forward(self, mel, diffusion_step, conditioner, speaker_emb, mask=None):
         """mel [B,1,M,T], diffusion_step [B], conditioner [B,H,T], speaker_emb [B,H]|None -> [B,1,M,T]."""
