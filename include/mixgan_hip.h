@@ -465,6 +465,39 @@ int mg_stft_mel(const float *x, long x_bs, const int *lengths, int B, int L, int
 int mg_istft(const float *mag, const float *phase, long s_bs, long s_ks, long s_ts, int B, int T, int hop,
              const float *window, const double *wsq, const float *twiddle, float *out, int tile, void *stream);
 
+/* ------------------------------------------------------------------ vocoder training (vocoder.py forward_train,
+ * audio.py mel_spectrogram_diff; csrc/vocoder_train.hip).  Every result is reproducible run to run. */
+/* dw[co,ci,k] (+)= alpha * sum_{b,l} dy[b,co,l] * lrelu(x[b,ci, l + k*dil - pad], in_slope), x out of range = 0:
+ * the weight gradient of mg_conv1d_fwd_ex through the saved PRE-activation x (in_slope = 1: identity).
+ * K in {3,7,11}, 1 <= dil <= 5, Ldy = Lx + 2 pad - dil (K-1); batch strides in floats (0 = dense); scratch of
+ * mg_conv1d_wgrad_scratch_floats(Co, Ci, K) floats.  The bias gradient is mg_rowsum of dy. */
+int mg_conv1d_wgrad_ex(const float *dy, long dy_bs, const float *x, long x_bs, float *dw, float *scratch, int B, int Co,
+                       int Ci, int Ldy, int Lx, int K, int dil, int pad, float in_slope, float alpha, int accumulate,
+                       void *stream);
+/* out[i] = dy[i] * (x[i] > 0 ? 1 : slope) (+ add[i]): a leaky ReLU's backward through its saved input, with the
+ * residual branch's gradient added (add may be NULL; out may be dy or add). */
+int mg_lrelu_bwd(const float *dy, const float *x, const float *add, float *out, float slope, size_t n, void *stream);
+/* Backward of y = alpha * convT(lrelu(x, in_slope), w, stride u, padding u/2) (mg_conv_transpose1d_fwd), w [Ci, Co, 2u],
+ * x [B, Ci, L], dy [B, Co, u L], u in {2,4,8}; out-of-range dy is 0.
+ *   dgrad: dx[b,ci,l] = (x > 0 ? 1 : in_slope) * alpha * sum_{co,k} w[ci,co,k] dy[b,co, u l + k - u/2], dy read as u
+ *          phases of length L: a 3-tap implicit GEMM with Ci rows over Co*u channels.  w is the plain weight.
+ *   wgrad: dw[ci,co,k] (+)= alpha * sum_{b,l} lrelu(x[b,ci,l], in_slope) dy[b,co, u l + k - u/2]. */
+size_t mg_conv_transpose1d_dgrad_workspace_floats(int B, int Ci, int L, int Co, int u);
+int mg_conv_transpose1d_dgrad(const float *dy, const float *w, const float *x, float *dx, float *workspace,
+                              size_t workspace_floats, int B, int Ci, int L, int Co, int u, float in_slope, float alpha,
+                              void *stream);
+size_t mg_conv_transpose1d_wgrad_scratch_floats(int Ci, int Co, int u);
+int mg_conv_transpose1d_wgrad(const float *dy, const float *x, float *dw, float *scratch, int B, int Ci, int L, int Co,
+                              int u, float in_slope, float alpha, int accumulate, void *stream);
+/* Gradient of mg_stft_mel's mel with respect to the signal: dx [B, L] (batch stride dx_bs) from dmel [B, n_mels, T].
+ * lengths must be NULL (MG_ERR_SHAPE otherwise); energy is not differentiated.  Frames whose mel sum is under the 1e-5
+ * clamp and bins with |X| = 0 contribute 0.  Two passes: windowed frame gradients into the workspace, then a gather
+ * that overlap-adds them in ascending frame order and folds the reflect padding back. */
+size_t mg_stft_mel_bwd_workspace_bytes(int B, int T);
+int mg_stft_mel_bwd(const float *x, long x_bs, const int *lengths, int B, int L, int hop, const float *window,
+                    const float *twiddle, const int *band, const float *band_w, int n_mels, const float *dmel, int T,
+                    float *dx, long dx_bs, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Step-embedding MLP: out = W2 mish(W0 [sin|cos](t * freq)).  Denoiser: model/modules.py:398-403,434;
  * JCUDiscriminator: model/mixgantts.py:203-208,265.  emb [B,D0], pre/h [B,D1] are saved for backward. */
 int mg_step_mlp_fwd(const int64_t *t, const float *freq, const float *W0, const float *W2, float *emb,

@@ -229,6 +229,14 @@ def _signatures():
         "mg_mel_cepstra": (i, [vp, vp, i, i, i, i, vp, vp]),
         "mg_dtw_workspace_bytes": (sz, [i, i, i]),
         "mg_dtw": (i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]),
+        "mg_conv1d_wgrad_ex": (i, [vp, lg, vp, lg, vp, vp, i, i, i, i, i, i, i, i, f, f, i, vp]),
+        "mg_lrelu_bwd": (i, [vp, vp, vp, vp, f, sz, vp]),
+        "mg_conv_transpose1d_dgrad_workspace_floats": (sz, [i, i, i, i, i]),
+        "mg_conv_transpose1d_dgrad": (i, [vp, vp, vp, vp, vp, sz, i, i, i, i, i, f, f, vp]),
+        "mg_conv_transpose1d_wgrad_scratch_floats": (sz, [i, i, i]),
+        "mg_conv_transpose1d_wgrad": (i, [vp, vp, vp, vp, i, i, i, i, i, f, f, i, vp]),
+        "mg_stft_mel_bwd_workspace_bytes": (sz, [i, i]),
+        "mg_stft_mel_bwd": (i, [vp, lg, vp, i, i, i, vp, vp, vp, vp, i, vp, i, vp, lg, vp, sz, vp]),
     }
 
 

@@ -337,6 +337,19 @@ class TacotronSTFT(nn.Module):
                                      fptr(mel), fptr(energy), T, stream_ptr()))
         return mel, energy
 
+    def mel_spectrogram_diff(self, y):
+        """y [B, N] -> log-mel [B, n_mels, 1 + N // hop] with autograd to y (mg_stft_mel / mg_stft_mel_bwd): HiFi-GAN's
+        mel-reconstruction term.  The value is mel_spectrogram's, bit for bit.  No `lengths`, no energy, and no range
+        check of y (a generator's tanh output is inside [-1, 1]; the check is a host read), so nothing here syncs."""
+        from .autograd import mel_diff
+        return mel_diff(self.stft_fn._signal(y), self)
+
+    def _mel_args(self, x):
+        """(hop, window, twiddle, band, band_w) on x's device, as the two mel kernels take them."""
+        win, _, tw = self.stft_fn._tables.on(x.device)
+        band, band_w = self._bands(x.device)
+        return self.stft_fn.hop_length, win, tw, band, band_w
+
 
 # ---------------------------------------------------------------------------------------------
 # Griffin-Lim and the tools

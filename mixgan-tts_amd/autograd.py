@@ -378,3 +378,157 @@ class _BatchNormActFn(torch.autograd.Function):
 
 def batchnorm_act(x, gamma, beta, keep, drop_scale, act, eps, group=None):
     return _BatchNormActFn.apply(x, gamma, beta, keep, drop_scale, act, eps, group)
+
+
+# --------------------------------------------------------------------------------------------------
+# Differentiable log-mel (audio.TacotronSTFT.mel_spectrogram_diff) and the HiFi-GAN generator's training ops
+# (vocoder.Generator.forward_train).  The HIP side differentiates with respect to the EFFECTIVE weight; weight norm is
+# a torch expression in front of these functions.
+# --------------------------------------------------------------------------------------------------
+class _MelDiffFn(torch.autograd.Function):
+    """log-mel of x [B, N] (mg_stft_mel); the gradient recomputes each frame's spectrum (mg_stft_mel_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, stft):
+        _require_cuda(x)
+        B, L = x.shape
+        hop, win, tw, band, band_w = stft._mel_args(x)
+        T = 1 + L // hop
+        mel = torch.empty(B, stft.n_mel_channels, T, device=x.device, dtype=torch.float32)
+        energy = torch.empty(B, T, device=x.device, dtype=torch.float32)
+        _lib.check(_lib.lib().mg_stft_mel(_lib.fptr(x), L, None, B, L, hop, _lib.fptr(win), _lib.fptr(tw),
+                                          _lib.iptr(band, torch.int32), _lib.fptr(band_w), stft.n_mel_channels,
+                                          _lib.fptr(mel), _lib.fptr(energy), T, _lib.stream_ptr()))
+        ctx.save_for_backward(x)
+        ctx.stft = stft
+        return mel
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        stft = ctx.stft
+        B, L = x.shape
+        hop, win, tw, band, band_w = stft._mel_args(x)
+        T = g.shape[2]
+        g = g.contiguous()
+        L_ = _lib.lib()
+        nbytes = L_.mg_stft_mel_bwd_workspace_bytes(B, T)
+        ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x)
+        _lib.check(L_.mg_stft_mel_bwd(_lib.fptr(x), L, None, B, L, hop, _lib.fptr(win), _lib.fptr(tw),
+                                      _lib.iptr(band, torch.int32), _lib.fptr(band_w), stft.n_mel_channels, _lib.fptr(g),
+                                      T, _lib.fptr(dx), L, _lib.fptr(ws), nbytes, _lib.stream_ptr()))
+        return dx, None
+
+
+def mel_diff(x, stft):
+    return _MelDiffFn.apply(x, stft)
+
+
+def _voc_dgrad(g, w, K, dil, pad, alpha, Lin):
+    """Data gradient of alpha * conv1d(., w [Co,Ci,K], dilation dil, padding pad): the forward kernel on the transposed,
+    tap-flipped pack with pad' = dil (K-1) - pad."""
+    Ci = w.shape[1]
+    return ops.conv1d_packed(g, ops.pack_conv_weight(w, ops.PACK_DGRAD), None, Ci, K, 1, dil * (K - 1) - pad,
+                             alpha=alpha, Lout=Lin, dilation=dil)
+
+
+class _VocConvFn(torch.autograd.Function):
+    """y = act(alpha * conv1d(leaky_relu(x, in_slope), w, dilation, padding) + b), act None or "tanh" (conv_pre and
+    conv_post).  Saves x, w (and y for tanh)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, dil, pad, in_slope, alpha, act):
+        Co, Ci, K = w.shape
+        y = ops.conv1d_packed(x, ops.pack_conv_weight(w, ops.PACK_PLAIN), b, Co, K, 1, pad, act=act, alpha=alpha,
+                              dilation=dil, in_slope=in_slope)
+        ctx.save_for_backward(x, w, y if act else None)
+        ctx.cfg = (dil, pad, in_slope, alpha, act)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, y = ctx.saved_tensors
+        dil, pad, in_slope, alpha, act = ctx.cfg
+        K = w.shape[2]
+        g = g.contiguous()
+        if act:
+            g = ops.act_bwd(g, y, act)
+        need = ctx.needs_input_grad
+        dw = ops.conv1d_wgrad_ex(g, x, K, dil, pad, in_slope, alpha) if need[1] else None
+        db = ops.rowsum(g) if need[2] else None
+        dx = None
+        if need[0]:
+            dx = _voc_dgrad(g, w, K, dil, pad, alpha, x.shape[2])
+            if in_slope != 1.0:
+                ops.lrelu_bwd(dx, x, in_slope, out=dx)
+        return dx, dw, db, None, None, None, None, None
+
+
+class _VocPairFn(torch.autograd.Function):
+    """One (convs1[m], convs2[m]) pair of a ResBlock: t = conv1(lrelu(r)) + b1, out = conv2(lrelu(t)) + b2 + r.
+    Saves the two PRE-activations r and t; both leaky ReLUs are applied while the kernels stage their input."""
+
+    @staticmethod
+    def forward(ctx, r, w1, b1, w2, b2, dil, slope):
+        C, _, K = w1.shape
+        t = ops.conv1d_packed(r, ops.pack_conv_weight(w1, ops.PACK_PLAIN), b1, C, K, 1, (K * dil - dil) // 2,
+                              dilation=dil, in_slope=slope)
+        out = ops.conv1d_packed(t, ops.pack_conv_weight(w2, ops.PACK_PLAIN), b2, C, K, 1, (K - 1) // 2, add=r,
+                                in_slope=slope)
+        ctx.save_for_backward(r, t, w1, w2)
+        ctx.cfg = (dil, slope)
+        ctx.mark_non_differentiable(t)
+        return out, t
+
+    @staticmethod
+    def backward(ctx, g, _gt):
+        r, t, w1, w2 = ctx.saved_tensors
+        dil, slope = ctx.cfg
+        K = w1.shape[2]
+        p1, p2 = (K * dil - dil) // 2, (K - 1) // 2
+        L = r.shape[2]
+        g = g.contiguous()
+        dw2 = ops.conv1d_wgrad_ex(g, t, K, 1, p2, slope)
+        db2 = ops.rowsum(g)
+        dt = _voc_dgrad(g, w2, K, 1, p2, 1.0, L)
+        ops.lrelu_bwd(dt, t, slope, out=dt)
+        dw1 = ops.conv1d_wgrad_ex(dt, r, K, dil, p1, slope)
+        db1 = ops.rowsum(dt)
+        dr = _voc_dgrad(dt, w1, K, dil, p1, 1.0, L)
+        ops.lrelu_bwd(dr, r, slope, add=g, out=dr)      # the mask and the residual branch's gradient in one pass
+        return dr, dw1, db1, dw2, db2, None, None
+
+
+class _VocUpFn(torch.autograd.Function):
+    """y = alpha * conv_transpose1d(leaky_relu(x, slope), w [Ci,Co,2u], stride u, padding u/2) + b, polyphase."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, u, slope, alpha):
+        Co = w.shape[1]
+        y = ops.conv_transpose1d_packed(x, ops.pack_conv_transpose_weight(w), b, Co, u, in_slope=slope, alpha=alpha)
+        ctx.save_for_backward(x, w)
+        ctx.cfg = (u, slope, alpha)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        u, slope, alpha = ctx.cfg
+        g = g.contiguous()
+        dw = ops.conv_transpose1d_wgrad(g, x, w.shape[1], u, slope, alpha)
+        db = ops.rowsum(g)
+        dx = ops.conv_transpose1d_dgrad(g, w, x, slope, alpha)
+        return dx, dw, db, None, None, None
+
+
+def voc_conv(x, w, b, dil, pad, in_slope=1.0, alpha=1.0, act=None):
+    return _VocConvFn.apply(x, w.contiguous(), b, dil, pad, in_slope, alpha, act)
+
+
+def voc_pair(r, w1, b1, w2, b2, dil, slope):
+    return _VocPairFn.apply(r, w1.contiguous(), b1, w2.contiguous(), b2, dil, slope)
+
+
+def voc_up(x, w, b, u, slope, alpha):
+    return _VocUpFn.apply(x, w.contiguous(), b, u, slope, alpha)

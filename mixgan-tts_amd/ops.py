@@ -203,6 +203,58 @@ def rowsum(x, per_batch=False, alpha=1.0):
     return out
 
 
+def conv1d_wgrad_ex(dy, x, K, dilation=1, padding=0, in_slope=1.0, alpha=1.0, out=None, accumulate=False):
+    """dW [Co, Ci, K] of alpha * conv1d(leaky_relu(x, in_slope), W, dilation, padding) through the saved
+    pre-activation x [B,Ci,Lx]; dy [B,Co,Ldy].  accumulate adds into `out`."""
+    L = _lib.lib()
+    B, Co, Ldy = dy.shape
+    _, Ci, Lx = x.shape
+    dw = out if out is not None else torch.empty(Co, Ci, K, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(L.mg_conv1d_wgrad_scratch_floats(Co, Ci, K), device=x.device, dtype=torch.float32)
+    check(L.mg_conv1d_wgrad_ex(fptr(dy), 0, fptr(x), 0, fptr(dw), fptr(scratch), B, Co, Ci, Ldy, Lx, K, dilation, padding,
+                               float(in_slope), float(alpha), int(accumulate), stream_ptr()))
+    return dw
+
+
+def lrelu_bwd(dy, x, slope, add=None, out=None):
+    """dy * (x > 0 ? 1 : slope) (+ add): leaky ReLU backward through its saved input, residual gradient added."""
+    L = _lib.lib()
+    if out is None:
+        out = torch.empty_like(dy)
+    check(L.mg_lrelu_bwd(fptr(dy), fptr(x), fptr(add, True), fptr(out), float(slope), dy.numel(), stream_ptr()))
+    return out
+
+
+def conv_transpose1d_dgrad(dy, w, x, in_slope=1.0, alpha=1.0):
+    """dx of alpha * conv_transpose1d(leaky_relu(x, in_slope), w [Ci,Co,2u], stride u, padding u/2); dy [B,Co,u*L]."""
+    L = _lib.lib()
+    B, Ci, Lin = x.shape
+    _, Co, K = w.shape
+    u = K // 2
+    n = L.mg_conv_transpose1d_dgrad_workspace_floats(B, Ci, Lin, Co, u) if K == 2 * u else 0
+    if n == 0:
+        raise _lib.MixganHipError("unsupported transposed-conv weight shape %s" % (tuple(w.shape),))
+    ws = torch.empty(n, device=x.device, dtype=torch.float32)
+    dx = torch.empty_like(x)
+    check(L.mg_conv_transpose1d_dgrad(fptr(dy), fptr(w), fptr(x), fptr(dx), fptr(ws), n, B, Ci, Lin, Co, u,
+                                      float(in_slope), float(alpha), stream_ptr()))
+    return dx
+
+
+def conv_transpose1d_wgrad(dy, x, Co, u, in_slope=1.0, alpha=1.0, out=None, accumulate=False):
+    """dW [Ci, Co, 2u] of alpha * conv_transpose1d(leaky_relu(x, in_slope), W, stride u, padding u/2)."""
+    L = _lib.lib()
+    B, Ci, Lin = x.shape
+    n = L.mg_conv_transpose1d_wgrad_scratch_floats(Ci, Co, u)
+    if n == 0:
+        raise _lib.MixganHipError("unsupported transposed-conv shape Ci=%d Co=%d u=%d" % (Ci, Co, u))
+    dw = out if out is not None else torch.empty(Ci, Co, 2 * u, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(n, device=x.device, dtype=torch.float32)
+    check(L.mg_conv_transpose1d_wgrad(fptr(dy), fptr(x), fptr(dw), fptr(scratch), B, Ci, Lin, Co, u, float(in_slope),
+                                      float(alpha), int(accumulate), stream_ptr()))
+    return dw
+
+
 def act_bwd(dy, y, act):
     L = _lib.lib()
     out = torch.empty_like(dy)

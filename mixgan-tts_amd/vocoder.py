@@ -12,7 +12,11 @@ add in the epilogue; ConvTranspose1d (k = 2*stride) is a polyphase 3-tap GEMM ov
 fused in staging, phases interleaved by the epilogue; other (k, stride) fall back to zero insertion plus a
 stride-1 convolution on the transposed, tap-flipped pack); the three ResBlocks of a stage accumulate into
 one buffer and the 1/3 is folded into the next convolution (leaky ReLU is positively homogeneous).
-Inference only (the vocoder is not trained on this path).
+
+`forward` is the inference path (no_grad, post-activations fused into epilogues).  `forward_train` is the same
+function as an autograd tensor: every convolution keeps its pre-activation input and differentiates on the HIP side
+(csrc/vocoder_train.hip through autograd.py; weight norm stays a torch expression).  vocoder_train.GeneratorTrainer
+puts HiFi-GAN's mel-reconstruction loss on it; the MPD / MSD discriminators are not on this path yet.
 """
 import math
 
@@ -152,6 +156,50 @@ class Generator(nn.Module):
         # F.leaky_relu(x) with the DEFAULT slope 0.01 (hifigan/models.py:161), conv_post, tanh
         return ops.conv1d_packed(x, self.conv_post.packed(ops.PACK_PLAIN), self.conv_post.bias.detach(), 1, 7, 1, 3,
                                  act="tanh", alpha=scale, in_slope=0.01)
+
+
+    def forward_train(self, x, taps=None):
+        """x: mel [B, 80, L] -> [B, 1, L * prod(upsample_rates)] as an autograd tensor: gradients reach every
+        parameter (weight_g / weight_v through the torch expression effective_weight(), the effective weight's own
+        gradient from the HIP backward) and x when it requires grad.  Same function as forward(); each leaky ReLU's
+        pre-activation is what the backward keeps.  taps (dict, optional) receives those tensors: "ups.i" the input of
+        upsampler i, "resblocks.j.convs1.m" / "resblocks.j.convs2.m" the inputs of the two convolutions of a pair,
+        "conv_post" the input of the last convolution (stage sums are kept undivided: the 1/num_kernels rides on the
+        next convolution and does not move a sign)."""
+        from . import autograd as ag
+        if not x.is_cuda:
+            raise _lib.MixganHipError("hifigan.Generator on %s: the HIP path has no CPU fallback" % x.device)
+        h = self.h
+        for u, k in zip(h.upsample_rates, h.upsample_kernel_sizes):
+            if k != 2 * u or u not in (2, 4, 8):
+                raise _lib.MixganHipError("forward_train: upsampler (kernel %d, stride %d) has no HIP backward; only "
+                                          "kernel = 2 * stride with stride in {2, 4, 8}" % (k, u))
+        x = ag.voc_conv(x.contiguous(), self.conv_pre.effective_weight(), self.conv_pre.bias, 1, 3)
+        scale = 1.0
+        for i, u in enumerate(h.upsample_rates):
+            up = self.ups[i]
+            if taps is not None:
+                taps["ups.%d" % i] = x
+            x = ag.voc_up(x, up.effective_weight(), up.bias, u, LRELU_SLOPE, scale)
+            acc = None
+            for j in range(self.num_kernels):
+                jj = i * self.num_kernels + j
+                rb = self.resblocks[jj]
+                r = x
+                for m, d in enumerate(rb.dilation):
+                    c1, c2 = rb.convs1[m], rb.convs2[m]
+                    rin = r
+                    r, t = ag.voc_pair(rin, c1.effective_weight(), c1.bias, c2.effective_weight(), c2.bias, d, LRELU_SLOPE)
+                    if taps is not None:
+                        taps["resblocks.%d.convs1.%d" % (jj, m)] = rin
+                        taps["resblocks.%d.convs2.%d" % (jj, m)] = t
+                acc = r if acc is None else acc + r
+            x = acc
+            scale = 1.0 / self.num_kernels
+        if taps is not None:
+            taps["conv_post"] = x
+        return ag.voc_conv(x, self.conv_post.effective_weight(), self.conv_post.bias, 1, 3, in_slope=0.01, alpha=scale,
+                           act="tanh")
 
 
 class AttrDict(dict):
