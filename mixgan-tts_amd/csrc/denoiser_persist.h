@@ -14,8 +14,8 @@
 //     algorithmic MFMAs (no halo MFMAs).
 // Two tile widths (same code, template parameter NT):
 //   NT = 64: 4 waves, wave w owns channels 64w..64w+63 x 64 frames -- ONE wave per SIMD with the whole 512-entry register
-//            file (x, the skip sum and GEMM 2's accumulators alone are 384 registers); one workgroup per CU (139 KB of
-//            LDS); the weight stream is read once per 64 frames.  Used when it fills the chip (B x ceil(L/64) > 128
+//            file (x, the skip sum and GEMM 2's accumulators alone are 384 registers); one workgroup per CU (133,132 B
+//            of LDS); the weight stream is read once per 64 frames.  Used when it fills the chip (B x ceil(L/64) > 128
 //            workgroups).  (Until round 3: 8 waves of 32 channels, two per SIMD; still there as MG_PERSIST_NT=864.  The
 //            second wave of every SIMD ran each GEMM phase 12-15 % slower than the first and the workgroup waited for it
 //            at every barrier: 350 -> 367 steps/s on the headline when each SIMD has one wave and nothing to wait for.)
@@ -45,6 +45,8 @@
 typedef unsigned long long dp_u64;
 typedef __attribute__((address_space(1))) dp_u64 dp_gu64;
 typedef __attribute__((address_space(1))) unsigned dp_gu32;
+typedef __attribute__((address_space(1))) const char dp_gcchar;     // the weight streams: a pointer that went through an
+typedef __attribute__((address_space(1))) const f32x4 dp_gcf32x4;   // opaque asm keeps "global" only in its type
 
 struct PersistArgs {
     const float *x_t;    // [B, M, L]
@@ -128,7 +130,8 @@ __device__ __forceinline__ int dp_at(int ch, int col) { return (((ch >> 3) * NTC
 // prefetches are pinned at the TOP of each k-group with sched_barrier (left alone, hipcc sinks them to the end of the
 // group: one k-group of latency cover instead of DIST) and the MFMAs keep the written order, which never puts two MFMAs
 // on one accumulator back to back.  The iteration order over (chunk, tap) comes from IT.
-//   ap[i]: packed weights of block i (+ lane); k-group q of (chunk, tap) = (chunk * KW + tap) * 4 + g sits at ap[i][q * 64]
+//   ap[i]: packed weights of block i (+ lane, or with loff: see SBASE); k-group q of (chunk, tap) = (chunk * KW + tap) * 4 + g
+//          sits at ap[i][q * 64]
 //   tile:  k-interleaved LDS tile + (this lane's column of n-block 0 for tap 0) * 8 + hh * 4;  NTC: its columns
 // DIST: how many k-groups ahead the weight fragments are requested.  3 everywhere since round 3: per-wave stamps
 // (MG_PERSIST_DBG_WAVE) show the second wave of every SIMD (waves 4-7) 14 % slower than the first in every GEMM phase
@@ -136,12 +139,42 @@ __device__ __forceinline__ int dp_at(int ch, int col) { return (((ch >> 3) * NTC
 #ifndef DP_DIST_BIG
 #define DP_DIST_BIG 3
 #endif
-template <int NMB, int NNB, int NTC, class IT, int DIST = (NMB * NNB >= 4 ? DP_DIST_BIG : 3)>
-__device__ __forceinline__ void dp_mfma_loop(f32x16 (&acc)[NMB][NNB], const f32x4 *const (&ap)[NMB], const float *__restrict__ tile)
+// Weight addressing, SBASE: ap[i] is WAVE-UNIFORM (no lane in it) and every lane adds the one 32-bit byte offset loff
+// (= lane * 16) -- the loads take the scalar-base form global_load v, s[base], offset: the base of an iteration's first
+// k-group is advanced on the scalar unit and the k-group inside the iteration is the instruction's immediate (at most
+// 3 * 1024 bytes), so a k-group's prefetch clump holds no vector address arithmetic (as per-lane 64-bit pointers it was
+// a v_lshl_add_u64 or an add / add-with-carry pair per row block and k-group, issued in the one MFMA gap the prefetches
+// are pinned to).  The offset is made opaque in every iteration: left visible, base + offset is hoisted out of the loop
+// as a 64-bit pointer per lane and row block again.  !SBASE (the backward kernels): ap[i] includes the lane.
+template <int NMB, int NNB, int NTC, class IT, int DIST, bool SBASE>
+__device__ __forceinline__ void dp_mfma_loop_at(f32x16 (&acc)[NMB][NNB], const f32x4 *const (&ap)[NMB], unsigned loff,
+                                                const float *__restrict__ tile)
 {
     static_assert(DIST >= 1 && DIST <= 3, "ring of 4 slots");
     f32x4 ring[4][NMB];
     f32x4 bb[2][NNB];
+    dp_gcchar *ub[NMB];   // SBASE: ap[i] in scalar registers, whatever the compiler can prove about it
+    if (SBASE) {
+#pragma unroll
+        for (int i = 0; i < NMB; ++i) {
+            const unsigned long long v = reinterpret_cast<unsigned long long>(ap[i]);
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+            ub[i] = (dp_gcchar *)(((unsigned long long)hi << 32) | lo);
+        }
+    }
+    // SBASE, inside the loop: row block i's scalar base of k-group qb.  Opaque as well: the row blocks of a wave lie a
+    // constant apart, and seen through, the compiler keeps ONE scalar base and adds the constants per lane again.
+    auto sbase = [&](int i, int qb) {
+        dp_gcchar *p = ub[i] + (size_t)qb * 1024;
+        asm volatile("" : "+s"(p));
+        return p;
+    };
+    if (SBASE) asm volatile("" : "+v"(loff));
+    // k-group qb + d of row block i; d is a constant once the loops are unrolled (SBASE: the prologue's loads)
+    auto wload = [&](int i, int qb, int d) -> f32x4 {
+        if (SBASE) return *(dp_gcf32x4 *)(ub[i] + (size_t)qb * 1024 + loff + d * 1024);
+        return ap[i][(size_t)(qb + d) * 64];
+    };
     auto qbase = [](int it) { return (IT::chunk(it) * IT::KW + IT::tap(it)) * 4; };
     auto boff = [](int it) { return IT::chunk(it) * (4 * NTC * 8) + IT::tap(it) * 8; };
     {
@@ -149,7 +182,7 @@ __device__ __forceinline__ void dp_mfma_loop(f32x16 (&acc)[NMB][NNB], const f32x
 #pragma unroll
         for (int s = 0; s < DIST; ++s)
 #pragma unroll
-            for (int i = 0; i < NMB; ++i) ring[s][i] = ap[i][(size_t)(q0 + s) * 64];
+            for (int i = 0; i < NMB; ++i) ring[s][i] = wload(i, q0, s);
         const float *T0 = tile + boff(0);
 #pragma unroll
         for (int j = 0; j < NNB; ++j) bb[0][j] = *reinterpret_cast<const f32x4 *>(T0 + 32 * 8 * j);
@@ -159,11 +192,24 @@ __device__ __forceinline__ void dp_mfma_loop(f32x16 (&acc)[NMB][NNB], const f32x
         const int itn = it + 1 < IT::N ? it + 1 : IT::N - 1;
         const int qc = qbase(it), qn = qbase(itn);
         const float *Tc = tile + boff(it), *Tn = tile + boff(itn);
+        dp_gcchar *bc[NMB], *bn[NMB];
+        if (SBASE) {
+            asm volatile("" : "+v"(loff));
+#pragma unroll
+            for (int i = 0; i < NMB; ++i) {
+                bc[i] = sbase(i, qc);
+                bn[i] = sbase(i, qn);
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int qa = u + DIST < 4 ? qc + u + DIST : qn + u + DIST - 4;   // DIST k-groups ahead
 #pragma unroll
-            for (int i = 0; i < NMB; ++i) ring[(u + DIST) & 3][i] = ap[i][(size_t)qa * 64];
+            for (int i = 0; i < NMB; ++i) {   // DIST k-groups ahead
+                constexpr int LIM = 4 - DIST;
+                const int d = u < LIM ? u + DIST : u - LIM;
+                if (SBASE) ring[(u + DIST) & 3][i] = *(dp_gcf32x4 *)((u < LIM ? bc[i] : bn[i]) + loff + d * 1024);
+                else ring[(u + DIST) & 3][i] = wload(i, u < LIM ? qc : qn, d);
+            }
             {
                 const float *Tx = u < 3 ? Tc + (u + 1) * (NTC * 8) : Tn;
 #pragma unroll
@@ -182,6 +228,19 @@ __device__ __forceinline__ void dp_mfma_loop(f32x16 (&acc)[NMB][NNB], const f32x
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+}
+template <int NMB, int NNB, int NTC, class IT, int DIST = (NMB * NNB >= 4 ? DP_DIST_BIG : 3)>
+__device__ __forceinline__ void dp_mfma_loop(f32x16 (&acc)[NMB][NNB], const f32x4 *const (&ap)[NMB], const float *__restrict__ tile)
+{
+    dp_mfma_loop_at<NMB, NNB, NTC, IT, DIST, false>(acc, ap, 0u, tile);
+}
+// ap[i] WITHOUT the lane (wave-uniform: the loop takes readfirstlane of it, so a lane-dependent pointer here would be
+// wrong addresses, not an error -- hence its own name), loff = lane * 16
+template <int NMB, int NNB, int NTC, class IT, int DIST = (NMB * NNB >= 4 ? DP_DIST_BIG : 3)>
+__device__ __forceinline__ void dp_mfma_loop_sbase(f32x16 (&acc)[NMB][NNB], const f32x4 *const (&ap)[NMB], unsigned loff,
+                                             const float *__restrict__ tile)
+{
+    dp_mfma_loop_at<NMB, NNB, NTC, IT, DIST, true>(acc, ap, loff, tile);
 }
 
 // write the 16 accumulator registers of one 32x32 block (rows ch0 + 8 (r >> 2) + 4 hh + (r & 3), this lane's column)
@@ -361,6 +420,10 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int hh = lane >> 5, c32 = lane & 31;
     const int L = a.L;
+    // weight addressing of the k loops (dp_mfma_loop_sbase): the wave's number as a scalar, so that the row-block bases
+    // derived from it are wave-uniform, and the lane's byte offset inside a k-group
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const unsigned loff = (unsigned)lane * 16u;
 
     // NT = 32: the two workgroups of a CU sit in different hardware wave slots; the matrix pipe serves the older wave
     // first, so one of them runs ahead and the other fills its gaps.  A workgroup that waits for a neighbour which is
@@ -460,11 +523,11 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
         const f32x4 *ap[MB];
 #pragma unroll
         for (int i = 0; i < MB; ++i) {
-            ap[i] = reinterpret_cast<const f32x4 *>(a.in_w) + (size_t)(MB * w + i) * 12 * 64 + lane;
+            ap[i] = reinterpret_cast<const f32x4 *>(a.in_w) + (size_t)(MB * wu + i) * 12 * 64;
 #pragma unroll
             for (int j = 0; j < NNB; ++j) acc[i][j] = st[i][j];
         }
-        dp_mfma_loop<MB, NNB, NH, DpIterHead>(acc, ap, hT + c32 * 8 + hh * 4);
+        dp_mfma_loop_sbase<MB, NNB, NH, DpIterHead>(acc, ap, loff, hT + c32 * 8 + hh * 4);
 #pragma unroll
         for (int i = 0; i < MB; ++i)
 #pragma unroll
@@ -540,8 +603,8 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
             const f32x4 *wc = reinterpret_cast<const f32x4 *>(lp + a.l_wc);
             const f32x4 *ap[MB];
 #pragma unroll
-            for (int i = 0; i < MB; ++i) ap[i] = wc + (size_t)(MB * w + i) * 32 * 64 + lane;
-            dp_mfma_loop<MB, NNB, NC, DpIterK1, (MB * NNB >= 4 ? DBIG : 3)>(acc1, ap, condT + c32 * 8 + hh * 4);
+            for (int i = 0; i < MB; ++i) ap[i] = wc + (size_t)(MB * wu + i) * 32 * 64;
+            dp_mfma_loop_sbase<MB, NNB, NC, DpIterK1, (MB * NNB >= 4 ? DBIG : 3)>(acc1, ap, loff, condT + c32 * 8 + hh * 4);
             if (WRITEP) {   // the first step of a sampling loop leaves the projections for the steps behind it
                 // uniform base + a 32-bit lane offset that is recomputed every layer (the opaque asm): kept live across
                 // the layer loop, 32 store addresses cost 34 spilled registers
@@ -626,19 +689,19 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
         const f32x4 *ap2[MB][2];
 #pragma unroll
         for (int p = 0; p < MB; ++p) {
-            ap2[p][0] = w3 + (size_t)(2 * (MB * w + p)) * 96 * 64 + lane;
-            ap2[p][1] = w3 + (size_t)(2 * (MB * w + p) + 1) * 96 * 64 + lane;
+            ap2[p][0] = w3 + (size_t)(2 * (MB * wu + p)) * 96 * 64;
+            ap2[p][1] = w3 + (size_t)(2 * (MB * wu + p) + 1) * 96 * 64;
         }
         // ONEPASS (one wave per SIMD, 512 registers): all four row blocks of the wave in one loop -- half the B-fragment
         // reads and one pipeline fill per phase instead of two
         if (ONEPASS) {
-            dp_mfma_loop<2 * MB, NNB, NH, DpIterCentre, DBIG>(reinterpret_cast<f32x16 (&)[2 * MB][NNB]>(acc2),
-                                                              reinterpret_cast<const f32x4 *const (&)[2 * MB]>(ap2),
+            dp_mfma_loop_sbase<2 * MB, NNB, NH, DpIterCentre, DBIG>(reinterpret_cast<f32x16 (&)[2 * MB][NNB]>(acc2),
+                                                              reinterpret_cast<const f32x4 *const (&)[2 * MB]>(ap2), loff,
                                                               hT + c32 * 8 + hh * 4);
         } else {
 #pragma unroll
             for (int p = 0; p < MB; ++p)
-                dp_mfma_loop<2, NNB, NH, DpIterCentre, (2 * NNB >= 4 ? DBIG : 3)>(acc2[p], ap2[p], hT + c32 * 8 + hh * 4);
+                dp_mfma_loop_sbase<2, NNB, NH, DpIterCentre, (2 * NNB >= 4 ? DBIG : 3)>(acc2[p], ap2[p], loff, hT + c32 * 8 + hh * 4);
         }
         DP_STAMP(4);
 
@@ -678,13 +741,13 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
 
         // ------------------------------------------------------------ GEMM 2, taps 0 and 2; gate
         if (ONEPASS) {
-            dp_mfma_loop<2 * MB, NNB, NH, DpIterOuter, DBIG>(reinterpret_cast<f32x16 (&)[2 * MB][NNB]>(acc2),
-                                                             reinterpret_cast<const f32x4 *const (&)[2 * MB]>(ap2),
+            dp_mfma_loop_sbase<2 * MB, NNB, NH, DpIterOuter, DBIG>(reinterpret_cast<f32x16 (&)[2 * MB][NNB]>(acc2),
+                                                             reinterpret_cast<const f32x4 *const (&)[2 * MB]>(ap2), loff,
                                                              hT + c32 * 8 + hh * 4);
         } else {
 #pragma unroll
             for (int p = 0; p < MB; ++p)
-                dp_mfma_loop<2, NNB, NH, DpIterOuter, (2 * NNB >= 4 ? DBIG : 3)>(acc2[p], ap2[p], hT + c32 * 8 + hh * 4);
+                dp_mfma_loop_sbase<2, NNB, NH, DpIterOuter, (2 * NNB >= 4 ? DBIG : 3)>(acc2[p], ap2[p], loff, hT + c32 * 8 + hh * 4);
         }
         DP_STAMP(7);
         __syncthreads();   // every wave has read hT for the last time: g may overwrite it
@@ -731,10 +794,10 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
             const f32x4 *ap[2 * MB];
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
-                ap[i] = wo + (size_t)(MB * w + i) * 32 * 64 + lane;            // x rows
-                ap[MB + i] = wo + (size_t)(8 + MB * w + i) * 32 * 64 + lane;   // skip rows
+                ap[i] = wo + (size_t)(MB * wu + i) * 32 * 64;            // x rows
+                ap[MB + i] = wo + (size_t)(8 + MB * wu + i) * 32 * 64;   // skip rows
             }
-            dp_mfma_loop<2 * MB, NNB, NH, DpIterK1, (2 * MB * NNB >= 4 ? DBIG : 3)>(st, ap, hT + c32 * 8 + hh * 4);
+            dp_mfma_loop_sbase<2 * MB, NNB, NH, DpIterK1, (2 * MB * NNB >= 4 ? DBIG : 3)>(st, ap, loff, hT + c32 * 8 + hh * 4);
         }
         DP_STAMP(11);
 #pragma unroll
@@ -763,13 +826,13 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
         const f32x4 *ap[MB];
 #pragma unroll
         for (int i = 0; i < MB; ++i) {
-            ap[i] = reinterpret_cast<const f32x4 *>(a.skip_w) + (size_t)(MB * w + i) * 32 * 64 + lane;
+            ap[i] = reinterpret_cast<const f32x4 *>(a.skip_w) + (size_t)(MB * wu + i) * 32 * 64;
 #pragma unroll
             for (int j = 0; j < NNB; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = a.skip_b[row_of(i, r)];
         }
-        dp_mfma_loop<MB, NNB, NH, DpIterK1>(acc, ap, hT + c32 * 8 + hh * 4);
+        dp_mfma_loop_sbase<MB, NNB, NH, DpIterK1>(acc, ap, loff, hT + c32 * 8 + hh * 4);
         // y -> the cond tile's storage (dead now), col c <-> frame l0+c
 #pragma unroll
         for (int i = 0; i < MB; ++i)
@@ -784,7 +847,7 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
     const int mblocks = (a.M + 31) / 32;
     // output projection: (32-row block, 32-column block) tasks dealt over the waves (M <= 96: 3 NNB tasks; one each, two for
     // the first waves of the 4-wave 64-frame form)
-    for (int task = w; task < mblocks * NNB; task += NW) {
+    for (int task = wu; task < mblocks * NNB; task += NW) {
         const int mb = task / NNB, nb = task - mb * NNB;
         f32x16 o[1][1];
 #pragma unroll
@@ -792,8 +855,8 @@ __global__ __launch_bounds__(NWV * 64, ((NT == 64 && NWV == 4) || SOLO) ? 1 : 2)
             const int row = 32 * mb + 8 * (r >> 2) + 4 * hh + (r & 3);
             o[0][0][r] = row < a.M ? a.out_b[row] : 0.f;
         }
-        const f32x4 *const ap[1] = {reinterpret_cast<const f32x4 *>(a.out_w) + (size_t)mb * 32 * 64 + lane};
-        dp_mfma_loop<1, 1, NC, DpIterK1>(o, ap, condT + (32 * nb + c32) * 8 + hh * 4);
+        const f32x4 *const ap[1] = {reinterpret_cast<const f32x4 *>(a.out_w) + (size_t)mb * 32 * 64};   // mb: a function of w
+        dp_mfma_loop_sbase<1, 1, NC, DpIterK1>(o, ap, loff, condT + (32 * nb + c32) * 8 + hh * 4);
         const int f = l0 + 32 * nb + c32;
         const size_t bo = (size_t)b * a.M * L;
         // a hand-off timed out somewhere in this launch (or an earlier one on this workspace whose error nobody has

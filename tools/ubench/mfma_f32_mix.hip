@@ -12,8 +12,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum { LD_NONE = 0, LD_LDS = 1, LD_GLB = 2, LD_BOTH = 3 };
 enum { PL_TOP = 0, PL_SPREAD = 1, PL_FREE = 2 };
+// how the weight loads are addressed -- AD_LANE: one 64-bit pointer per lane and row block (+ q * 1024 bytes per k-group);
+// AD_SBASE: one wave-uniform base per row block (advanced once per four k-groups on the scalar unit), one 32-bit lane
+// offset shared by all row blocks, and the k-group inside the four as the instruction's immediate offset
+enum { AD_LANE = 0, AD_SBASE = 1 };
 
-template <int NMB, int NNB, int LD, int PL>
+template <int NMB, int NNB, int LD, int PL, int AD = AD_LANE>
 __global__ __launch_bounds__(512) void k(const f32x4 *__restrict__ w, const float *__restrict__ init, float *out, int groups,
                                          int wrap_groups)
 {
@@ -28,6 +32,10 @@ __global__ __launch_bounds__(512) void k(const f32x4 *__restrict__ w, const floa
     f32x4 ring[4][NMB], bb[2][NNB];
     const f32x4 *ap[NMB];
     for (int i = 0; i < NMB; ++i) ap[i] = w + ((size_t)(wv * NMB + i) * wrap_groups) * 64 + lane;
+    const char *sb[NMB];   // AD_SBASE
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    for (int i = 0; i < NMB; ++i) sb[i] = reinterpret_cast<const char *>(w + ((size_t)(wvu * NMB + i) * wrap_groups) * 64);
+    unsigned loff = (unsigned)lane * 16u;
     for (int s = 0; s < 4; ++s)
         for (int i = 0; i < NMB; ++i) ring[s][i] = ap[i][(size_t)s * 64];
     const float *T = lds + c32 * 8 + hh * 4;
@@ -35,10 +43,17 @@ __global__ __launch_bounds__(512) void k(const f32x4 *__restrict__ w, const floa
     int q = 0;
 #pragma unroll 1
     for (int g = 0; g < groups; g += 4) {
+        const int q4 = q;   // AD_SBASE: the four k-groups q4 .. q4 + 3 (q4 % 4 == 0 and wrap_groups % 4 == 0: inside the row block)
+        // opaque: otherwise base + lane offset is hoisted out of the loop as one 64-bit pointer per lane and row block
+        if (AD == AD_SBASE) asm volatile("" : "+v"(loff));
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             q = q + 1 < wrap_groups ? q + 1 : 0;
-            if (LD & LD_GLB) {
+            if ((LD & LD_GLB) && AD == AD_SBASE) {
+#pragma unroll
+                for (int i = 0; i < NMB; ++i)
+                    ring[(u + 2) & 3][i] = *reinterpret_cast<const f32x4 *>(sb[i] + (size_t)q4 * 1024 + loff + u * 1024);
+            } else if (LD & LD_GLB) {
 #pragma unroll
                 for (int i = 0; i < NMB; ++i) ring[(u + 2) & 3][i] = ap[i][(size_t)q * 64];
             }
@@ -87,13 +102,13 @@ static float gauss()
 static f32x4 *g_w;
 static float *g_init, *g_out;
 
-template <int NMB, int NNB, int LD, int PL>
+template <int NMB, int NNB, int LD, int PL, int AD = AD_LANE>
 static void run(const char *name, int wrap_groups)
 {
     const int blocks = 256, groups = 8000;
-    auto kern = k<NMB, NNB, LD, PL>;
+    auto kern = k<NMB, NNB, LD, PL, AD>;
     // every wave reads f32x4 indices < (8 waves * NMB rows) * wrap_groups * 64: must stay inside the 64 Mi-float buffer
-    if ((size_t)8 * NMB * wrap_groups * 64 * 4 > ((size_t)64 << 20) || wrap_groups < 4) {
+    if ((size_t)8 * NMB * wrap_groups * 64 * 4 > ((size_t)64 << 20) || wrap_groups < 4 || wrap_groups % 4) {
         printf("%dx%d %s: stream does not fit the buffer, skipped\n", NMB, NNB, name);
         return;
     }
@@ -140,5 +155,13 @@ int main()
     run<4, 2, LD_BOTH, PL_TOP>("both, top (4x2: 32 MFMAs per group), 4 MB", W_BIG);
     run<4, 2, LD_BOTH, PL_SPREAD>("both, spread (4x2), 4 MB", W_BIG);
     run<2, 1, LD_BOTH, PL_TOP>("both, top (the 32-frame form), 4 MB", W_BIG);
+    // scalar-base weight addressing against the per-lane pointers, each row three times (the spread of a row is the yardstick)
+    for (int rep = 0; rep < 3; ++rep) {
+        run<4, 2, LD_BOTH, PL_TOP>("both, top (4x2), 4 MB, per-lane pointers", W_BIG);
+        run<4, 2, LD_BOTH, PL_SPREAD>("both, spread (4x2), 4 MB, per-lane pointers", W_BIG);
+        run<2, 2, LD_BOTH, PL_TOP>("both, top, 4 MB, per-lane pointers", W_BIG);
+        run<4, 2, LD_BOTH, PL_TOP, AD_SBASE>("both, top (4x2), 4 MB, scalar base + lane offset + imm", W_BIG);
+        run<2, 2, LD_BOTH, PL_TOP, AD_SBASE>("both, top, 4 MB, scalar base + lane offset + imm", W_BIG);
+    }
     return 0;
 }
