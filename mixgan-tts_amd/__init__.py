@@ -43,6 +43,7 @@ from . import metrics  # noqa: F401
 from .metrics import (DtwGeometryError, mel_cepstra, dtw, mel_cepstral_distortion, f0_metrics,  # noqa: F401
                       synthesis_report, evaluate_model)
 from . import vocoder_train  # noqa: F401
-from .vocoder_train import GeneratorTrainer, sample_segments  # noqa: F401
+from .vocoder_train import GeneratorTrainer, VocoderGANTrainer, sample_segments  # noqa: F401
+from .losses import hifigan_discriminator_loss, hifigan_generator_loss, hifigan_feature_loss  # noqa: F401
 
 __version__ = "0.1.0"

@@ -128,6 +128,48 @@ def weighted_means(terms):
     return _WeightedMeansFn.apply(tuple(spec), *xs, *ys)
 
 
+# --------------------------------------------------------------------------------------------------
+# HiFi-GAN's GAN terms (Kong et al. 2020: discriminator_loss, generator_loss, feature_loss) over the outputs of
+# discriminators with the published calling convention (vocoder_train.VocoderGANTrainer).
+# --------------------------------------------------------------------------------------------------
+def _means_in_calls(terms):
+    """weighted_means over any number of terms, MG_LOSS_MAX_TERMS per launch: (total, [detached per-term means])."""
+    total, means = None, []
+    for at in range(0, len(terms), _lib.MG_LOSS_MAX_TERMS):
+        part = terms[at:at + _lib.MG_LOSS_MAX_TERMS]
+        out = weighted_means(part)
+        total = out[0] if total is None else total + out[0]
+        means.extend(out.detach()[1 + _lib.MG_LOSS_GROUPS:1 + _lib.MG_LOSS_GROUPS + len(part)].unbind(0))
+    return total, means
+
+
+def hifigan_discriminator_loss(disc_real, disc_gen):
+    """sum over the discriminators of mean((1 - dr)^2) + mean(dg^2).  Returns (total, r_losses, g_losses); the lists
+    hold device scalars (upstream's hold host floats)."""
+    if len(disc_real) != len(disc_gen) or not disc_real:
+        raise ValueError("one real and one generated output per discriminator")
+    terms = []
+    for dr, dg in zip(disc_real, disc_gen):
+        terms += [("mse", dr, 1.0, 1.0), ("mse", dg, 0.0, 1.0)]
+    total, means = _means_in_calls(terms)
+    return total, means[0::2], means[1::2]
+
+
+def hifigan_generator_loss(disc_gen):
+    """sum of mean((1 - dg)^2).  Returns (total, gen_losses)."""
+    if not disc_gen:
+        raise ValueError("no discriminator outputs")
+    return _means_in_calls([("mse", dg, 1.0, 1.0) for dg in disc_gen])
+
+
+def hifigan_feature_loss(fmap_r, fmap_g):
+    """2 sum over the discriminators and their maps of mean|fr - fg|, the real maps as targets (gradient to fmap_g)."""
+    terms = [("l1", g, r, 2.0) for dr, dg in zip(fmap_r, fmap_g) for r, g in zip(dr, dg)]
+    if not terms:
+        raise ValueError("no feature maps")
+    return _means_in_calls(terms)[0]
+
+
 class _RangeMeansFn(torch.autograd.Function):
     """weighted_means over BATCH RANGES of whole feature maps: term k reads rows [a_lo, a_hi) of tensor `ti` (mode 0:
     mean (x - c)^2; mode 1: mean |x[a] - x[b]| against rows [b_lo, b_lo + a_hi - a_lo) of the same tensor, gradient to

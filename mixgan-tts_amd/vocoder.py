@@ -16,7 +16,8 @@ one buffer and the 1/3 is folded into the next convolution (leaky ReLU is positi
 `forward` is the inference path (no_grad, post-activations fused into epilogues).  `forward_train` is the same
 function as an autograd tensor: every convolution keeps its pre-activation input and differentiates on the HIP side
 (csrc/vocoder_train.hip through autograd.py; weight norm stays a torch expression).  vocoder_train.GeneratorTrainer
-puts HiFi-GAN's mel-reconstruction loss on it; the MPD / MSD discriminators are not on this path yet.
+puts HiFi-GAN's mel-reconstruction loss on it, vocoder_train.VocoderGANTrainer the full GAN step over torch
+discriminators (the MPD / MSD themselves are not native yet).
 """
 import math
 

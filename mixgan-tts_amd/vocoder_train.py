@@ -1,13 +1,16 @@
 """Generator half of HiFi-GAN training on the HIP path: vocoder.Generator.forward_train, HiFi-GAN's mel-reconstruction
 loss through audio.TacotronSTFT.mel_spectrogram_diff, and checkpoints that vocoder.get_vocoder loads.
 
-The MPD / MSD discriminators and the adversarial and feature-matching terms are not here; forward_train returns an
-ordinary autograd tensor, so any PyTorch loss or discriminator can be put on top of it.
+GeneratorTrainer trains on the mel term alone.  VocoderGANTrainer is HiFi-GAN's full step: the discriminator phase and
+the generator phase with the adversarial and feature-matching terms (losses.hifigan_*: the fused HIP loss kernels), over
+any discriminator modules with the published calling convention.  The discriminators themselves (MPD / MSD) are not
+native yet: they are ordinary torch modules.
 """
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .losses import hifigan_discriminator_loss, hifigan_generator_loss, hifigan_feature_loss
 
 
 def sample_segments(mels, wavs, mel_lens, frames=32, generator=None, hop=256):
@@ -91,5 +94,123 @@ class GeneratorTrainer:
             self.optimizer.load_state_dict(ckpt["optimizer"])
         if "scheduler" in ckpt:
             self.scheduler.load_state_dict(ckpt["scheduler"])
+        self.steps = int(ckpt.get("steps", 0))
+        return self
+
+
+class VocoderGANTrainer:
+    """HiFi-GAN's training step (Kong et al. 2020, train.py) over a vocoder.Generator and a dict name -> discriminator.
+
+    A discriminator is any module whose forward(y, y_hat) on [B, 1, T] tensors returns (y_d_rs, y_d_gs, fmap_rs,
+    fmap_gs) -- per sub-discriminator the logits of the real and of the generated half, and their lists of feature
+    maps -- as the published MultiPeriodDiscriminator / MultiScaleDiscriminator do.  Defaults as GeneratorTrainer: two
+    AdamW optimizers (2e-4, betas 0.8 / 0.99), two ExponentialLR(0.999) schedulers stepped by end_epoch(),
+    lambda_mel = 45.
+    optimizer: None -> torch.optim.AdamW; a class is built as optimizer(params, lr=lr) for each side."""
+
+    def __init__(self, generator, stft, discriminators, optimizer=None, lr=2e-4, betas=(0.8, 0.99), lr_decay=0.999,
+                 lambda_mel=45.0):
+        if not discriminators:
+            raise ValueError("VocoderGANTrainer needs at least one discriminator")
+        for name in discriminators:
+            if name in ("generator", "optim_g", "optim_d", "sched_g", "sched_d", "steps"):
+                raise ValueError("discriminator name %r is a checkpoint key" % name)
+        self.generator = generator
+        self.stft = stft
+        self.discriminators = dict(discriminators)
+        self.lambda_mel = float(lambda_mel)
+        g_params = [p for p in generator.parameters() if p.requires_grad]
+        self._d_params = [p for d in self.discriminators.values() for p in d.parameters() if p.requires_grad]
+        if optimizer is None:
+            make = lambda ps: torch.optim.AdamW(ps, lr=lr, betas=betas)  # noqa: E731
+        elif isinstance(optimizer, type):
+            make = lambda ps: optimizer(ps, lr=lr)  # noqa: E731
+        else:
+            raise TypeError("optimizer: None or an optimizer class (two instances are built)")
+        self.optim_g, self.optim_d = make(g_params), make(self._d_params)
+        self.scheduler_g = torch.optim.lr_scheduler.ExponentialLR(self.optim_g, gamma=lr_decay)
+        self.scheduler_d = torch.optim.lr_scheduler.ExponentialLR(self.optim_d, gamma=lr_decay)
+        self.steps = 0
+
+    def step(self, mel, wav, taps=None):
+        """mel [B, 80, F], wav [B, 256 F] (or [B, 1, 256 F]).  y_hat = G(mel); the discriminators learn on
+        y_hat.detach() and step; then the generator learns on lambda_mel * mel L1 + adversarial + feature matching
+        through the UPDATED discriminators, whose parameters need no gradient for the duration, and steps.
+        Returns {"loss_d", "loss_g", "mel_l1", "adv", "fm"} as device scalars; nothing here reads the device.
+        taps: a dict that receives what fixes the step's leaky-ReLU sign patterns: "generator" (forward_train's taps)
+        and "d" / "g": name -> (fmap_rs, fmap_gs) of the discriminator and of the generator phase."""
+        if not mel.is_cuda or not wav.is_cuda:
+            raise _lib.MixganHipError("VocoderGANTrainer.step: tensors must be on the GPU (no CPU fallback)")
+        y = wav.unsqueeze(1) if wav.dim() == 2 else wav
+        if taps is not None:
+            taps.update({"generator": {}, "d": {}, "g": {}})
+        y_hat = self.generator.forward_train(mel, None if taps is None else taps["generator"])
+        if y_hat.shape != y.shape:
+            raise ValueError("wav must be %s, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
+
+        self.optim_d.zero_grad(set_to_none=True)
+        y_hat_d = y_hat.detach()
+        loss_d = None
+        for name, d in self.discriminators.items():
+            y_d_rs, y_d_gs, fmap_rs, fmap_gs = d(y, y_hat_d)
+            if taps is not None:
+                taps["d"][name] = (fmap_rs, fmap_gs)
+            part = hifigan_discriminator_loss(y_d_rs, y_d_gs)[0]
+            loss_d = part if loss_d is None else loss_d + part
+        loss_d.backward()
+        self.optim_d.step()
+
+        self.optim_g.zero_grad(set_to_none=True)
+        m_hat = self.stft.mel_spectrogram_diff(y_hat.squeeze(1))
+        with torch.no_grad():
+            m_ref = self.stft.mel_spectrogram_diff(y.squeeze(1))
+        T = min(m_hat.shape[2], m_ref.shape[2])
+        mel_l1 = F.l1_loss(m_hat[:, :, :T], m_ref[:, :, :T])
+        for p in self._d_params:
+            p.requires_grad_(False)
+        try:
+            adv = fm = None
+            for name, d in self.discriminators.items():
+                _, y_d_gs, fmap_rs, fmap_gs = d(y, y_hat)
+                if taps is not None:
+                    taps["g"][name] = (fmap_rs, fmap_gs)
+                a, f = hifigan_generator_loss(y_d_gs)[0], hifigan_feature_loss(fmap_rs, fmap_gs)
+                adv, fm = (a, f) if adv is None else (adv + a, fm + f)
+            loss_g = adv + fm + self.lambda_mel * mel_l1
+            loss_g.backward()
+        finally:
+            for p in self._d_params:
+                p.requires_grad_(True)
+        self.optim_g.step()
+        self.steps += 1
+        return {"loss_d": loss_d.detach(), "loss_g": loss_g.detach(), "mel_l1": mel_l1.detach(), "adv": adv.detach(),
+                "fm": fm.detach()}
+
+    def end_epoch(self):
+        """lr *= lr_decay on both sides, once per epoch."""
+        self.scheduler_g.step()
+        self.scheduler_d.step()
+
+    def save(self, path):
+        """{"generator": state_dict, <name>: state_dict per discriminator, "optim_g", "optim_d", "steps", ...}: the
+        "generator" entry is what vocoder.get_vocoder(..., checkpoint_path=path) loads."""
+        cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}  # noqa: E731
+        ckpt = {"generator": cpu(self.generator.state_dict())}
+        for name, d in self.discriminators.items():
+            ckpt[name] = cpu(d.state_dict())
+        ckpt.update({"optim_g": self.optim_g.state_dict(), "optim_d": self.optim_d.state_dict(),
+                     "sched_g": self.scheduler_g.state_dict(), "sched_d": self.scheduler_d.state_dict(),
+                     "steps": self.steps})
+        torch.save(ckpt, path)
+
+    def load(self, path):
+        ckpt = torch.load(path, map_location="cpu", weights_only=True)
+        self.generator.load_state_dict(ckpt["generator"])
+        for name, d in self.discriminators.items():
+            d.load_state_dict(ckpt[name])
+        for key, obj in (("optim_g", self.optim_g), ("optim_d", self.optim_d), ("sched_g", self.scheduler_g),
+                         ("sched_d", self.scheduler_d)):
+            if key in ckpt:
+                obj.load_state_dict(ckpt[key])
         self.steps = int(ckpt.get("steps", 0))
         return self
