@@ -425,12 +425,21 @@ def mel_diff(x, stft):
     return _MelDiffFn.apply(x, stft)
 
 
-def _voc_dgrad(g, w, K, dil, pad, alpha, Lin):
-    """Data gradient of alpha * conv1d(., w [Co,Ci,K], dilation dil, padding pad): the forward kernel on the transposed,
-    tap-flipped pack with pad' = dil (K-1) - pad."""
-    Ci = w.shape[1]
-    return ops.conv1d_packed(g, ops.pack_conv_weight(w, ops.PACK_DGRAD), None, Ci, K, 1, dil * (K - 1) - pad,
-                             alpha=alpha, Lout=Lin, dilation=dil)
+def _voc_conv_bwd(g, x, w, dil, pad, in_slope, alpha, need=(True, True, True), add=None):
+    """(dw, db, dx), each where `need` asks for it, of alpha * conv1d(leaky_relu(x, in_slope), w [Co,Ci,K], dilation dil,
+    padding pad) + b, from the output's gradient g and the saved pre-activation x.  The data gradient is the forward
+    kernel on the transposed, tap-flipped pack with pad' = dil (K-1) - pad, then masked in place; `add` (a residual
+    branch's gradient) joins in the mask's pass."""
+    Ci, K = w.shape[1], w.shape[2]
+    dw = ops.conv1d_wgrad_ex(g, x, K, dil, pad, in_slope, alpha) if need[0] else None
+    db = ops.rowsum(g) if need[1] else None
+    dx = None
+    if need[2]:
+        dx = ops.conv1d_packed(g, ops.pack_conv_weight(w, ops.PACK_DGRAD), None, Ci, K, 1, dil * (K - 1) - pad,
+                               alpha=alpha, Lout=x.shape[2], dilation=dil)
+        if in_slope != 1.0 or add is not None:
+            ops.lrelu_bwd(dx, x, in_slope, add=add, out=dx)
+    return dw, db, dx
 
 
 class _VocConvFn(torch.autograd.Function):
@@ -450,54 +459,38 @@ class _VocConvFn(torch.autograd.Function):
     def backward(ctx, g):
         x, w, y = ctx.saved_tensors
         dil, pad, in_slope, alpha, act = ctx.cfg
-        K = w.shape[2]
         g = g.contiguous()
         if act:
             g = ops.act_bwd(g, y, act)
         need = ctx.needs_input_grad
-        dw = ops.conv1d_wgrad_ex(g, x, K, dil, pad, in_slope, alpha) if need[1] else None
-        db = ops.rowsum(g) if need[2] else None
-        dx = None
-        if need[0]:
-            dx = _voc_dgrad(g, w, K, dil, pad, alpha, x.shape[2])
-            if in_slope != 1.0:
-                ops.lrelu_bwd(dx, x, in_slope, out=dx)
+        dw, db, dx = _voc_conv_bwd(g, x, w, dil, pad, in_slope, alpha, (need[1], need[2], need[0]))
         return dx, dw, db, None, None, None, None, None
 
 
 class _VocPairFn(torch.autograd.Function):
-    """One (convs1[m], convs2[m]) pair of a ResBlock: t = conv1(lrelu(r)) + b1, out = conv2(lrelu(t)) + b2 + r.
-    Saves the two PRE-activations r and t; both leaky ReLUs are applied while the kernels stage their input."""
+    """One (convs1[m], convs2[m]) pair of a ResBlock: t = conv1(lrelu(r)) + b1 (dilation dil, padding pad1),
+    out = conv2(lrelu(t)) + b2 + r (padding pad2).  Saves the two PRE-activations r and t; both leaky ReLUs are applied
+    while the kernels stage their input."""
 
     @staticmethod
-    def forward(ctx, r, w1, b1, w2, b2, dil, slope):
+    def forward(ctx, r, w1, b1, w2, b2, dil, pad1, pad2, slope):
         C, _, K = w1.shape
-        t = ops.conv1d_packed(r, ops.pack_conv_weight(w1, ops.PACK_PLAIN), b1, C, K, 1, (K * dil - dil) // 2,
-                              dilation=dil, in_slope=slope)
-        out = ops.conv1d_packed(t, ops.pack_conv_weight(w2, ops.PACK_PLAIN), b2, C, K, 1, (K - 1) // 2, add=r,
-                                in_slope=slope)
+        t = ops.conv1d_packed(r, ops.pack_conv_weight(w1, ops.PACK_PLAIN), b1, C, K, 1, pad1, dilation=dil,
+                              in_slope=slope)
+        out = ops.conv1d_packed(t, ops.pack_conv_weight(w2, ops.PACK_PLAIN), b2, C, K, 1, pad2, add=r, in_slope=slope)
         ctx.save_for_backward(r, t, w1, w2)
-        ctx.cfg = (dil, slope)
+        ctx.cfg = (dil, pad1, pad2, slope)
         ctx.mark_non_differentiable(t)
         return out, t
 
     @staticmethod
     def backward(ctx, g, _gt):
         r, t, w1, w2 = ctx.saved_tensors
-        dil, slope = ctx.cfg
-        K = w1.shape[2]
-        p1, p2 = (K * dil - dil) // 2, (K - 1) // 2
-        L = r.shape[2]
+        dil, pad1, pad2, slope = ctx.cfg
         g = g.contiguous()
-        dw2 = ops.conv1d_wgrad_ex(g, t, K, 1, p2, slope)
-        db2 = ops.rowsum(g)
-        dt = _voc_dgrad(g, w2, K, 1, p2, 1.0, L)
-        ops.lrelu_bwd(dt, t, slope, out=dt)
-        dw1 = ops.conv1d_wgrad_ex(dt, r, K, dil, p1, slope)
-        db1 = ops.rowsum(dt)
-        dr = _voc_dgrad(dt, w1, K, dil, p1, 1.0, L)
-        ops.lrelu_bwd(dr, r, slope, add=g, out=dr)      # the mask and the residual branch's gradient in one pass
-        return dr, dw1, db1, dw2, db2, None, None
+        dw2, db2, dt = _voc_conv_bwd(g, t, w2, 1, pad2, slope, 1.0)
+        dw1, db1, dr = _voc_conv_bwd(dt, r, w1, dil, pad1, slope, 1.0, add=g)    # + the residual branch's gradient
+        return dr, dw1, db1, dw2, db2, None, None, None, None
 
 
 class _VocUpFn(torch.autograd.Function):
@@ -526,8 +519,8 @@ def voc_conv(x, w, b, dil, pad, in_slope=1.0, alpha=1.0, act=None):
     return _VocConvFn.apply(x, w.contiguous(), b, dil, pad, in_slope, alpha, act)
 
 
-def voc_pair(r, w1, b1, w2, b2, dil, slope):
-    return _VocPairFn.apply(r, w1.contiguous(), b1, w2.contiguous(), b2, dil, slope)
+def voc_pair(r, w1, b1, w2, b2, dil, pad1, pad2, slope):
+    return _VocPairFn.apply(r, w1.contiguous(), b1, w2.contiguous(), b2, dil, pad1, pad2, slope)
 
 
 def voc_up(x, w, b, u, slope, alpha):

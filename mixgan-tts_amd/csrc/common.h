@@ -25,6 +25,20 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 static inline int mg_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t mg_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// number of frame splits for a [Co, Ci, K] weight gradient (wgrad_mfma.h and vocoder_train.hip; the one count that both
+// the launchers and the scratch sizes use): two workgroups per CU are resident (66.5 KB LDS each), keep the grid within
+// ONE round of 512 workgroups -- 560 workgroups take two rounds, i.e. twice the time of 504
+static inline int wgrad_nsplit(int Co, int Ci, int K, int G = 1)
+{
+    const int tiles = mg_cdiv(Co, 128) * mg_cdiv(Ci, 128) * K * G;
+    // measured sweep (B=8, L=1000): 512 workgroups is the optimum for every shape with more than 8 tiles; the small
+    // k=1 gradients (<= 8 tiles: 512x256, 256x256) are 10-25 % faster with 256 -- their finalize pass, which reads
+    // nsplit copies of the output, is as long as the GEMM itself
+    const int target = tiles <= 8 ? 256 : 512;
+    const int n = target / tiles;
+    return n < 1 ? 1 : n;
+}
+
 // v_rcp_f32 (1 ulp) instead of the IEEE division sequence (~10 VALU instructions): the gate epilogue evaluates 64
 // of these per lane per layer between two barriers, where nothing overlaps them.
 __device__ __forceinline__ float mg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }

@@ -184,15 +184,6 @@ __global__ __launch_bounds__(256) void vt_wgrad_finalize_kernel(const float *__r
     }
 }
 
-// the split count of wgrad_mfma.h: one round of 512 workgroups (256 for gradients of at most 8 tiles)
-int vt_nsplit(int M, int Nn, int K)
-{
-    const int tiles = mg_cdiv(M, 128) * mg_cdiv(Nn, 128) * K;
-    const int target = tiles <= 8 ? 256 : 512;
-    const int n = target / tiles;
-    return n < 1 ? 1 : n;
-}
-
 int vt_wgrad_launch(const float *am, long a_bs, float a_slope, const float *bm, long b_bs, float b_slope, float *dw,
                     float *scratch, int B, int M, int Nn, int La, int Lb, int K, int bstride, int dil, int pad,
                     float alpha, int accumulate, hipStream_t st)
@@ -209,7 +200,7 @@ int vt_wgrad_launch(const float *am, long a_bs, float a_slope, const float *bm, 
     a.nchunks = a.chunks_per_b * B;
     const int TM = M <= 32 ? 1 : (M <= 64 ? 2 : 4), TN = Nn <= 32 ? 1 : (Nn <= 64 ? 2 : 4);
     a.n_tiles = mg_cdiv(Nn, 32 * TN);
-    int nsplit = vt_nsplit(M, Nn, K);   // by 128 x 128 tiles whatever the tile: the scratch the caller sized
+    int nsplit = wgrad_nsplit(M, Nn, K);   // mg_conv1d_wgrad_scratch_floats >= nsplit * M * Nn * K for this same count
     if (nsplit > a.nchunks) nsplit = a.nchunks;
     a.nsplit = nsplit;
     a.a_slope = a_slope;
@@ -447,7 +438,7 @@ extern "C" int mg_lrelu_bwd(const float *dy, const float *x, const float *add, f
 extern "C" size_t mg_conv_transpose1d_wgrad_scratch_floats(int Ci, int Co, int u)
 {
     if (Ci <= 0 || Co <= 0 || !vt_u_ok(u)) return 0;
-    return (size_t)vt_nsplit(Ci, Co, 2 * u) * Ci * Co * 2 * u;
+    return (size_t)wgrad_nsplit(Ci, Co, 2 * u) * Ci * Co * 2 * u;
 }
 
 extern "C" int mg_conv_transpose1d_wgrad(const float *dy, const float *x, float *dw, float *scratch, int B, int Ci, int L,

@@ -256,18 +256,6 @@ __global__ __launch_bounds__(256) void wgrad_finalize_kernel(const float *__rest
     }
 }
 
-// number of frame splits for a [Co, Ci, K] gradient: two workgroups per CU are resident (66.5 KB LDS each), keep
-// the grid within ONE round of 512 workgroups -- 560 workgroups take two rounds, i.e. twice the time of 504
-static inline int wgrad_nsplit(int Co, int Ci, int K, int G = 1)
-{
-    const int tiles = mg_cdiv(Co, 128) * mg_cdiv(Ci, 128) * K * G;
-    // measured sweep (B=8, L=1000): 512 workgroups is the optimum for every shape with more than 8 tiles; the small
-    // k=1 gradients (<= 8 tiles: 512x256, 256x256) are 10-25 % faster with 256 -- their finalize pass, which reads
-    // nsplit copies of the output, is as long as the GEMM itself
-    const int target = tiles <= 8 ? 256 : 512;
-    const int n = target / tiles;
-    return n < 1 ? 1 : n;
-}
 static inline size_t wgrad_scratch_floats(int Co, int Ci, int K, int G = 1)
 {
     // either kernel may run (the streaming one needs aligned, stride-1 operands): size for both

@@ -13,18 +13,17 @@ fused in staging, phases interleaved by the epilogue; other (k, stride) fall bac
 stride-1 convolution on the transposed, tap-flipped pack); the three ResBlocks of a stage accumulate into
 one buffer and the 1/3 is folded into the next convolution (leaky ReLU is positively homogeneous).
 
-`forward` is the inference path (no_grad, post-activations fused into epilogues).  `forward_train` is the same
-function as an autograd tensor: every convolution keeps its pre-activation input and differentiates on the HIP side
-(csrc/vocoder_train.hip through autograd.py; weight norm stays a torch expression).  vocoder_train.GeneratorTrainer
-puts HiFi-GAN's mel-reconstruction loss on it, vocoder_train.VocoderGANTrainer the full GAN step over torch
-discriminators (the MPD / MSD themselves are not native yet).
+The network is walked in one place, Generator._walk, with one of two site sets: _Infer (`forward`: no_grad, cached packs,
+post-activations fused into epilogues) or _Train (`forward_train`: autograd Functions that keep each pre-activation and
+differentiate in csrc/vocoder_train.hip; weight norm stays a torch expression).  vocoder_train's trainers put HiFi-GAN's
+mel loss and the full GAN step (over torch discriminators: the MPD / MSD are not native yet) on forward_train.
 """
 import math
 
 import torch
 from torch import nn
 
-from . import ops, _lib
+from . import ops, _lib, autograd as ag
 
 LRELU_SLOPE = 0.1
 
@@ -81,22 +80,59 @@ class ResBlock(nn.Module):
         for l in list(self.convs1) + list(self.convs2):
             l.remove_weight_norm()
 
-    def forward_cm(self, x, acc, first):
-        """x [B,C,L] -> adds this block's output into `acc` (= on `first`)."""
-        k = self.kernel_size
-        C = x.shape[1]
-        r = x
-        n = len(self.dilation)
-        for m, d in enumerate(self.dilation):
-            c1, c2 = self.convs1[m], self.convs2[m]
-            t = ops.conv1d_packed(r, c1.packed(ops.PACK_PLAIN), c1.bias.detach(), C, k, 1, (k * d - d) // 2,
-                                  act="lrelu_s", act_slope=LRELU_SLOPE, dilation=d, in_slope=LRELU_SLOPE)
-            if m < n - 1:
-                r = ops.conv1d_packed(t, c2.packed(ops.PACK_PLAIN), c2.bias.detach(), C, k, 1, (k - 1) // 2, add=r)
-            else:   # last pair: write (conv + bias + r) straight into the stage accumulator
-                ops.conv1d_packed(t, c2.packed(ops.PACK_PLAIN), c2.bias.detach(), C, k, 1, (k - 1) // 2, add=r,
-                                  out=acc, accumulate=not first)
-        return acc
+
+def _polyphase(k, u):
+    """The upsamplers with a polyphase kernel (forward and backward): kernel = 2 * stride, stride in {2, 4, 8}."""
+    return k == 2 * u and u in (2, 4, 8)
+
+
+class _Infer:
+    """Generator._walk's sites in inference: cached packs, detached biases, activations and sums in the epilogues."""
+
+    @staticmethod
+    def conv(c, x, Co, k, pad, in_slope=1.0, alpha=1.0, act=None):
+        return ops.conv1d_packed(x, c.packed(ops.PACK_PLAIN), c.bias.detach(), Co, k, 1, pad, act=act, alpha=alpha,
+                                 in_slope=in_slope)
+
+    @staticmethod
+    def up(c, x, Co, k, u, slope, alpha):
+        if _polyphase(k, u):                  # 3-tap GEMM with Co*u rows, lrelu fused in staging
+            return ops.conv_transpose1d_packed(x, c.packed(ops.PACK_TPOSE), c.bias.detach(), Co, u, in_slope=slope,
+                                               alpha=alpha)
+        L = x.shape[2]                        # general (k, u): lrelu + zero insertion, flipped stride-1 conv
+        pad = (k - u) // 2
+        z = ops.upsample_zero(x, u, (L - 1) * u + 1, slope=slope)
+        return ops.conv1d_packed(z, c.packed(ops.PACK_DGRAD), c.bias.detach(), Co, k, 1, k - 1 - pad, alpha=alpha,
+                                 Lout=(L - 1) * u - 2 * pad + k)
+
+    @staticmethod
+    def pair(c1, c2, r, k, d, pad1, pad2, slope, acc, last):
+        C = r.shape[1]     # t leaves the first epilogue already activated: this walk has no taps to give
+        t = ops.conv1d_packed(r, c1.packed(ops.PACK_PLAIN), c1.bias.detach(), C, k, 1, pad1, act="lrelu_s",
+                              act_slope=slope, dilation=d, in_slope=slope)
+        # the last pair of a block writes (conv + bias + r) straight into the stage sum
+        r = ops.conv1d_packed(t, c2.packed(ops.PACK_PLAIN), c2.bias.detach(), C, k, 1, pad2, add=r,
+                              out=acc if last else None, accumulate=last and acc is not None)
+        return r, t, (r if last else acc)
+
+
+class _Train:
+    """Generator._walk's sites in training: autograd Functions on the effective weights and the pre-activations."""
+
+    @staticmethod
+    def conv(c, x, Co, k, pad, in_slope=1.0, alpha=1.0, act=None):
+        return ag.voc_conv(x, c.effective_weight(), c.bias, 1, pad, in_slope, alpha, act)
+
+    @staticmethod
+    def up(c, x, Co, k, u, slope, alpha):
+        return ag.voc_up(x, c.effective_weight(), c.bias, u, slope, alpha)
+
+    @staticmethod
+    def pair(c1, c2, r, k, d, pad1, pad2, slope, acc, last):
+        r, t = ag.voc_pair(r, c1.effective_weight(), c1.bias, c2.effective_weight(), c2.bias, d, pad1, pad2, slope)
+        if last:
+            acc = r if acc is None else acc + r
+        return r, t, acc
 
 
 class Generator(nn.Module):
@@ -127,37 +163,40 @@ class Generator(nn.Module):
         self.conv_pre.remove_weight_norm()
         self.conv_post.remove_weight_norm()
 
+    def _walk(self, x, site, taps=None):
+        """conv_pre; per stage an upsampler and num_kernels ResBlocks of dilation pairs, summed; conv_post.  `site`
+        (_Infer or _Train) runs each convolution, upsampler and pair; `taps`: see forward_train."""
+        h, nk, c0 = self.h, self.num_kernels, self.h.upsample_initial_channel
+        x = site.conv(self.conv_pre, x.contiguous(), c0, 7, 3)
+        scale = 1.0
+        for i, (u, uk) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
+            if taps is not None:
+                taps["ups.%d" % i] = x
+            x = site.up(self.ups[i], x, c0 // (2 ** (i + 1)), uk, u, LRELU_SLOPE, scale)
+            acc = None
+            for jj in range(i * nk, (i + 1) * nk):
+                rb = self.resblocks[jj]
+                k, r = rb.kernel_size, x
+                for m, d in enumerate(rb.dilation):
+                    rin = r
+                    r, t, acc = site.pair(rb.convs1[m], rb.convs2[m], rin, k, d, (k * d - d) // 2, (k - 1) // 2,
+                                          LRELU_SLOPE, acc, m == len(rb.dilation) - 1)
+                    if taps is not None:
+                        taps["resblocks.%d.convs1.%d" % (jj, m)] = rin
+                        taps["resblocks.%d.convs2.%d" % (jj, m)] = t
+            x = acc                       # = num_kernels * (xs / num_kernels); the division rides on the next conv
+            scale = 1.0 / self.num_kernels
+        if taps is not None:
+            taps["conv_post"] = x
+        # F.leaky_relu(x) with the DEFAULT slope 0.01 (hifigan/models.py:161), conv_post, tanh
+        return site.conv(self.conv_post, x, 1, 7, 3, in_slope=0.01, alpha=scale, act="tanh")
+
     @torch.no_grad()
     def forward(self, x):
         """x: mel [B, 80, L] -> [B, 1, L * prod(upsample_rates)]."""
         if not x.is_cuda:
             raise _lib.MixganHipError("hifigan.Generator on %s: the HIP path has no CPU fallback" % x.device)
-        h = self.h
-        x = x.contiguous()
-        c0 = h.upsample_initial_channel
-        x = ops.conv1d_packed(x, self.conv_pre.packed(ops.PACK_PLAIN), self.conv_pre.bias.detach(), c0, 7, 1, 3)
-        scale = 1.0
-        for i, (u, k) in enumerate(zip(h.upsample_rates, h.upsample_kernel_sizes)):
-            up = self.ups[i]
-            co = c0 // (2 ** (i + 1))
-            if k == 2 * u and u in (2, 4, 8):     # polyphase: 3-tap GEMM with co*u rows, lrelu fused in staging
-                x = ops.conv_transpose1d_packed(x, up.packed(ops.PACK_TPOSE), up.bias.detach(), co, u,
-                                                in_slope=LRELU_SLOPE, alpha=scale)
-            else:                                 # general (k, u): lrelu + zero insertion, flipped stride-1 conv
-                L = x.shape[2]
-                pad = (k - u) // 2
-                z = ops.upsample_zero(x, u, (L - 1) * u + 1, slope=LRELU_SLOPE)
-                x = ops.conv1d_packed(z, up.packed(ops.PACK_DGRAD), up.bias.detach(), co, k, 1, k - 1 - pad,
-                                      alpha=scale, Lout=(L - 1) * u - 2 * pad + k)
-            acc = torch.empty_like(x)
-            for j in range(self.num_kernels):
-                self.resblocks[i * self.num_kernels + j].forward_cm(x, acc, j == 0)
-            x = acc                       # = num_kernels * (xs / num_kernels); the division rides on the next conv
-            scale = 1.0 / self.num_kernels
-        # F.leaky_relu(x) with the DEFAULT slope 0.01 (hifigan/models.py:161), conv_post, tanh
-        return ops.conv1d_packed(x, self.conv_post.packed(ops.PACK_PLAIN), self.conv_post.bias.detach(), 1, 7, 1, 3,
-                                 act="tanh", alpha=scale, in_slope=0.01)
-
+        return self._walk(x, _Infer)
 
     def forward_train(self, x, taps=None):
         """x: mel [B, 80, L] -> [B, 1, L * prod(upsample_rates)] as an autograd tensor: gradients reach every
@@ -167,40 +206,13 @@ class Generator(nn.Module):
         upsampler i, "resblocks.j.convs1.m" / "resblocks.j.convs2.m" the inputs of the two convolutions of a pair,
         "conv_post" the input of the last convolution (stage sums are kept undivided: the 1/num_kernels rides on the
         next convolution and does not move a sign)."""
-        from . import autograd as ag
         if not x.is_cuda:
             raise _lib.MixganHipError("hifigan.Generator on %s: the HIP path has no CPU fallback" % x.device)
-        h = self.h
-        for u, k in zip(h.upsample_rates, h.upsample_kernel_sizes):
-            if k != 2 * u or u not in (2, 4, 8):
+        for u, k in zip(self.h.upsample_rates, self.h.upsample_kernel_sizes):
+            if not _polyphase(k, u):
                 raise _lib.MixganHipError("forward_train: upsampler (kernel %d, stride %d) has no HIP backward; only "
                                           "kernel = 2 * stride with stride in {2, 4, 8}" % (k, u))
-        x = ag.voc_conv(x.contiguous(), self.conv_pre.effective_weight(), self.conv_pre.bias, 1, 3)
-        scale = 1.0
-        for i, u in enumerate(h.upsample_rates):
-            up = self.ups[i]
-            if taps is not None:
-                taps["ups.%d" % i] = x
-            x = ag.voc_up(x, up.effective_weight(), up.bias, u, LRELU_SLOPE, scale)
-            acc = None
-            for j in range(self.num_kernels):
-                jj = i * self.num_kernels + j
-                rb = self.resblocks[jj]
-                r = x
-                for m, d in enumerate(rb.dilation):
-                    c1, c2 = rb.convs1[m], rb.convs2[m]
-                    rin = r
-                    r, t = ag.voc_pair(rin, c1.effective_weight(), c1.bias, c2.effective_weight(), c2.bias, d, LRELU_SLOPE)
-                    if taps is not None:
-                        taps["resblocks.%d.convs1.%d" % (jj, m)] = rin
-                        taps["resblocks.%d.convs2.%d" % (jj, m)] = t
-                acc = r if acc is None else acc + r
-            x = acc
-            scale = 1.0 / self.num_kernels
-        if taps is not None:
-            taps["conv_post"] = x
-        return ag.voc_conv(x, self.conv_post.effective_weight(), self.conv_post.bias, 1, 3, in_slope=0.01, alpha=scale,
-                           act="tanh")
+        return self._walk(x, _Train, taps)
 
 
 class AttrDict(dict):

@@ -1,5 +1,6 @@
-"""Generator half of HiFi-GAN training on the HIP path: vocoder.Generator.forward_train, HiFi-GAN's mel-reconstruction
-loss through audio.TacotronSTFT.mel_spectrogram_diff, and checkpoints that vocoder.get_vocoder loads.
+"""HiFi-GAN training on the HIP path: vocoder.Generator.forward_train (the generator's one walk with its training sites),
+the mel-reconstruction loss through audio.TacotronSTFT.mel_spectrogram_diff, and checkpoints that vocoder.get_vocoder
+loads.  The two trainers share the optimizer rule, the mel-L1 term and the checkpoint helpers below.
 
 GeneratorTrainer trains on the mel term alone.  VocoderGANTrainer is HiFi-GAN's full step: the discriminator phase and
 the generator phase with the adversarial and feature-matching terms (losses.hifigan_*: the fused HIP loss kernels), over
@@ -33,6 +34,32 @@ def sample_segments(mels, wavs, mel_lens, frames=32, generator=None, hop=256):
     return mel, wav, torch.tensor(offs, dtype=torch.int64)
 
 
+def _optimizer(optimizer, params, lr, betas):
+    """None -> torch.optim.AdamW; a class is built as optimizer(params, lr=lr); an instance is used as it is."""
+    if optimizer is None:
+        return torch.optim.AdamW(params, lr=lr, betas=betas)
+    return optimizer(params, lr=lr) if isinstance(optimizer, type) else optimizer
+
+
+def _mel_l1(stft, y_hat, y):
+    """L1 between the differentiable log-mel of y_hat [B, N] and the log-mel of y [B, N], over the common frames."""
+    m_hat = stft.mel_spectrogram_diff(y_hat)
+    with torch.no_grad():
+        m_ref = stft.mel_spectrogram_diff(y)
+    T = min(m_hat.shape[2], m_ref.shape[2])
+    return F.l1_loss(m_hat[:, :, :T], m_ref[:, :, :T])
+
+
+def _cpu_state(module):
+    return {k: v.detach().cpu() for k, v in module.state_dict().items()}
+
+
+def _load_present(ckpt, **targets):
+    for key, obj in targets.items():
+        if key in ckpt:
+            obj.load_state_dict(ckpt[key])
+
+
 class GeneratorTrainer:
     """One optimizer over a vocoder.Generator with the mel term of HiFi-GAN's generator loss.
 
@@ -45,11 +72,7 @@ class GeneratorTrainer:
         self.stft = stft
         self.lambda_mel = float(lambda_mel)
         params = [p for p in generator.parameters() if p.requires_grad]
-        if optimizer is None:
-            optimizer = torch.optim.AdamW(params, lr=lr, betas=betas)
-        elif isinstance(optimizer, type):
-            optimizer = optimizer(params, lr=lr)
-        self.optimizer = optimizer
+        self.optimizer = _optimizer(optimizer, params, lr, betas)
         self.scheduler = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, gamma=lr_decay)
         self.steps = 0
 
@@ -58,11 +81,7 @@ class GeneratorTrainer:
         y_hat = self.generator.forward_train(mel)
         if wav.dim() == 3:
             wav = wav.squeeze(1)
-        m_hat = self.stft.mel_spectrogram_diff(y_hat.squeeze(1))
-        with torch.no_grad():
-            m_ref = self.stft.mel_spectrogram_diff(wav)
-        T = min(m_hat.shape[2], m_ref.shape[2])
-        return self.lambda_mel * F.l1_loss(m_hat[:, :, :T], m_ref[:, :, :T]), y_hat
+        return self.lambda_mel * _mel_l1(self.stft, y_hat.squeeze(1), wav), y_hat
 
     def step(self, mel, wav):
         """mel [B, 80, F], wav [B, 256 F]: forward, loss, backward, optimizer step.  Returns {"loss", "mel_l1"} as
@@ -83,17 +102,13 @@ class GeneratorTrainer:
 
     def save(self, path):
         """{"generator": state_dict, ...}: the layout vocoder.get_vocoder(..., checkpoint_path=path) loads."""
-        torch.save({"generator": {k: v.detach().cpu() for k, v in self.generator.state_dict().items()},
-                    "optimizer": self.optimizer.state_dict(), "scheduler": self.scheduler.state_dict(),
-                    "steps": self.steps}, path)
+        torch.save({"generator": _cpu_state(self.generator), "optimizer": self.optimizer.state_dict(),
+                    "scheduler": self.scheduler.state_dict(), "steps": self.steps}, path)
 
     def load(self, path):
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
         self.generator.load_state_dict(ckpt["generator"])
-        if "optimizer" in ckpt:
-            self.optimizer.load_state_dict(ckpt["optimizer"])
-        if "scheduler" in ckpt:
-            self.scheduler.load_state_dict(ckpt["scheduler"])
+        _load_present(ckpt, optimizer=self.optimizer, scheduler=self.scheduler)
         self.steps = int(ckpt.get("steps", 0))
         return self
 
@@ -121,13 +136,9 @@ class VocoderGANTrainer:
         self.lambda_mel = float(lambda_mel)
         g_params = [p for p in generator.parameters() if p.requires_grad]
         self._d_params = [p for d in self.discriminators.values() for p in d.parameters() if p.requires_grad]
-        if optimizer is None:
-            make = lambda ps: torch.optim.AdamW(ps, lr=lr, betas=betas)  # noqa: E731
-        elif isinstance(optimizer, type):
-            make = lambda ps: optimizer(ps, lr=lr)  # noqa: E731
-        else:
+        if optimizer is not None and not isinstance(optimizer, type):
             raise TypeError("optimizer: None or an optimizer class (two instances are built)")
-        self.optim_g, self.optim_d = make(g_params), make(self._d_params)
+        self.optim_g, self.optim_d = (_optimizer(optimizer, ps, lr, betas) for ps in (g_params, self._d_params))
         self.scheduler_g = torch.optim.lr_scheduler.ExponentialLR(self.optim_g, gamma=lr_decay)
         self.scheduler_d = torch.optim.lr_scheduler.ExponentialLR(self.optim_d, gamma=lr_decay)
         self.steps = 0
@@ -161,11 +172,7 @@ class VocoderGANTrainer:
         self.optim_d.step()
 
         self.optim_g.zero_grad(set_to_none=True)
-        m_hat = self.stft.mel_spectrogram_diff(y_hat.squeeze(1))
-        with torch.no_grad():
-            m_ref = self.stft.mel_spectrogram_diff(y.squeeze(1))
-        T = min(m_hat.shape[2], m_ref.shape[2])
-        mel_l1 = F.l1_loss(m_hat[:, :, :T], m_ref[:, :, :T])
+        mel_l1 = _mel_l1(self.stft, y_hat.squeeze(1), y.squeeze(1))
         for p in self._d_params:
             p.requires_grad_(False)
         try:
@@ -194,10 +201,7 @@ class VocoderGANTrainer:
     def save(self, path):
         """{"generator": state_dict, <name>: state_dict per discriminator, "optim_g", "optim_d", "steps", ...}: the
         "generator" entry is what vocoder.get_vocoder(..., checkpoint_path=path) loads."""
-        cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}  # noqa: E731
-        ckpt = {"generator": cpu(self.generator.state_dict())}
-        for name, d in self.discriminators.items():
-            ckpt[name] = cpu(d.state_dict())
+        ckpt = {name: _cpu_state(m) for name, m in [("generator", self.generator), *self.discriminators.items()]}
         ckpt.update({"optim_g": self.optim_g.state_dict(), "optim_d": self.optim_d.state_dict(),
                      "sched_g": self.scheduler_g.state_dict(), "sched_d": self.scheduler_d.state_dict(),
                      "steps": self.steps})
@@ -208,9 +212,7 @@ class VocoderGANTrainer:
         self.generator.load_state_dict(ckpt["generator"])
         for name, d in self.discriminators.items():
             d.load_state_dict(ckpt[name])
-        for key, obj in (("optim_g", self.optim_g), ("optim_d", self.optim_d), ("sched_g", self.scheduler_g),
-                         ("sched_d", self.scheduler_d)):
-            if key in ckpt:
-                obj.load_state_dict(ckpt[key])
+        _load_present(ckpt, optim_g=self.optim_g, optim_d=self.optim_d, sched_g=self.scheduler_g,
+                      sched_d=self.scheduler_d)
         self.steps = int(ckpt.get("steps", 0))
         return self

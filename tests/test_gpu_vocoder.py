@@ -113,6 +113,48 @@ def test_conv_transpose_polyphase(mg, u, Ci, Co, B, L):
     assert_close(y.cpu(), ref, 1e-5, "polyphase conv transpose")
 
 
+MIXED = dict(upsample_rates=(4, 2), upsample_kernel_sizes=(7, 4), upsample_initial_channel=128,
+             resblock_kernel_sizes=(3, 7), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5)))
+
+
+@pytest.fixture(scope="module")
+def mixed(mg):
+    """A generator whose first upsampler (k 7, stride 4) takes the zero-insertion branch of the walk and whose second
+    (k 4, stride 2) the polyphase one; fan-in scaled weights, weight_g pushed off the norm, from a fixed seed."""
+    G = mg.vocoder.Generator(types.SimpleNamespace(**MIXED))
+    gen = torch.Generator().manual_seed(1207)
+    with torch.no_grad():
+        for name, p in sorted(G.named_parameters()):
+            if name.endswith("weight_v"):
+                p.copy_(torch.randn(p.shape, generator=gen) / (p[0].numel()) ** 0.5)
+            elif name.endswith("bias"):
+                p.copy_(torch.rand(p.shape, generator=gen) * 0.2 - 0.1)
+        for name, p in sorted(G.named_parameters()):
+            if name.endswith("weight_g"):
+                v = G.get_parameter(name[:-1] + "v")
+                p.copy_(v.flatten(1).norm(dim=1).view(-1, 1, 1) * (0.5 + torch.rand(p.shape, generator=gen)))
+    W = {k: v.detach().double() for k, v in G.state_dict().items()}
+    return G.cuda().eval(), W
+
+
+@pytest.mark.parametrize("B,L", [(2, 5), (1, 1)])
+def test_generator_with_mixed_upsamplers_vs_oracle(mg, mixed, B, L):
+    """The zero-insertion upsampler inside the walk (not only as an op), followed by a polyphase stage, against the
+    float64 oracle; the output length follows (L - 1) u - 2 pad + k per stage."""
+    G, W = mixed
+    mel = torch.from_numpy(np.random.default_rng(40 + L).uniform(-11.5, 2.0, (B, 80, L)).astype(np.float32))
+    ref = R.hifigan_forward(W, mel.double(), MIXED)
+    n = L
+    for u, k in zip(MIXED["upsample_rates"], MIXED["upsample_kernel_sizes"]):
+        n = (n - 1) * u - 2 * ((k - u) // 2) + k
+    assert tuple(ref.shape) == (B, 1, n)
+    y = G(mel.cuda())
+    assert y.dtype == torch.float32 and tuple(y.shape) == (B, 1, n)
+    assert_close(y.cpu().double(), ref, TOL, "hifigan mixed upsamplers B=%d L=%d" % (B, L))
+    with pytest.raises(mg._lib.MixganHipError):
+        G.forward_train(mel.cuda())
+
+
 def test_generator_cpu_input_fails_loudly(mg):
     G = mg.vocoder.Generator(_h())
     with pytest.raises(mg._lib.MixganHipError):

@@ -126,3 +126,65 @@ def test_reference_helper_masks_of_its_own_run_change_nothing(manifest, dtype):
                 assert torch.equal(a[k][n], b[k][n]), n
         else:
             assert a[k].dtype == dtype and torch.equal(a[k], b[k]), k
+
+
+def test_inference_and_training_walk_the_same_sites(monkeypatch):
+    """Generator._walk is the one traversal: with the library calls of the inference sites and the autograd entry points
+    of the training sites replaced by shape-propagating recorders on CPU tensors, both modes visit the same sequence of
+    (module, dilation, padding, alpha, leaky-ReLU slope on the input) for HiFi-GAN V1, every convolution once.  The
+    inference path's fused post-activation counts as the next convolution's input slope."""
+    from oracle import refmath as R
+    from mixgan_tts_amd import ops, autograd as ag, vocoder
+    G = vocoder.Generator(types.SimpleNamespace(**R.HIFIGAN_V1))
+    path = {p.data_ptr(): n[:-len(".bias")] for n, p in G.named_parameters() if n.endswith(".bias")}
+    sites = []
+
+    def conv1d_packed(x, packed, bias, Co, K, stride=1, padding=0, act=None, alpha=1.0, add=None, out=None,
+                      accumulate=False, dilation=1, in_slope=1.0, act_slope=0.0):
+        fused = getattr(x, "post_slope", None)      # the producer's epilogue already applied this leaky ReLU
+        assert fused is None or in_slope == 1.0
+        sites.append((path[bias.data_ptr()], dilation, padding, alpha, in_slope if fused is None else fused))
+        assert stride == 1 and (add is None or add.shape == x.shape) and (accumulate is False or out is not None)
+        y = out if out is not None else torch.zeros(x.shape[0], Co, x.shape[2] + 2 * padding - dilation * (K - 1))
+        if act == "lrelu_s":
+            y.post_slope = act_slope
+        return y
+
+    def conv_transpose1d_packed(x, packed, bias, Co, u, in_slope=1.0, alpha=1.0):
+        sites.append((path[bias.data_ptr()], 1, u // 2, alpha, in_slope))       # polyphase: padding u/2 by construction
+        return torch.zeros(x.shape[0], Co, u * x.shape[2])
+
+    def voc_conv(x, w, b, dil, pad, in_slope=1.0, alpha=1.0, act=None):
+        sites.append((path[b.data_ptr()], dil, pad, alpha, in_slope))
+        return torch.zeros(x.shape[0], w.shape[0], x.shape[2] + 2 * pad - dil * (w.shape[2] - 1))
+
+    def voc_up(x, w, b, u, slope, alpha):
+        sites.append((path[b.data_ptr()], 1, u // 2, alpha, slope))
+        return torch.zeros(x.shape[0], w.shape[1], u * x.shape[2])
+
+    def voc_pair(r, w1, b1, w2, b2, dil, pad1, pad2, slope):
+        sites.append((path[b1.data_ptr()], dil, pad1, 1.0, slope))
+        sites.append((path[b2.data_ptr()], 1, pad2, 1.0, slope))
+        return torch.zeros_like(r), torch.zeros_like(r)
+
+    monkeypatch.setattr(ops, "pack_conv_weight", lambda w, mode=None, out=None: w)
+    monkeypatch.setattr(ops, "pack_conv_transpose_weight", lambda w: w)
+    monkeypatch.setattr(ops, "conv1d_packed", conv1d_packed)
+    monkeypatch.setattr(ops, "conv_transpose1d_packed", conv_transpose1d_packed)
+    monkeypatch.setattr(ag, "voc_conv", voc_conv)
+    monkeypatch.setattr(ag, "voc_up", voc_up)
+    monkeypatch.setattr(ag, "voc_pair", voc_pair)
+    mel = torch.zeros(1, 80, 2)
+    with torch.no_grad():
+        y = G._walk(mel, vocoder._Infer)
+    infer, sites = sites, []
+    taps = {}
+    y_train = G._walk(mel, vocoder._Train, taps)
+    assert tuple(y.shape) == tuple(y_train.shape) == (1, 1, 512)
+    assert infer == sites
+    assert sorted(s[0] for s in sites) == sorted(path.values()) and len(sites) == 1 + 4 + 12 * 6 + 1
+    assert sites[0] == ("conv_pre", 1, 3, 1.0, 1.0) and sites[1] == ("ups.0", 1, 4, 1.0, 0.1)
+    assert sites[2] == ("resblocks.0.convs1.0", 1, 1, 1.0, 0.1) and sites[-1] == ("conv_post", 1, 3, 1.0 / 3, 0.01)
+    assert sites[-2] == ("resblocks.11.convs2.2", 1, 5, 1.0, 0.1) and sites[-3] == ("resblocks.11.convs1.2", 5, 25, 1.0, 0.1)
+    assert sites[1 + 1 + 18] == ("ups.1", 1, 4, 1.0 / 3, 0.1)
+    assert len(taps) == 4 + 12 * 6 + 1
