@@ -544,6 +544,9 @@ int mg_diffuse_trace_bwd(const float *g, const float *x_start, const float *spec
 int mg_bgemm(const float *A, const float *B, float *C, int M, int N, int K, int batch, int heads, long a_ms, long a_ks,
              long a_bs, long a_hs, long b_ks, long b_ns, long b_bs, long b_hs, long c_ms, long c_bs, long c_hs,
              float alpha, int accumulate, void *stream);
+/* 64 or 128: the workgroup tile mg_bgemm launches for these sizes (64 x 64 while the 128 x 128 tiles would number
+ * fewer than 512).  MG_BGEMM_TILE=64|128 pins it; read on every call, any other value is ignored. */
+int mg_bgemm_tile(int M, int N, int batch, int heads);
 /* In place: S [B*H, L, L] -> softmax over keys of scale*S with padded keys (key_pad [B, L] != 0) at -inf. */
 int mg_softmax_rows_fwd(float *S, const uint8_t *key_pad, int B, int H, int L, float scale, void *stream);
 /* In place on dP: dS = scale * P o (dP - rowsum(dP o P)). */

@@ -108,6 +108,7 @@ def _signatures():
         "mg_upsample_zero_act": (i, [vp, vp, i, i, i, i, f, vp]),
         "mg_diffuse_trace_bwd": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_bgemm": (i, [vp, vp, vp, i, i, i, i, i] + [lg] * 11 + [f, i, vp]),
+        "mg_bgemm_tile": (i, [i, i, i, i]),
         "mg_softmax_rows_fwd": (i, [vp, vp, i, i, i, f, vp]),
         "mg_softmax_rows_bwd": (i, [vp, vp, i, i, i, f, vp]),
         "mg_layernorm_cm_train_fwd": (i, [vp, vp, f, vp, vp, vp, vp, vp, vp, i, i, i, f, vp]),

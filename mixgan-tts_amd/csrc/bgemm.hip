@@ -14,10 +14,12 @@
 // mg_bgemm: C[z][m][n] (+)= alpha * sum_k A[z](m,k) B[z](k,n), z = (b, h) with separate batch / head strides,
 // arbitrary element strides for A and B (one of the two strides of each operand must be 1), C row-major.
 // Workgroup tile 128 x 128 x 16, 4 waves as 2 x 2, wave tile 64 x 64 = 2 x 2 accumulators of
-// v_mfma_f32_32x32x2_f32 (64 x 64 / 1 x 1 when that under-fills the chip); operand tiles are staged k-major in
+// v_mfma_f32_32x32x2_f32 (64 x 64 / 1 x 1 when that under-fills the chip: mg_bgemm_tile); operand tiles are staged k-major in
 // LDS ([16][tile + 1]) through registers with the next
 // tile's global loads in flight behind the current tile's 32 MFMAs per wave.
 #include "common.h"
+#include <cstdlib>
+#include <cstring>
 
 struct BgemmArgs {
     const float *A, *B;
@@ -151,6 +153,15 @@ __global__ __launch_bounds__(256, 2) void bgemm_kernel(BgemmArgs a)
     }
 }
 
+// The workgroup tile mg_bgemm launches: 64 while the 128 x 128 tiles would number fewer than 512 (two per CU), else 128.
+extern "C" int mg_bgemm_tile(int M, int N, int batch, int heads)
+{
+    const char *te = std::getenv("MG_BGEMM_TILE");   // tests pin each form
+    if (te && !std::strcmp(te, "64")) return 64;
+    if (te && !std::strcmp(te, "128")) return 128;
+    return (long)mg_cdiv(N, 128) * mg_cdiv(M, 128) * batch * heads < 512 ? 64 : 128;
+}
+
 extern "C" int mg_bgemm(const float *A, const float *B, float *C, int M, int N, int K, int batch, int heads, long a_ms,
                         long a_ks, long a_bs, long a_hs, long b_ks, long b_ns, long b_bs, long b_hs, long c_ms, long c_bs,
                         long c_hs, float alpha, int accumulate, void *stream)
@@ -161,7 +172,7 @@ extern "C" int mg_bgemm(const float *A, const float *B, float *C, int M, int N, 
     BgemmArgs a{A, B, C, M, N, K, heads, a_ms, a_ks, a_bs, a_hs, b_ks, b_ns, b_bs, b_hs, c_ms, c_bs, c_hs, alpha, accumulate};
     const bool amc = a_ms == 1, bnc = b_ns == 1;
     hipStream_t st = (hipStream_t)stream;
-    const bool small = (long)mg_cdiv(N, 128) * mg_cdiv(M, 128) * batch * heads < 512;
+    const bool small = mg_bgemm_tile(M, N, batch, heads) == 64;
 #define BG_LAUNCH(AM, BN)                                                                                     \
     do {                                                                                                      \
         if (small)                                                                                            \

@@ -140,6 +140,19 @@ def assert_close(a, b, tol, what=""):
     assert e <= tol, "%s: max-abs err / max-abs ref = %.3e > %.1e" % (what, e, tol)
 
 
+def bar_for(ref32, ref64, bar):
+    """The project's fallback rule: `bar`, or 8 x the float32 CPU restatement's own error where that exceeds bar / 8."""
+    e = rel_err(ref32.detach().double().numpy(), ref64.detach().numpy())
+    return bar if e <= bar / 8 else 8 * e
+
+
+def check(got, ref32, ref64, bar, what):
+    b = bar_for(ref32, ref64, bar)
+    e = rel_err(got.detach().cpu().double().numpy(), ref64.detach().numpy())
+    print("%-40s err %.3e  bar %.1e" % (what, e, b))
+    assert_close(got.detach().cpu().double(), ref64, b, what)
+
+
 def digest(g):
     g = g.detach().double().cpu()
     corner = g[tuple(slice(0, min(4, s)) for s in g.shape)].float().numpy()

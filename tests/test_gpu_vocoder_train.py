@@ -17,7 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import golden, assert_close, rel_err, load_seeded, seeded, T
+from helpers import golden, assert_close, check, load_seeded, seeded, T
 from oracle import refmath as R
 import hifigan_train_ref as HR
 
@@ -29,19 +29,6 @@ BAR_MAP, BAR_DATA, BAR_PARAM = 2e-5, 5e-5, 1e-4
 def mg():
     import mixgan_tts_amd
     return mixgan_tts_amd
-
-
-def bar_for(ref32, ref64, bar):
-    """The project's fallback rule: `bar`, or 8 x the float32 CPU restatement's own error where that exceeds bar / 8."""
-    e = rel_err(ref32.detach().double().numpy(), ref64.detach().numpy())
-    return bar if e <= bar / 8 else 8 * e
-
-
-def check(got, ref32, ref64, bar, what):
-    b = bar_for(ref32, ref64, bar)
-    e = rel_err(got.detach().cpu().double().numpy(), ref64.detach().numpy())
-    print("%-40s err %.3e  bar %.1e" % (what, e, b))
-    assert_close(got.detach().cpu().double(), ref64, b, what)
 
 
 # ------------------------------------------------------------------------------------------------------------------

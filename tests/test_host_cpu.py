@@ -122,6 +122,27 @@ def test_error_strings_and_arg_checks():
     assert L.mg_conv1d_wgrad_grouped(None, 0, 0, None, 0, 0, None, 0, None, 2, 1, 8, 8, 8, 8, 1, 1, 0, 1.0, 0, None) == _lib.MG_ERR_ARG
 
 
+def test_bgemm_tile_choice_and_pin(monkeypatch):
+    """mg_bgemm_tile: 64 x 64 workgroup tiles while the 128 x 128 ones would number fewer than 512; MG_BGEMM_TILE pins
+    either form, is read on every call, and any other value is ignored."""
+    L = mg.lib()
+    monkeypatch.delenv("MG_BGEMM_TILE", raising=False)
+    cases = [((650, 650, 8, 2), 128),        # 6 * 6 * 16 = 576 tiles: the L x L GEMMs of training from L = 641 on
+             ((640, 640, 8, 2), 64),         # 5 * 5 * 16 = 400
+             ((128, 1500, 8, 2), 64),        # the d-row GEMMs: 1 * 12 * 16 = 192
+             ((200, 200, 16, 8), 128)]       # 2 * 2 * 128 = 512: the threshold itself
+    for args, tile in cases:
+        assert L.mg_bgemm_tile(*args) == tile, args
+    for pin in ("64", "128"):
+        monkeypatch.setenv("MG_BGEMM_TILE", pin)
+        for args, _ in cases:
+            assert L.mg_bgemm_tile(*args) == int(pin), (pin, args)
+    for junk in ("", "0", "32", "256", "64x64", "128 ", "big"):
+        monkeypatch.setenv("MG_BGEMM_TILE", junk)
+        for args, tile in cases:
+            assert L.mg_bgemm_tile(*args) == tile, (junk, args)
+
+
 def test_schedule_matches_reference_bits():
     g = golden("schedule")
     for mode, T in [("vpsde", 1), ("vpsde", 4), ("vpsde", 100), ("vpsde", 1000), ("linear", 4), ("cosine", 4)]:
