@@ -932,6 +932,52 @@ size_t mg_dtw_workspace_bytes(int B, int Ta, int Tb);
 int mg_dtw(const float *a, const float *b, const int *a_len, const int *b_len, int B, int Ta, int Tb, int D,
            float *total, int *path_len, int *path, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ HiFi-GAN multi-scale discriminator (msd.hip)
+ * Grouped strided Conv1d, channel-major [N, C, L], weight in torch's [Co, Ci/G, K] layout:
+ *   out[n, g Cog + co, l] = act(sum_{ci<Cig, k<K} w[g Cog + co, ci, k] in[n, g Cig + ci, l s + k - pad] + bias),
+ * in out of range = 0, Lout = (Lin + 2 pad - K) / s + 1 (MG_ERR_SHAPE otherwise), act MG_ACT_NONE or MG_ACT_LRELU with
+ * the runtime `slope`.  Instantiated (Cig, Cog, K, s): (32,32,41,2) (8,16,41,2) (16,32,41,4) (32,64,41,4) (64,64,41,1),
+ * the DiscriminatorS stack, for any G >= 1; every other form is MG_ERR_SHAPE (a packed size of 0) before any launch,
+ * a null pointer MG_ERR_ARG.  `packed` is a derived cache in MFMA fragment order, per group:
+ *   MG_GCONV_FWD   [G][Cog/32 up][K][Cig/2][64]: lane -> w[row lane&31, ci 2q + lane>>5, tap]
+ *   MG_GCONV_DGRAD [G][Cig/32 up][K taps ordered by (k mod s, k div s)][Cog/2][64]: lane -> w[co 2q + lane>>5, row lane&31, tap]
+ * rows past Cog (Cig) are zero. */
+#define MG_GCONV_FWD 0
+#define MG_GCONV_DGRAD 1
+size_t mg_gconv_packed_floats(int Ci, int Co, int K, int stride, int groups, int mode);
+int mg_gconv_pack(const float *w, float *packed, int Ci, int Co, int K, int stride, int groups, int mode, void *stream);
+int mg_gconv1d_fwd(const float *in, const float *packed, const float *bias, float *out, int N, int Ci, int Lin, int Co,
+                   int Lout, int K, int stride, int pad, int groups, int act, float slope, void *stream);
+/* Data gradient of mg_gconv1d_fwd in polyphase form (per output phase (m + pad) mod s a stride-1 convolution over dy with
+ * ceil(K / s) taps; no zero insertion):
+ *   dx[n, g Cig + ci, m] = (sum_{co, k : (m + pad - k) = s l} w[g Cog + co, ci, k] dy[n, g Cog + co, l] + add) * mask,
+ * mask = map > 0 ? 1 : slope from the layer below's stored activated map (NULL: no mask); add (NULL: none) is a
+ * gradient that reaches the same map from elsewhere.  map, add and dx are [N, Ci, Lin]; positions no output read get
+ * exactly add * mask.  packed: the MG_GCONV_DGRAD form. */
+int mg_gconv1d_dgrad(const float *dy, const float *packed, const float *map, const float *add, float *dx, int N, int Ci,
+                     int Lin, int Co, int Lout, int K, int stride, int pad, int groups, float slope, void *stream);
+/* dw[g Cog + co, ci, k] = sum_{n,l} dy[n, g Cog + co, l] x[n, g Cig + ci, l s + k - pad].  A workgroup stages 64 frames
+ * of dy and the matching x window once and takes every tap from it as an address offset; workgroups split (n, l) and
+ * write partial tiles to `scratch`, a second kernel adds them in ascending order: two runs are bit-identical.  The bias
+ * gradient is mg_rowsum of dy. */
+size_t mg_gconv1d_wgrad_scratch_floats(int N, int Ci, int Co, int Lout, int K, int stride, int groups);
+int mg_gconv1d_wgrad(const float *dy, const float *x, float *dw, float *scratch, size_t scratch_floats, int N, int Ci,
+                     int Lin, int Co, int Lout, int K, int stride, int pad, int groups, void *stream);
+/* The first layer, Conv1d(1, Co, K, stride 1): in [N, 1, L], w [Co, 1, K], Lout = L + 2 pad - K + 1 >= 1, K <= 16,
+ * plain VALU kernels (one input channel leaves the matrix pipe nothing to reduce over).  fwd applies act as above;
+ * dgrad: dx[n, m] = sum_{co,k} w[co,k] dy[n, co, m + pad - k]; wgrad writes dw [Co, K] and db [Co] (db may be NULL)
+ * through partial sums in `scratch` added in a fixed order. */
+int mg_conv1d_c1_fwd(const float *in, const float *w, const float *bias, float *out, int N, int L, int Co, int K, int pad,
+                     int act, float slope, void *stream);
+int mg_conv1d_c1_dgrad(const float *dy, const float *w, float *dx, int N, int L, int Co, int K, int pad, void *stream);
+size_t mg_conv1d_c1_wgrad_scratch_floats(int N, int L, int Co, int K);
+int mg_conv1d_c1_wgrad(const float *dy, const float *x, float *dw, float *db, float *scratch, size_t scratch_floats,
+                       int N, int L, int Co, int K, int pad, void *stream);
+/* AvgPool1d(4, 2, padding 2), padding counted (always / 4): in [rows, L] -> out [rows, L / 2 + 1], and its backward
+ * dx[r, m] = (dy[r, (m + 2) / 2] + dy[r, (m + 2) / 2 - 1]) / 4 over the outputs that exist. */
+int mg_avgpool4s2_fwd(const float *in, float *out, int rows, int L, void *stream);
+int mg_avgpool4s2_bwd(const float *dy, float *dx, int rows, int L, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3
  * gated convolution of a residual layer) with HIP events recorded on the launch stream.

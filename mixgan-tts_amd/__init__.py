@@ -45,5 +45,7 @@ from .metrics import (DtwGeometryError, mel_cepstra, dtw, mel_cepstral_distortio
 from . import vocoder_train  # noqa: F401
 from .vocoder_train import GeneratorTrainer, VocoderGANTrainer, sample_segments  # noqa: F401
 from .losses import hifigan_discriminator_loss, hifigan_generator_loss, hifigan_feature_loss  # noqa: F401
+from . import hifigan_discriminators  # noqa: F401
+from .hifigan_discriminators import DiscriminatorS, MultiScaleDiscriminator  # noqa: F401
 
 __version__ = "0.1.0"

@@ -36,6 +36,7 @@ MG_PITCH_N, MG_PITCH_W, MG_PITCH_K, MG_PITCH_PARAMS = 1024, 512, 4, 7
  MG_PITCH_P_GATE) = range(MG_PITCH_PARAMS)
 MG_ALIGN_MAX_D, MG_ALIGN_MAX_G, MG_ALIGN_MAX_S, MG_ALIGN_MAX_T = 128, 1024, 2048, 4096
 MG_CEPSTRA_MAX_M, MG_DTW_MAX_T, MG_DTW_MAX_D = 128, 4096, 64
+MG_GCONV_FWD, MG_GCONV_DGRAD = 0, 1                                               # mg_gconv_pack modes
 
 
 class LossTerm(ctypes.Structure):
@@ -238,6 +239,18 @@ def _signatures():
         "mg_conv_transpose1d_wgrad": (i, [vp, vp, vp, vp, i, i, i, i, i, f, f, i, vp]),
         "mg_stft_mel_bwd_workspace_bytes": (sz, [i, i]),
         "mg_stft_mel_bwd": (i, [vp, lg, vp, i, i, i, vp, vp, vp, vp, i, vp, i, vp, lg, vp, sz, vp]),
+        "mg_gconv_packed_floats": (sz, [i, i, i, i, i, i]),
+        "mg_gconv_pack": (i, [vp, vp, i, i, i, i, i, i, vp]),
+        "mg_gconv1d_fwd": (i, [vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f, vp]),
+        "mg_gconv1d_dgrad": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, f, vp]),
+        "mg_gconv1d_wgrad_scratch_floats": (sz, [i, i, i, i, i, i, i]),
+        "mg_gconv1d_wgrad": (i, [vp, vp, vp, vp, sz, i, i, i, i, i, i, i, i, i, vp]),
+        "mg_conv1d_c1_fwd": (i, [vp, vp, vp, vp, i, i, i, i, i, i, f, vp]),
+        "mg_conv1d_c1_dgrad": (i, [vp, vp, vp, i, i, i, i, i, vp]),
+        "mg_conv1d_c1_wgrad_scratch_floats": (sz, [i, i, i, i]),
+        "mg_conv1d_c1_wgrad": (i, [vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]),
+        "mg_avgpool4s2_fwd": (i, [vp, vp, i, i, vp]),
+        "mg_avgpool4s2_bwd": (i, [vp, vp, i, i, vp]),
     }
 
 

@@ -525,3 +525,125 @@ def voc_pair(r, w1, b1, w2, b2, dil, pad1, pad2, slope):
 
 def voc_up(x, w, b, u, slope, alpha):
     return _VocUpFn.apply(x, w.contiguous(), b, u, slope, alpha)
+
+
+# --------------------------------------------------------------------------------------------------
+# HiFi-GAN multi-scale discriminator (csrc/msd.hip; hifigan_discriminators.py)
+# --------------------------------------------------------------------------------------------------
+class _ScaleStackFn(torch.autograd.Function):
+    """DiscriminatorS' one-channel first layer and the grouped layers above it as ONE node, every layer followed by
+    leaky_relu(slope): x [N, 1, T] -> the activated maps.  params = (w0, b0, w1, b1, ...), effective weights;
+    layers[j] = (stride, groups, padding).  One node so that a map's gradient from outside (feature matching) and the
+    leaky-ReLU mask of the layer below ride in the data-gradient kernel's epilogue; masks come from the stored
+    activated maps (slope > 0 keeps the sign).  Weight / bias / data gradients are computed only where asked for."""
+
+    @staticmethod
+    def forward(ctx, x, slope, layers, *params):
+        _require_cuda(x)
+        x = x.contiguous()
+        ws = [w.detach().contiguous() for w in params[0::2]]
+        bs = [b.detach() for b in params[1::2]]
+        maps = [ops.conv1d_c1_fwd(x, ws[0], bs[0], layers[0][2], slope)]
+        for j in range(1, len(layers)):
+            s, g, pad = layers[j]
+            Co, _, K = ws[j].shape
+            maps.append(ops.gconv1d_fwd(maps[-1], ops.gconv_pack(ws[j], s, g), bs[j], Co, K, s, pad, g, slope))
+        ctx.save_for_backward(x, *maps, *ws)
+        ctx.cfg = (slope, layers)
+        ctx.set_materialize_grads(False)
+        return tuple(maps)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        slope, layers = ctx.cfg
+        n = len(layers)
+        saved = ctx.saved_tensors
+        x, maps, ws = saved[0], saved[1:1 + n], saved[1 + n:]
+        need = ctx.needs_input_grad
+        need_w = [need[3 + 2 * j] for j in range(n)]
+        need_b = [need[4 + 2 * j] for j in range(n)]
+        lowest = 0 if need[0] else min([j for j in range(n) if need_w[j] or need_b[j]], default=n)
+        grads = [None] * (3 + 2 * n)
+        d = None                                   # gradient of layer j's PRE-activation
+        for j in range(n - 1, lowest - 1, -1):
+            if d is None:
+                if gs[j] is None:
+                    continue
+                d = ops.lrelu_bwd(gs[j].contiguous(), maps[j], slope)
+            s, g, pad = layers[j]
+            K = ws[j].shape[2]
+            if j == 0:
+                if need_w[0] or need_b[0]:
+                    dw, db = ops.conv1d_c1_wgrad(d, x, K, pad)
+                    grads[3], grads[4] = (dw if need_w[0] else None), (db if need_b[0] else None)
+                if need[0]:
+                    grads[0] = ops.conv1d_c1_dgrad(d, ws[0], x.shape[2], pad)
+                break
+            below = maps[j - 1]
+            if need_w[j]:
+                grads[3 + 2 * j] = ops.gconv1d_wgrad(d, below, K, s, pad, g)
+            if need_b[j]:
+                grads[4 + 2 * j] = ops.rowsum(d)
+            if j > lowest:
+                add = gs[j - 1]
+                d = ops.gconv1d_dgrad(d, ops.gconv_pack(ws[j], s, g, ops.GCONV_DGRAD), below.shape[1], below.shape[2], K, s,
+                                      pad, g, map=below, add=None if add is None else add.contiguous(), slope=slope)
+        return tuple(grads)
+
+
+def scale_stack(x, slope, layers, *params):
+    return _ScaleStackFn.apply(x, slope, tuple(layers), *params)
+
+
+class _ConvSlopeFn(torch.autograd.Function):
+    """y = leaky_relu(conv1d(x, W, b, padding), slope) (slope None: no activation), stride 1, through the MFMA
+    convolution kernel and its DGRAD pack: _Conv1dFn with a runtime slope.  Saves x, W and the activated y."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, padding, slope):
+        _require_cuda(x)
+        x, w = x.contiguous(), w.detach().contiguous()
+        Co, _, K = w.shape
+        y = ops.conv1d_packed(x, ops.pack_conv_weight(w), b.detach(), Co, K, 1, padding,
+                              act=None if slope is None else "lrelu_s", act_slope=slope or 0.0, split=True)
+        ctx.save_for_backward(x, w, None if slope is None else y)
+        ctx.cfg = (padding, slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, y = ctx.saved_tensors
+        padding, slope = ctx.cfg
+        Co, Ci, K = w.shape
+        g = g.contiguous()
+        d = g if slope is None else ops.lrelu_bwd(g, y, slope)
+        need = ctx.needs_input_grad
+        dw = ops.conv1d_wgrad(d, x, K, 1, padding) if need[1] else None
+        db = ops.rowsum(d) if need[2] else None
+        dx = None
+        if need[0]:
+            dx = ops.conv1d_packed(d, ops.pack_conv_weight(w, ops.PACK_DGRAD), None, Ci, K, 1, K - 1 - padding,
+                                   Lout=x.shape[2], split=True)
+        return dx, dw, db, None, None
+
+
+def conv1d_slope(x, w, b, padding, slope=None):
+    return _ConvSlopeFn.apply(x, w, b, padding, slope)
+
+
+class _AvgPool4s2Fn(torch.autograd.Function):
+    """AvgPool1d(4, 2, padding=2), padding counted."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_cuda(x)
+        ctx.Lin = x.shape[2]
+        return ops.avgpool4s2_fwd(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.avgpool4s2_bwd(g.contiguous(), ctx.Lin)
+
+
+def avgpool4s2(x):
+    return _AvgPool4s2Fn.apply(x)

@@ -1,0 +1,118 @@
+"""HiFi-GAN's multi-scale discriminator (Kong et al. 2020) on the HIP kernels of csrc/msd.hip.
+
+DiscriminatorS / MultiScaleDiscriminator keep the published constructor arguments, attribute names (convs, conv_post,
+discriminators, meanpools), forward(y, y_hat) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs) and the state-dict keys of the torch
+construction (Conv1d under torch.nn.utils.weight_norm / spectral_norm): `bias, weight_g, weight_v` per weight-norm
+layer, `bias, weight_orig` plus the buffers `weight_u, weight_v` per spectral-norm layer.
+
+The effective weight is a torch expression, as vocoder.Generator.effective_weight(): HIP differentiates with respect to
+it and torch carries the gradient to weight_g / weight_v / weight_orig.  Spectral norm is torch's legacy hook: in
+training mode one power iteration per sub-forward under no_grad, updating u and v in place, sigma = u . (W v) with u, v
+constants of the graph; no iteration in eval mode.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import autograd as A
+from ._lib import MixganHipError
+
+LRELU_SLOPE = 0.1
+# (Ci, Co, K, stride, groups, padding) of DiscriminatorS.convs; conv_post is (1024, 1, 3, 1, 1, 1)
+MSD_LAYERS = ((1, 128, 15, 1, 1, 7), (128, 128, 41, 2, 4, 20), (128, 256, 41, 2, 16, 20), (256, 512, 41, 4, 16, 20),
+              (512, 1024, 41, 4, 16, 20), (1024, 1024, 41, 1, 16, 20), (1024, 1024, 5, 1, 1, 2))
+MSD_POST = (1024, 1, 3, 1, 1, 1)
+_STACK = 6      # convs[:6] run as one node of msd.hip kernels; convs[6] and conv_post go through the MFMA conv kernel
+
+
+class NormConv1d(nn.Module):
+    """The parameters of one Conv1d under weight_norm (bias, weight_g, weight_v) or spectral_norm (bias, weight_orig;
+    buffers weight_u, weight_v), initialised as torch initialises them, and the effective weight as a torch expression."""
+
+    def __init__(self, ci, co, k, stride, groups, padding, spectral):
+        super().__init__()
+        self.geometry = (ci, co, k, stride, groups, padding)
+        self.spectral, self.eps = bool(spectral), 1e-12
+        ref = nn.Conv1d(ci, co, k, stride, padding=padding, groups=groups)
+        w = ref.weight.detach()
+        self.bias = nn.Parameter(ref.bias.detach().clone())
+        if spectral:
+            self.weight_orig = nn.Parameter(w.clone())
+            self.register_buffer("weight_u", F.normalize(torch.randn(co), dim=0, eps=self.eps))
+            self.register_buffer("weight_v", F.normalize(torch.randn(w[0].numel()), dim=0, eps=self.eps))
+        else:
+            self.weight_g = nn.Parameter(w.flatten(1).norm(dim=1).view(-1, 1, 1))
+            self.weight_v = nn.Parameter(w.clone())
+
+    def effective_weight(self):
+        """weight_norm: g v / |v| per output row.  spectral_norm: W / sigma after this call's power iteration."""
+        if not self.spectral:
+            v = self.weight_v
+            return v * (self.weight_g / v.flatten(1).norm(dim=1).view(-1, 1, 1))
+        W = self.weight_orig
+        mat = W.flatten(1)
+        u, v = self.weight_u, self.weight_v
+        if self.training:
+            with torch.no_grad():
+                F.normalize(torch.mv(mat.t(), u), dim=0, eps=self.eps, out=v)
+                F.normalize(torch.mv(mat, v), dim=0, eps=self.eps, out=u)
+                u, v = u.clone(), v.clone()
+        return W / torch.dot(u, torch.mv(mat, v))
+
+
+class DiscriminatorS(nn.Module):
+    def __init__(self, use_spectral_norm=False):
+        super().__init__()
+        self.convs = nn.ModuleList([NormConv1d(*g, spectral=use_spectral_norm) for g in MSD_LAYERS])
+        self.conv_post = NormConv1d(*MSD_POST, spectral=use_spectral_norm)
+
+    def forward(self, x):
+        """x [N, 1, T] -> (logits [N, T'], [seven activated maps, conv_post's raw map])."""
+        if not x.is_cuda:
+            raise MixganHipError("DiscriminatorS: tensors must be on the GPU (no CPU fallback)")
+        params = []
+        for conv in self.convs[:_STACK]:
+            params += [conv.effective_weight(), conv.bias]
+        layers = [g[3:] for g in MSD_LAYERS[:_STACK]]
+        fmap = list(A.scale_stack(x, LRELU_SLOPE, layers, *params))
+        last = self.convs[_STACK]
+        fmap.append(A.conv1d_slope(fmap[-1], last.effective_weight(), last.bias, last.geometry[5], LRELU_SLOPE))
+        x = A.conv1d_slope(fmap[-1], self.conv_post.effective_weight(), self.conv_post.bias, MSD_POST[5], None)
+        fmap.append(x)
+        return torch.flatten(x, 1, -1), fmap
+
+
+class MeanPool(nn.Module):
+    """AvgPool1d(4, 2, padding=2)."""
+    kernel_size, stride, padding = 4, 2, 2
+
+    def forward(self, x):
+        return A.avgpool4s2(x)
+
+
+class MultiScaleDiscriminator(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorS(use_spectral_norm=True), DiscriminatorS(), DiscriminatorS()])
+        self.meanpools = nn.ModuleList([MeanPool(), MeanPool()])
+
+    def forward(self, y, y_hat):
+        """The published forward runs every scale on y, then on y_hat.  Scale 0 does exactly that, so that its spectral
+        norm iterates twice and the halves see different weights; scales 1 and 2 (weight norm: one weight for both)
+        and the pools run once on the batch [y; y_hat]."""
+        B = y.shape[0]
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        both = None
+        for i, d in enumerate(self.discriminators):
+            if i == 0:
+                (r, fr), (g, fg) = d(y), d(y_hat)
+            else:
+                both = self.meanpools[i - 1](torch.cat([y, y_hat], 0) if both is None else both)
+                out, fmap = d(both)
+                r, g = out[:B], out[B:]
+                fr, fg = [f[:B] for f in fmap], [f[B:] for f in fmap]
+            y_d_rs.append(r)
+            y_d_gs.append(g)
+            fmap_rs.append(fr)
+            fmap_gs.append(fg)
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs

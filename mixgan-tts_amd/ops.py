@@ -529,3 +529,107 @@ def adam_flat(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None, h
     check(L.mg_adam_flat_dev(fptr(p), fptr(g), fptr(m), fptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
                              float(eps), float(weight_decay), int(step), fptr(grad_scale, True), fptr(hyper, True),
                              stream_ptr()))
+
+
+# ---- HiFi-GAN multi-scale discriminator (csrc/msd.hip)
+GCONV_FWD, GCONV_DGRAD = _lib.MG_GCONV_FWD, _lib.MG_GCONV_DGRAD
+
+
+def gconv_pack(w, stride, groups, mode=GCONV_FWD):
+    """Grouped Conv1d weight [Co, Ci / groups, K] -> the fragment-ordered pack of mg_gconv1d_fwd (GCONV_FWD) or of
+    mg_gconv1d_dgrad (GCONV_DGRAD); raises for a (Ci / G, Co / G, K, stride) the library does not instantiate."""
+    L = _lib.lib()
+    w = w.detach().contiguous()
+    Co, Cig, K = w.shape
+    n = L.mg_gconv_packed_floats(Cig * groups, Co, K, stride, groups, mode)
+    if n == 0:
+        raise _lib.MixganHipError("unsupported grouped conv: weight %s, stride %d, groups %d" % (tuple(w.shape), stride,
+                                                                                                groups))
+    out = torch.empty(n, device=w.device, dtype=torch.float32)
+    check(L.mg_gconv_pack(fptr(w), fptr(out), Cig * groups, Co, K, stride, groups, mode, stream_ptr()))
+    return out
+
+
+def gconv1d_fwd(x, packed, bias, Co, K, stride, padding, groups, slope=None):
+    """act(conv1d(x, w, bias, stride, padding, groups)), act = leaky ReLU with `slope` (None: no activation)."""
+    N, Ci, Lin = x.shape
+    Lout = (Lin + 2 * padding - K) // stride + 1
+    out = torch.empty(N, Co, max(Lout, 0), device=x.device, dtype=torch.float32)
+    check(_lib.lib().mg_gconv1d_fwd(fptr(x), fptr(packed), fptr(bias, True), fptr(out), N, Ci, Lin, Co, Lout, K, stride,
+                                    padding, groups, _lib.MG_ACT_NONE if slope is None else _lib.MG_ACT_LRELU,
+                                    0.0 if slope is None else float(slope), stream_ptr()))
+    return out
+
+
+def gconv1d_dgrad(dy, packed, Ci, Lin, K, stride, padding, groups, map=None, add=None, slope=1.0):
+    """(data gradient of gconv1d_fwd + add) * (map > 0 ? 1 : slope); packed is the GCONV_DGRAD form."""
+    N, Co, Lout = dy.shape
+    dx = torch.empty(N, Ci, Lin, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().mg_gconv1d_dgrad(fptr(dy), fptr(packed), fptr(map, True), fptr(add, True), fptr(dx), N, Ci, Lin, Co,
+                                      Lout, K, stride, padding, groups, float(slope), stream_ptr()))
+    return dx
+
+
+def gconv1d_wgrad(dy, x, K, stride, padding, groups):
+    """dW [Co, Ci / groups, K] of gconv1d_fwd: dy [N, Co, Lout], x [N, Ci, Lin]."""
+    L = _lib.lib()
+    N, Co, Lout = dy.shape
+    _, Ci, Lin = x.shape
+    n = L.mg_gconv1d_wgrad_scratch_floats(N, Ci, Co, Lout, K, stride, groups)
+    if n == 0:
+        raise _lib.MixganHipError("unsupported grouped conv: Ci %d Co %d K %d stride %d groups %d" % (Ci, Co, K, stride,
+                                                                                                      groups))
+    dw = torch.empty(Co, Ci // groups, K, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(n, device=x.device, dtype=torch.float32)
+    check(L.mg_gconv1d_wgrad(fptr(dy), fptr(x), fptr(dw), fptr(scratch), n, N, Ci, Lin, Co, Lout, K, stride, padding,
+                             groups, stream_ptr()))
+    return dw
+
+
+def conv1d_c1_fwd(x, w, bias, padding, slope=None):
+    """act(conv1d(x [N, 1, L], w [Co, 1, K], bias, padding)): the one-input-channel first layer."""
+    N, _, Lin = x.shape
+    Co, _, K = w.shape
+    out = torch.empty(N, Co, Lin + 2 * padding - K + 1, device=x.device, dtype=torch.float32)
+    check(_lib.lib().mg_conv1d_c1_fwd(fptr(x), fptr(w), fptr(bias, True), fptr(out), N, Lin, Co, K, padding,
+                                      _lib.MG_ACT_NONE if slope is None else _lib.MG_ACT_LRELU,
+                                      0.0 if slope is None else float(slope), stream_ptr()))
+    return out
+
+
+def conv1d_c1_dgrad(dy, w, Lin, padding):
+    N, Co, _ = dy.shape
+    dx = torch.empty(N, 1, Lin, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().mg_conv1d_c1_dgrad(fptr(dy), fptr(w), fptr(dx), N, Lin, Co, w.shape[2], padding, stream_ptr()))
+    return dx
+
+
+def conv1d_c1_wgrad(dy, x, K, padding):
+    """(dW [Co, 1, K], db [Co]) of conv1d_c1_fwd."""
+    L = _lib.lib()
+    N, Co, _ = dy.shape
+    Lin = x.shape[2]
+    n = L.mg_conv1d_c1_wgrad_scratch_floats(N, Lin, Co, K)
+    if n == 0:
+        raise _lib.MixganHipError("unsupported first-layer conv: Co %d K %d" % (Co, K))
+    dw = torch.empty(Co, 1, K, device=x.device, dtype=torch.float32)
+    db = torch.empty(Co, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(n, device=x.device, dtype=torch.float32)
+    check(L.mg_conv1d_c1_wgrad(fptr(dy), fptr(x), fptr(dw), fptr(db), fptr(scratch), n, N, Lin, Co, K, padding,
+                               stream_ptr()))
+    return dw, db
+
+
+def avgpool4s2_fwd(x):
+    """AvgPool1d(4, 2, padding=2) of x [N, C, L] -> [N, C, L / 2 + 1]."""
+    N, C, Lin = x.shape
+    out = torch.empty(N, C, Lin // 2 + 1, device=x.device, dtype=torch.float32)
+    check(_lib.lib().mg_avgpool4s2_fwd(fptr(x), fptr(out), N * C, Lin, stream_ptr()))
+    return out
+
+
+def avgpool4s2_bwd(dy, Lin):
+    N, C, _ = dy.shape
+    dx = torch.empty(N, C, Lin, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().mg_avgpool4s2_bwd(fptr(dy), fptr(dx), N * C, Lin, stream_ptr()))
+    return dx
