@@ -25,8 +25,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 static inline int mg_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t mg_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
-// number of frame splits for a [Co, Ci, K] weight gradient (wgrad_mfma.h and vocoder_train.hip; the one count that both
-// the launchers and the scratch sizes use): two workgroups per CU are resident (66.5 KB LDS each), keep the grid within
+// number of frame splits for a [Co, Ci, K] weight gradient (both launchers of wgrad_mfma.h; the one count that they
+// and the scratch sizes of the entry points use): two workgroups per CU are resident (66.5 KB LDS each), keep the grid within
 // ONE round of 512 workgroups -- 560 workgroups take two rounds, i.e. twice the time of 504
 static inline int wgrad_nsplit(int Co, int Ci, int K, int G = 1)
 {

@@ -51,7 +51,8 @@ extern "C" int mg_conv_pack(const float *w, float *packed, int Co, int Ci, int K
 
 // ConvTranspose1d(Ci -> Co, kernel 2u, stride u, padding u/2) -- hifigan/models.py:121-127 -- as a polyphase
 // GEMM: no zero insertion, 3 taps instead of 2u on the matrix cores.
-static bool tpose_ok(int Ci, int Co, int u) { return Ci > 0 && Co > 0 && (u == 2 || u == 4 || u == 8) && (Co * u) % 4 == 0; }
+static bool tpose_u_ok(int u) { return u == 2 || u == 4 || u == 8; }
+static bool tpose_ok(int Ci, int Co, int u) { return Ci > 0 && Co > 0 && tpose_u_ok(u) && (Co * u) % 4 == 0; }
 
 extern "C" size_t mg_conv_transpose_packed_floats(int Ci, int Co, int u)
 {
@@ -209,6 +210,38 @@ extern "C" int mg_conv1d_wgrad(const float *dy, const float *x, const float *x_v
 {
     return mg_conv1d_wgrad_strided(dy, 0, x, 0, x_vec, dw, scratch, B, Co, Ci, Ldy, Lx, K, stride, pad, alpha, accumulate,
                                    stream);
+}
+
+// The vocoder's weight gradients (vocoder.py forward_train): wgrad_tile_kernel, the tile fitted to the generator's channel
+// counts and the leaky ReLU applied while the saved PRE-activation is staged (no activated copy exists).
+extern "C" int mg_conv1d_wgrad_ex(const float *dy, long dy_bs, const float *x, long x_bs, float *dw, float *scratch, int B,
+                                  int Co, int Ci, int Ldy, int Lx, int K, int dil, int pad, float in_slope, float alpha,
+                                  int accumulate, void *stream)
+{
+    if (!dy || !x || !dw || !scratch) return MG_ERR_ARG;
+    if (B <= 0 || Co <= 0 || Ci <= 0 || Ldy <= 0 || Lx <= 0) return MG_ERR_SHAPE;
+    if ((K != 3 && K != 7 && K != 11) || dil < 1 || dil > 5 || pad < 0) return MG_ERR_SHAPE;
+    if ((long)Ldy != (long)Lx + 2l * pad - (long)dil * (K - 1)) return MG_ERR_SHAPE;
+    const long dbs = dy_bs ? dy_bs : (long)Co * Ldy, xbs = x_bs ? x_bs : (long)Ci * Lx;
+    if (dbs < (long)Co * Ldy || xbs < (long)Ci * Lx) return MG_ERR_SHAPE;
+    return wgrad_tile_launch(dy, dbs, 1.f, x, xbs, in_slope, dw, scratch, B, Co, Ci, Ldy, Lx, K, 1, dil, pad, alpha,
+                             accumulate, (hipStream_t)stream);
+}
+
+extern "C" size_t mg_conv_transpose1d_wgrad_scratch_floats(int Ci, int Co, int u)
+{
+    if (Ci <= 0 || Co <= 0 || !tpose_u_ok(u)) return 0;
+    return (size_t)wgrad_nsplit(Ci, Co, 2 * u) * Ci * Co * 2 * u;
+}
+
+extern "C" int mg_conv_transpose1d_wgrad(const float *dy, const float *x, float *dw, float *scratch, int B, int Ci, int L,
+                                         int Co, int u, float in_slope, float alpha, int accumulate, void *stream)
+{
+    if (!dy || !x || !dw || !scratch) return MG_ERR_ARG;
+    if (B <= 0 || Ci <= 0 || Co <= 0 || L <= 0 || !tpose_u_ok(u)) return MG_ERR_SHAPE;
+    // dw[ci, co, k] = sum_{b,l} lrelu(x[b, ci, l]) dy[b, co, u l + k - u/2]: rows ci, columns co, frame stride u
+    return wgrad_tile_launch(x, (long)Ci * L, in_slope, dy, (long)Co * u * L, 1.f, dw, scratch, B, Ci, Co, L, u * L, 2 * u, u,
+                             1, u / 2, alpha, accumulate, (hipStream_t)stream);
 }
 
 // in [B, R, L] (batch stride in_bs, 0 -> R*L).  out_r[r] (+)= alpha * sum_{b,l};  out_br[b*R + r] = alpha * sum_l.

@@ -1,9 +1,5 @@
 // Backward of the HiFi-GAN generator (vocoder.py forward_train) and of the log-mel (audio.py mel_spectrogram_diff).
 //
-//   mg_conv1d_wgrad_ex            dW of a dilated Conv1d whose input leaky ReLU is applied while the saved
-//                                 PRE-activation is staged (no activated copy exists)
-//   mg_conv_transpose1d_wgrad     dW of the polyphase ConvTranspose1d: the same GEMM with the activation on the row
-//                                 operand and a frame stride of u on the other one (useful MACs only)
 //   mg_lrelu_bwd                  out = dy * (x > 0 ? 1 : slope) (+ add): the data gradient's mask and the residual add
 //   mg_conv_transpose1d_dgrad     dy read as u phases of length L -> 3-tap implicit GEMM with Ci rows over Co*u
 //                                 channels on the forward conv kernel (K = 3 case), then the mask
@@ -14,212 +10,12 @@
 //
 // Every result is reproducible run to run: no atomics, fixed summation orders.
 //
-// The weight-gradient GEMM follows wgrad_mfma.h (fp32 MFMA 32x32x2, 64-frame chunks in LDS with odd row strides, frame
-// axis split over workgroups, partial tiles summed by a finalize pass in a fixed order).  What differs: the workgroup
-// tile is 32, 64 or 128 rows by 32, 64 or 128 columns to fit the generator's channel counts, operand Bm is read at
-// frame f*bstride + tap*dil - pad, and either operand goes through a leaky ReLU on its way into LDS.
+// The two weight gradients (mg_conv1d_wgrad_ex, mg_conv_transpose1d_wgrad) are in conv_api.hip, on wgrad_tile_kernel of
+// wgrad_mfma.h.
 #include "common.h"
 #include "fft1024.h"
 
 namespace {
-
-constexpr int VT_FT = 64;    // frames per chunk
-constexpr int VT_RS = 65;    // odd LDS row stride: the 32 lanes of a fragment (32 rows, one column) hit 32 banks
-
-struct VtWgradArgs {
-    const float *am;   // row operand    [B, M, La]  (batch stride a_bs): element (b, m, f)
-    const float *bm;   // column operand [B, Nn, Lb] (batch stride b_bs): element (b, n, f*bstride + tap*dil - pad)
-    float *scratch;    // [nsplit][K][M][Nn] partial sums
-    long a_bs, b_bs;
-    int B, M, Nn, La, Lb, K, bstride, dil, pad;
-    int chunks_per_b, nchunks, nsplit, n_tiles;
-    float a_slope, b_slope;   // leaky ReLU applied while staging (1 = identity)
-};
-
-__device__ __forceinline__ float vt_lrelu(float v, float s) { return v > 0.f ? v : v * s; }
-
-// TM x TN blocks of 32 x 32 per workgroup tile (each of 1, 2, 4: the generator's channel counts run from 512 down to
-// 32 and to conv_post's single row, and a 128 x 128 tile on a 32 x 32 gradient spends 15/16 of its MFMAs on zeros).
-// With 4 or more blocks every wave owns TM TN / 4 of them over the whole chunk; with fewer, the waves that share a
-// block split the chunk's 64 frames and their accumulators are added through LDS in wave order at the end.
-template <int TM, int TN>
-__global__ __launch_bounds__(256, 2) void vt_wgrad_kernel(VtWgradArgs a)
-{
-    constexpr int MT = 32 * TM, NT = 32 * TN, NBLK = TM * TN;
-    constexpr int BPW = NBLK >= 4 ? NBLK / 4 : 1;   // blocks per wave
-    constexpr int KS = NBLK >= 4 ? 1 : 4 / NBLK;    // waves per block
-    constexpr int FS = VT_FT / KS;                  // frames of a chunk per wave
-    static_assert(KS == 1 || (MT + NT) * VT_RS >= 4 * 16 * 64, "the cross-wave sum reuses the tiles' LDS");
-    __shared__ float lds[(MT + NT) * VT_RS];
-    float *ldsA = lds, *ldsB = lds + MT * VT_RS;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int hh = lane >> 5, c32 = lane & 31;
-    const int split = blockIdx.x;
-    const int m0 = (blockIdx.y / a.n_tiles) * MT;
-    const int n0 = (blockIdx.y % a.n_tiles) * NT;
-    const int tap = blockIdx.z;
-    const int shift = tap * a.dil - a.pad;
-
-    f32x16 acc[BPW];
-#pragma unroll
-    for (int q = 0; q < BPW; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-
-    // A chunk's elements go global -> registers -> LDS: the loads of the next chunk are issued before the MFMAs of
-    // this one and stored after them (clamped address, selected value: no load waits on a branch).
-    float ra[MT / 4], rb[NT / 4];
-    auto load_stage = [&](int chunk) {
-        const int b = chunk / a.chunks_per_b;
-        const int f0 = (chunk - b * a.chunks_per_b) * VT_FT;
-        const float *ab = a.am + (size_t)b * a.a_bs;
-        const float *bb = a.bm + (size_t)b * a.b_bs;
-        const int f = f0 + lane;                     // a wave reads 64 consecutive frames of one row
-        const int fc = min(f, a.La - 1);
-        const long xf = (long)f * a.bstride + shift;
-        const bool xok = f < a.La && xf >= 0 && xf < a.Lb;
-        const int xc = xf < 0 ? 0 : (xf >= a.Lb ? a.Lb - 1 : (int)xf);
-        // 32-bit offsets inside one batch item (the launcher refuses planes of 2^31 elements)
-#pragma unroll
-        for (int k = 0; k < MT / 4; ++k) {
-            const int m = m0 + wave + 4 * k;
-            const float v = ab[min(m, a.M - 1) * a.La + fc];
-            ra[k] = (m < a.M && f < a.La) ? vt_lrelu(v, a.a_slope) : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < NT / 4; ++k) {
-            const int n = n0 + wave + 4 * k;
-            const float v = bb[min(n, a.Nn - 1) * a.Lb + xc];
-            rb[k] = (n < a.Nn && xok) ? vt_lrelu(v, a.b_slope) : 0.f;
-        }
-    };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int k = 0; k < MT / 4; ++k) ldsA[(wave + 4 * k) * VT_RS + lane] = ra[k];
-#pragma unroll
-        for (int k = 0; k < NT / 4; ++k) ldsB[(wave + 4 * k) * VT_RS + lane] = rb[k];
-    };
-
-    const int slice = NBLK >= 4 ? 0 : wave / NBLK;
-    const float *Ap[BPW], *Bp[BPW];
-    int bmq[BPW], bnq[BPW];
-#pragma unroll
-    for (int q = 0; q < BPW; ++q) {
-        const int blk = NBLK >= 4 ? wave * BPW + q : wave % NBLK;
-        bmq[q] = blk / TN;
-        bnq[q] = blk % TN;
-        Ap[q] = ldsA + (bmq[q] * 32 + c32) * VT_RS + hh + slice * FS;
-        Bp[q] = ldsB + (bnq[q] * 32 + c32) * VT_RS + hh + slice * FS;
-    }
-
-    int chunk = split;
-    if (chunk < a.nchunks) {
-        load_stage(chunk);
-        store_stage();
-    }
-    __syncthreads();
-    for (; chunk < a.nchunks; chunk += a.nsplit) {
-        const bool more = chunk + a.nsplit < a.nchunks;
-        if (more) load_stage(chunk + a.nsplit);   // in flight behind the MFMAs below
-#pragma unroll 8
-        for (int s = 0; s < FS / 2; ++s) {
-#pragma unroll
-            for (int q = 0; q < BPW; ++q)
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ap[q][2 * s], Bp[q][2 * s], acc[q], 0, 0, 0);
-        }
-        __syncthreads();   // every wave is done reading the tiles
-        if (more) store_stage();
-        __syncthreads();
-    }
-
-    if (KS > 1) {   // waves `blk`, NBLK + blk, ... hold the frame slices of one block: add them in that order
-        float *red = lds;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[0][r];
-        __syncthreads();
-        if (slice != 0) return;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = red[(wave * 16 + r) * 64 + lane];
-#pragma unroll
-            for (int sl = 1; sl < KS; ++sl) v += red[((sl * NBLK + wave) * 16 + r) * 64 + lane];
-            acc[0][r] = v;
-        }
-    }
-
-    // acc[q][r]: m = m0 + 32 bm + 8*(r>>2) + 4*hh + (r&3),  n = n0 + 32 bn + c32
-    float *dst = a.scratch + ((size_t)split * a.K + tap) * a.M * a.Nn;
-#pragma unroll
-    for (int q = 0; q < BPW; ++q) {
-        const int n = n0 + bnq[q] * 32 + c32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + bmq[q] * 32 + 8 * (r >> 2) + 4 * hh + (r & 3);
-            if (m < a.M && n < a.Nn) dst[(size_t)m * a.Nn + n] = acc[q][r];
-        }
-    }
-}
-
-// scratch [nsplit][K][M][Nn] -> dw [M][Nn][K] (= or +=), scaled; the splits are added in ascending order.
-__global__ __launch_bounds__(256) void vt_wgrad_finalize_kernel(const float *__restrict__ scratch, float *__restrict__ dw,
-                                                                int M, int Nn, int K, int nsplit, float alpha,
-                                                                int accumulate)
-{
-    const size_t mn = (size_t)M * Nn, n = mn * K;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float v0 = 0.f, v1 = 0.f;
-        int s = 0;
-        for (; s + 1 < nsplit; s += 2) {
-            v0 += scratch[(size_t)s * n + i];
-            v1 += scratch[(size_t)(s + 1) * n + i];
-        }
-        if (s < nsplit) v0 += scratch[(size_t)s * n + i];
-        const float v = alpha * (v0 + v1);
-        const size_t k = i / mn, cc = i - k * mn;
-        float *o = dw + cc * K + k;
-        *o = accumulate ? *o + v : v;
-    }
-}
-
-int vt_wgrad_launch(const float *am, long a_bs, float a_slope, const float *bm, long b_bs, float b_slope, float *dw,
-                    float *scratch, int B, int M, int Nn, int La, int Lb, int K, int bstride, int dil, int pad,
-                    float alpha, int accumulate, hipStream_t st)
-{
-    if ((long)M * La >= (1l << 31) || (long)Nn * Lb >= (1l << 31)) return MG_ERR_SHAPE;
-    VtWgradArgs a;
-    a.am = am;
-    a.bm = bm;
-    a.scratch = scratch;
-    a.a_bs = a_bs;
-    a.b_bs = b_bs;
-    a.B = B, a.M = M, a.Nn = Nn, a.La = La, a.Lb = Lb, a.K = K, a.bstride = bstride, a.dil = dil, a.pad = pad;
-    a.chunks_per_b = mg_cdiv(La, VT_FT);
-    a.nchunks = a.chunks_per_b * B;
-    const int TM = M <= 32 ? 1 : (M <= 64 ? 2 : 4), TN = Nn <= 32 ? 1 : (Nn <= 64 ? 2 : 4);
-    a.n_tiles = mg_cdiv(Nn, 32 * TN);
-    int nsplit = wgrad_nsplit(M, Nn, K);   // mg_conv1d_wgrad_scratch_floats >= nsplit * M * Nn * K for this same count
-    if (nsplit > a.nchunks) nsplit = a.nchunks;
-    a.nsplit = nsplit;
-    a.a_slope = a_slope;
-    a.b_slope = b_slope;
-    const dim3 grid(nsplit, mg_cdiv(M, 32 * TM) * a.n_tiles, K);
-#define VT_WGRAD_CASE(TM_, TN_) \
-    if (TM == TM_ && TN == TN_) hipLaunchKernelGGL((vt_wgrad_kernel<TM_, TN_>), grid, dim3(256), 0, st, a);
-    VT_WGRAD_CASE(1, 1) VT_WGRAD_CASE(1, 2) VT_WGRAD_CASE(1, 4)
-    VT_WGRAD_CASE(2, 1) VT_WGRAD_CASE(2, 2) VT_WGRAD_CASE(2, 4)
-    VT_WGRAD_CASE(4, 1) VT_WGRAD_CASE(4, 2) VT_WGRAD_CASE(4, 4)
-#undef VT_WGRAD_CASE
-    MG_LAUNCH_CHECK();
-    const size_t n = (size_t)M * Nn * K;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(vt_wgrad_finalize_kernel, dim3(blocks), dim3(256), 0, st, scratch, dw, M, Nn, K, nsplit, alpha,
-                       accumulate);
-    MG_LAUNCH_CHECK();
-    return MG_OK;
-}
 
 bool vt_u_ok(int u) { return u == 2 || u == 4 || u == 8; }
 
@@ -411,20 +207,6 @@ bool hop_ok(int hop) { return hop >= 1 && hop <= N && (hop & (hop - 1)) == 0; }
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-extern "C" int mg_conv1d_wgrad_ex(const float *dy, long dy_bs, const float *x, long x_bs, float *dw, float *scratch, int B,
-                                  int Co, int Ci, int Ldy, int Lx, int K, int dil, int pad, float in_slope, float alpha,
-                                  int accumulate, void *stream)
-{
-    if (!dy || !x || !dw || !scratch) return MG_ERR_ARG;
-    if (B <= 0 || Co <= 0 || Ci <= 0 || Ldy <= 0 || Lx <= 0) return MG_ERR_SHAPE;
-    if ((K != 3 && K != 7 && K != 11) || dil < 1 || dil > 5 || pad < 0) return MG_ERR_SHAPE;
-    if ((long)Ldy != (long)Lx + 2l * pad - (long)dil * (K - 1)) return MG_ERR_SHAPE;
-    const long dbs = dy_bs ? dy_bs : (long)Co * Ldy, xbs = x_bs ? x_bs : (long)Ci * Lx;
-    if (dbs < (long)Co * Ldy || xbs < (long)Ci * Lx) return MG_ERR_SHAPE;
-    return vt_wgrad_launch(dy, dbs, 1.f, x, xbs, in_slope, dw, scratch, B, Co, Ci, Ldy, Lx, K, 1, dil, pad, alpha,
-                           accumulate, (hipStream_t)stream);
-}
-
 extern "C" int mg_lrelu_bwd(const float *dy, const float *x, const float *add, float *out, float slope, size_t n,
                             void *stream)
 {
@@ -433,22 +215,6 @@ extern "C" int mg_lrelu_bwd(const float *dy, const float *x, const float *add, f
     hipLaunchKernelGGL(vt_lrelu_bwd_kernel, dim3(vt_blocks(n)), dim3(256), 0, (hipStream_t)stream, dy, x, add, out, slope, n);
     MG_LAUNCH_CHECK();
     return MG_OK;
-}
-
-extern "C" size_t mg_conv_transpose1d_wgrad_scratch_floats(int Ci, int Co, int u)
-{
-    if (Ci <= 0 || Co <= 0 || !vt_u_ok(u)) return 0;
-    return (size_t)wgrad_nsplit(Ci, Co, 2 * u) * Ci * Co * 2 * u;
-}
-
-extern "C" int mg_conv_transpose1d_wgrad(const float *dy, const float *x, float *dw, float *scratch, int B, int Ci, int L,
-                                         int Co, int u, float in_slope, float alpha, int accumulate, void *stream)
-{
-    if (!dy || !x || !dw || !scratch) return MG_ERR_ARG;
-    if (B <= 0 || Ci <= 0 || Co <= 0 || L <= 0 || !vt_u_ok(u)) return MG_ERR_SHAPE;
-    // dw[ci, co, k] = sum_{b,l} lrelu(x[b, ci, l]) dy[b, co, u l + k - u/2]: rows ci, columns co, frame stride u
-    return vt_wgrad_launch(x, (long)Ci * L, in_slope, dy, (long)Co * u * L, 1.f, dw, scratch, B, Ci, Co, L, u * L, 2 * u, u,
-                           1, u / 2, alpha, accumulate, (hipStream_t)stream);
 }
 
 extern "C" size_t mg_conv_transpose1d_dgrad_workspace_floats(int B, int Ci, int L, int Co, int u)

@@ -13,6 +13,18 @@
 // version combined the partials with fp32 atomics into one [K][Co][Ci] buffer: 8.4 M atomics per launch,
 // 15-30 us of a 60-100 us kernel, a memset in front, and a summation order that changed run to run.)
 //
+// Three split kernels share the chunk walk (chunk = split; chunk += nsplit), the k order of the MFMAs of a 32 x 32 block, the
+// scratch layout and the finalize kernel:
+//   wgrad_mfma_kernel<true>    16-byte staging loads with a register prefetch, 128 x 128 tile: aligned stride-1 operands
+//   wgrad_mfma_kernel<false>   scalar staging loads in batches, 128 x 128 tile: what the vector form cannot take (strided
+//                              convolutions, ragged lengths, misaligned bases, x_vec); same bits as the vector form
+//   wgrad_tile_kernel<TM, TN>  scalar staging loads with a register prefetch, a tile of 32/64/128 x 32/64/128, a
+//                              dilation, a frame stride and a leaky ReLU on either operand: the vocoder's gradients
+//                              (mg_conv1d_wgrad_ex, mg_conv_transpose1d_wgrad)
+// At TM = TN = 4 with slopes of 1, no dilation and bstride = stride, the third computes the second's partial tiles bit
+// for bit (measured, with a group index and the x_vec addend added to it), but its staging is 1.6x slower on the
+// discriminator's 250-frame rows (65 against 40 us a launch: DESIGN.md section 4.2), so the second stays.
+//
 // Measured and rejected (round 2): frame-interleaved tiles (stride 68, position (f & 1) * 4 + ((f >> 1) & 3) inside every
 // 8 frames) read with one ds_read_b128 per operand block and 4 k-steps -- 4 LDS reads per 16 MFMAs instead of 16.  The
 // reads were conflict-free, but the staging stores of that layout are 4-way bank-conflicted (2-way here), and they sit
@@ -216,44 +228,61 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WgradArgs a)
         }
 }
 
-// scratch [nsplit][G][K][Co][Ci] -> dw[g] [Co][Ci][K] (= or +=), scaled.  A block owns 32 consecutive scratch elements;
-// its 8 thread groups each add every 8th split (the small gradients of the discriminator run 25-128 splits: one
-// thread walking them all is a chain of that many dependent-latency loads, 15-35 us for a few hundred KB), then the
-// 8 sums are added in group order: a fixed summation order whatever the launch shape.
+// scratch [nsplit][G][K][Co][Ci] -> dw[g] [Co][Ci][K] (= or +=), scaled.  A block owns 256 / NG consecutive scratch
+// elements; its NG thread groups each add every NG-th split in two chains, then the NG sums are added in group order: a
+// fixed summation order whatever the launch shape.  NG = 8 for the convolutions (the small gradients of the
+// discriminator run 25-128 splits: one thread walking them all is a chain of that many dependent-latency loads, 15-35 us
+// for a few hundred KB); NG = 1, one thread per element adding the even and the odd splits, for the vocoder's.
+template <int NG>
 __global__ __launch_bounds__(256) void wgrad_finalize_kernel(const float *__restrict__ scratch, float *__restrict__ dw,
                                                              int Co, int Ci, int K, int G, long dw_gs, int nsplit,
                                                              float alpha, int accumulate)
 {
-    __shared__ float part[8][32];
+    constexpr int EPB = 256 / NG;   // elements per block
+    __shared__ float part[NG][EPB];
     const size_t per = (size_t)Co * Ci * K, n = per * G;
-    const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    for (size_t base = (size_t)blockIdx.x * 32; base < n; base += (size_t)gridDim.x * 32) {
+    const int lane = threadIdx.x % EPB, grp = threadIdx.x / EPB;
+    for (size_t base = (size_t)blockIdx.x * EPB; base < n; base += (size_t)gridDim.x * EPB) {
         const size_t i = base + lane;
         float v0 = 0.f, v1 = 0.f;
         if (i < n) {
             int s = grp;
-            for (; s + 8 < nsplit; s += 16) {
+            for (; s + NG < nsplit; s += 2 * NG) {
                 v0 += scratch[(size_t)s * n + i];
-                v1 += scratch[(size_t)(s + 8) * n + i];
+                v1 += scratch[(size_t)(s + NG) * n + i];
             }
             if (s < nsplit) v0 += scratch[(size_t)s * n + i];
         }
-        part[grp][lane] = v0 + v1;
-        __syncthreads();
+        float v = v0 + v1;
+        if (NG > 1) {
+            part[grp][lane] = v;
+            __syncthreads();
+        }
         if (grp == 0 && i < n) {
-            float v = part[0][lane];
 #pragma unroll
-            for (int q = 1; q < 8; ++q) v += part[q][lane];
+            for (int q = 1; q < NG; ++q) v += part[q][lane];
             v *= alpha;
             // scratch element (g, k, co, ci) -> dw[g][co][ci][k]: coalesced reads of every split, writes strided by K
-            const size_t g = i / per, r = i - g * per;
+            const size_t g = G > 1 ? i / per : 0, r = i - g * per;   // one division per element without groups
             const size_t cc = r % ((size_t)Co * Ci);
             const int k = (int)(r / ((size_t)Co * Ci));
             float *o = dw + g * dw_gs + cc * K + k;
             *o = accumulate ? *o + v : v;
         }
-        __syncthreads();
+        if (NG > 1) __syncthreads();
     }
+}
+
+template <int NG>
+static int wgrad_finalize_launch(const float *scratch, float *dw, int Co, int Ci, int K, int G, long dw_gs, int nsplit,
+                                 float alpha, int accumulate, hipStream_t st)
+{
+    const size_t n = (size_t)Co * Ci * K * G, epb = 256 / NG, cap = NG == 1 ? 4096 : 8192;
+    const int blocks = (int)((n + epb - 1) / epb < cap ? (n + epb - 1) / epb : cap);
+    hipLaunchKernelGGL(wgrad_finalize_kernel<NG>, dim3(blocks), dim3(256), 0, st, scratch, dw, Co, Ci, K, G, dw_gs, nsplit,
+                       alpha, accumulate);
+    MG_LAUNCH_CHECK();
+    return MG_OK;
 }
 
 static inline size_t wgrad_scratch_floats(int Co, int Ci, int K, int G = 1)
@@ -304,7 +333,6 @@ static int wgrad_launch(const WgradShape &s, const float *dy, const float *x, co
     int nsplit = wgrad_nsplit(s.Co, s.Ci, s.K, s.G);
     if (nsplit > a.nchunks) nsplit = a.nchunks;
     a.nsplit = nsplit;
-    const size_t n = (size_t)s.Co * s.Ci * s.K * s.G;
     dim3 grid(nsplit, mg_cdiv(s.Co, 128) * a.ci_tiles, s.K * s.G);
     {   // big stride-1 "same" gradients: the streaming kernel (wgrad_stream.h); MG_WGRAD_STREAM=0 keeps the split kernel
         const char *env = std::getenv("MG_WGRAD_STREAM");
@@ -329,9 +357,178 @@ static int wgrad_launch(const WgradShape &s, const float *dy, const float *x, co
     if (vec) hipLaunchKernelGGL(wgrad_mfma_kernel<true>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(wgrad_mfma_kernel<false>, grid, dim3(256), 0, st, a);
     MG_LAUNCH_CHECK();
-    const int blocks = (int)((n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192);
-    hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(blocks), dim3(256), 0, st, scratch, dw, s.Co, s.Ci, s.K, s.G,
-                       s.dw_gs ? s.dw_gs : (long)s.Co * s.Ci * s.K, nsplit, alpha, accumulate);
+    return wgrad_finalize_launch<8>(scratch, dw, s.Co, s.Ci, s.K, s.G, s.dw_gs ? s.dw_gs : (long)s.Co * s.Ci * s.K, nsplit,
+                                    alpha, accumulate, st);
+}
+
+// The vocoder's split kernel.  Operands are named for the GEMM, rows m and columns n: a convolution has am = dy, bm = x; the
+// transposed convolution has am = x, bm = dy.
+struct WgradTileArgs {
+    const float *am;   // row operand    [B, M, La]  (batch stride a_bs): element (b, m, f)
+    const float *bm;   // column operand [B, Nn, Lb] (batch stride b_bs): element (b, n, f*bstride + tap*dil - pad)
+    float *scratch;    // [nsplit][K][M][Nn] partial sums
+    long a_bs, b_bs;
+    int B, M, Nn, La, Lb, K, bstride, dil, pad;
+    int chunks_per_b, nchunks, nsplit, n_tiles;
+    float a_slope, b_slope;   // leaky ReLU applied while staging (1 = identity)
+};
+
+__device__ __forceinline__ float wg_lrelu(float v, float s) { return v > 0.f ? v : v * s; }
+
+// TM x TN blocks of 32 x 32 per workgroup tile (each of 1, 2, 4: the generator's channel counts run from 512 down to
+// 32 and to conv_post's single row, and a 128 x 128 tile on a 32 x 32 gradient spends 15/16 of its MFMAs on zeros).
+// With 4 or more blocks every wave owns TM TN / 4 of them over the whole chunk; with fewer, the waves that share a
+// block split the chunk's 64 frames and their accumulators are added through LDS in wave order at the end.
+template <int TM, int TN>
+__global__ __launch_bounds__(256, 2) void wgrad_tile_kernel(WgradTileArgs a)
+{
+    constexpr int MT = 32 * TM, NT = 32 * TN, NBLK = TM * TN;
+    constexpr int BPW = NBLK >= 4 ? NBLK / 4 : 1;   // blocks per wave
+    constexpr int KS = NBLK >= 4 ? 1 : 4 / NBLK;    // waves per block
+    constexpr int FS = WG_FT / KS;                  // frames of a chunk per wave
+    static_assert(KS == 1 || (MT + NT) * WG_RSA >= 4 * 16 * 64, "the cross-wave sum reuses the tiles' LDS");
+    __shared__ float lds[(MT + NT) * WG_RSA];
+    float *ldsA = lds, *ldsB = lds + MT * WG_RSA;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int hh = lane >> 5, c32 = lane & 31;
+    const int split = blockIdx.x;
+    const int m0 = (blockIdx.y / a.n_tiles) * MT;
+    const int n0 = (blockIdx.y % a.n_tiles) * NT;
+    const int tap = blockIdx.z;
+    const int shift = tap * a.dil - a.pad;
+
+    f32x16 acc[BPW];
+#pragma unroll
+    for (int q = 0; q < BPW; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+
+    // A chunk's elements go global -> registers -> LDS: the loads of the next chunk are issued before the MFMAs of
+    // this one and stored after them (clamped address, selected value: no load waits on a branch).
+    float ra[MT / 4], rb[NT / 4];
+    auto load_stage = [&](int chunk) {
+        const int b = chunk / a.chunks_per_b;
+        const int f0 = (chunk - b * a.chunks_per_b) * WG_FT;
+        const float *ab = a.am + (size_t)b * a.a_bs;
+        const float *bb = a.bm + (size_t)b * a.b_bs;
+        const int f = f0 + lane;                     // a wave reads 64 consecutive frames of one row
+        const int fc = min(f, a.La - 1);
+        const long xf = (long)f * a.bstride + shift;
+        const bool xok = f < a.La && xf >= 0 && xf < a.Lb;
+        const int xc = xf < 0 ? 0 : (xf >= a.Lb ? a.Lb - 1 : (int)xf);
+        // 32-bit offsets inside one batch item (the launcher refuses planes of 2^31 elements)
+#pragma unroll
+        for (int k = 0; k < MT / 4; ++k) {
+            const int m = m0 + wave + 4 * k;
+            const float v = ab[min(m, a.M - 1) * a.La + fc];
+            ra[k] = (m < a.M && f < a.La) ? wg_lrelu(v, a.a_slope) : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < NT / 4; ++k) {
+            const int n = n0 + wave + 4 * k;
+            const float v = bb[min(n, a.Nn - 1) * a.Lb + xc];
+            rb[k] = (n < a.Nn && xok) ? wg_lrelu(v, a.b_slope) : 0.f;
+        }
+    };
+    auto store_stage = [&]() {
+#pragma unroll
+        for (int k = 0; k < MT / 4; ++k) ldsA[(wave + 4 * k) * WG_RSA + lane] = ra[k];
+#pragma unroll
+        for (int k = 0; k < NT / 4; ++k) ldsB[(wave + 4 * k) * WG_RSA + lane] = rb[k];
+    };
+
+    const int slice = NBLK >= 4 ? 0 : wave / NBLK;
+    const float *Ap[BPW], *Bp[BPW];
+    int bmq[BPW], bnq[BPW];
+#pragma unroll
+    for (int q = 0; q < BPW; ++q) {
+        const int blk = NBLK >= 4 ? wave * BPW + q : wave % NBLK;
+        bmq[q] = blk / TN;
+        bnq[q] = blk % TN;
+        Ap[q] = ldsA + (bmq[q] * 32 + c32) * WG_RSA + hh + slice * FS;
+        Bp[q] = ldsB + (bnq[q] * 32 + c32) * WG_RSA + hh + slice * FS;
+    }
+
+    int chunk = split;
+    if (chunk < a.nchunks) {
+        load_stage(chunk);
+        store_stage();
+    }
+    __syncthreads();
+    for (; chunk < a.nchunks; chunk += a.nsplit) {
+        const bool more = chunk + a.nsplit < a.nchunks;
+        if (more) load_stage(chunk + a.nsplit);   // in flight behind the MFMAs below
+#pragma unroll 8
+        for (int s = 0; s < FS / 2; ++s) {
+#pragma unroll
+            for (int q = 0; q < BPW; ++q)
+                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ap[q][2 * s], Bp[q][2 * s], acc[q], 0, 0, 0);
+        }
+        __syncthreads();   // every wave is done reading the tiles
+        if (more) store_stage();
+        __syncthreads();
+    }
+
+    if (KS > 1) {   // waves `blk`, NBLK + blk, ... hold the frame slices of one block: add them in that order
+        float *red = lds;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[0][r];
+        __syncthreads();
+        if (slice != 0) return;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = red[(wave * 16 + r) * 64 + lane];
+#pragma unroll
+            for (int sl = 1; sl < KS; ++sl) v += red[((sl * NBLK + wave) * 16 + r) * 64 + lane];
+            acc[0][r] = v;
+        }
+    }
+
+    // acc[q][r]: m = m0 + 32 bm + 8*(r>>2) + 4*hh + (r&3),  n = n0 + 32 bn + c32
+    float *dst = a.scratch + ((size_t)split * a.K + tap) * a.M * a.Nn;
+#pragma unroll
+    for (int q = 0; q < BPW; ++q) {
+        const int n = n0 + bnq[q] * 32 + c32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + bmq[q] * 32 + 8 * (r >> 2) + 4 * hh + (r & 3);
+            if (m < a.M && n < a.Nn) dst[(size_t)m * a.Nn + n] = acc[q][r];
+        }
+    }
+}
+
+// Row offsets inside one batch item are 32-bit: planes of 2^31 elements (M * La, Nn * Lb) are refused.
+static int wgrad_tile_launch(const float *am, long a_bs, float a_slope, const float *bm, long b_bs, float b_slope, float *dw,
+                             float *scratch, int B, int M, int Nn, int La, int Lb, int K, int bstride, int dil, int pad,
+                             float alpha, int accumulate, hipStream_t st)
+{
+    if ((long)M * La >= (1l << 31) || (long)Nn * Lb >= (1l << 31)) return MG_ERR_SHAPE;
+    WgradTileArgs a;
+    a.am = am;
+    a.bm = bm;
+    a.scratch = scratch;
+    a.a_bs = a_bs;
+    a.b_bs = b_bs;
+    a.B = B, a.M = M, a.Nn = Nn, a.La = La, a.Lb = Lb, a.K = K, a.bstride = bstride, a.dil = dil, a.pad = pad;
+    a.chunks_per_b = mg_cdiv(La, WG_FT);
+    a.nchunks = a.chunks_per_b * B;
+    const int TM = M <= 32 ? 1 : (M <= 64 ? 2 : 4), TN = Nn <= 32 ? 1 : (Nn <= 64 ? 2 : 4);
+    a.n_tiles = mg_cdiv(Nn, 32 * TN);
+    int nsplit = wgrad_nsplit(M, Nn, K);   // mg_conv1d_wgrad_scratch_floats >= nsplit * M * Nn * K for this same count
+    if (nsplit > a.nchunks) nsplit = a.nchunks;
+    a.nsplit = nsplit;
+    a.a_slope = a_slope;
+    a.b_slope = b_slope;
+    const dim3 grid(nsplit, mg_cdiv(M, 32 * TM) * a.n_tiles, K);
+#define WG_TILE_CASE(TM_, TN_) \
+    if (TM == TM_ && TN == TN_) hipLaunchKernelGGL((wgrad_tile_kernel<TM_, TN_>), grid, dim3(256), 0, st, a);
+    WG_TILE_CASE(1, 1) WG_TILE_CASE(1, 2) WG_TILE_CASE(1, 4)
+    WG_TILE_CASE(2, 1) WG_TILE_CASE(2, 2) WG_TILE_CASE(2, 4)
+    WG_TILE_CASE(4, 1) WG_TILE_CASE(4, 2) WG_TILE_CASE(4, 4)
+#undef WG_TILE_CASE
     MG_LAUNCH_CHECK();
-    return MG_OK;
+    return wgrad_finalize_launch<1>(scratch, dw, M, Nn, K, 1, 0, nsplit, alpha, accumulate, st);
 }

@@ -29,6 +29,8 @@ def dev(a):
 @pytest.mark.parametrize("Ci,Co,K,stride,L", [
     (256, 512, 3, 1, 130), (256, 512, 1, 1, 64), (80, 256, 1, 1, 37), (256, 80, 1, 1, 200),
     (64, 128, 5, 2, 37), (128, 512, 5, 2, 300), (128, 1, 3, 1, 10), (7, 5, 3, 1, 3), (160, 64, 3, 1, 1000),
+    # the scalar-staged kernel's tile edges: ragged in rows, columns and frames at once; Ldy = 65, a full chunk plus a frame
+    (130, 129, 5, 2, 251), (64, 128, 5, 2, 129),
 ])
 def test_wgrad_matches_autograd(mg, Ci, Co, K, stride, L):
     g = torch.Generator().manual_seed(Ci + Co * 7 + K)
@@ -54,6 +56,43 @@ def test_wgrad_xvec(mg):
     F.conv1d(x + v[:, :, None], w, None, padding=2).backward(gy)
     dw = mg.ops.conv1d_wgrad(gy.cuda(), x.cuda(), K, 1, 2, x_vec=v.cuda())
     assert_close(dw.cpu(), w.grad, 2e-5, "wgrad with input vector")
+
+
+def test_wgrad_xvec_strided_ragged(mg):
+    """The input vector with a stride and a ragged length (Ldy = 36, the outer taps run off both ends of x): the vector
+    is added to the frames that exist, not to the zero padding."""
+    g = torch.Generator().manual_seed(5)
+    B, Ci, Co, L, K = 2, 96, 40, 71, 5
+    x, v = torch.randn(B, Ci, L, generator=g), torch.randn(B, Ci, generator=g)
+    w = (torch.randn(Co, Ci, K, generator=g) / (Ci * K) ** 0.5).requires_grad_()
+    y = F.conv1d(x + v[:, :, None], w, None, stride=2, padding=2)
+    gy = torch.randn(y.shape, generator=g)
+    y.backward(gy)
+    dw = mg.ops.conv1d_wgrad(gy.cuda(), x.cuda(), K, 2, 2, x_vec=v.cuda())
+    assert_close(dw.cpu(), w.grad, 2e-5, "strided wgrad with input vector")
+
+
+def offset_view(t):
+    """t's values as a contiguous GPU tensor that starts one float into a larger buffer: never 16-byte aligned."""
+    buf = torch.empty(t.numel() + 1, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+@pytest.mark.parametrize("B,Co,Ci,K,L", [(3, 96, 40, 3, 204), (2, 256, 130, 5, 132)])
+def test_wgrad_vector_and_scalar_staging_agree(mg, monkeypatch, B, Co, Ci, K, L):
+    """The two split kernels walk the same chunks in the same k order under the same split count: aligned operands (the
+    vector-staged kernel) and the same values one float off alignment (the scalar-staged kernel) give the same bits."""
+    monkeypatch.setenv("MG_WGRAD_STREAM", "0")
+    g = torch.Generator().manual_seed(B + Co + Ci + K + L)
+    dy, x = torch.randn(B, Co, L, generator=g).cuda(), torch.randn(B, Ci, L, generator=g).cuda()
+    assert dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+    pad = (K - 1) // 2
+    dw_vec = mg.ops.conv1d_wgrad(dy, x, K, 1, pad)
+    dw_scalar = mg.ops.conv1d_wgrad(offset_view(dy), offset_view(x), K, 1, pad)
+    assert torch.equal(dw_vec, dw_scalar)
 
 
 @pytest.mark.parametrize("ms", [0, 1])
@@ -229,3 +268,38 @@ def test_grouped_wgrad_matches_per_group_calls(mg):
     for g in range(G):
         ref = 1.0 + 0.5 * mg.ops.conv1d_wgrad(dy_all[:, :Co].contiguous(), x_all[g], K, 1, 1)
         assert_close(dw2[g].cpu(), ref.cpu(), 1e-6, "grouped wgrad shared dy, group %d" % g)
+
+
+def test_grouped_wgrad_scalar_staged(mg):
+    """mg_conv1d_wgrad_grouped at L % 4 == 1, which the vector-staged kernel cannot take: == per-group mg_conv1d_wgrad
+    calls bit for bit (per-group and shared dy, alpha and accumulation), and autograd for one group."""
+    import ctypes
+    G, B, Co, Ci, K, L = 3, 3, 96, 40, 3, 205
+    gen = torch.Generator().manual_seed(15)
+    dy_all = torch.randn(B, G * Co, L, generator=gen).cuda()          # slots in the row dimension: [B][G*Co][L]
+    x_all = torch.randn(G, B, Ci, L, generator=gen).cuda()            # layer-major saves: [G][B][Ci][L]
+    lib = mg._lib.lib()
+    cp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    scratch = torch.empty(lib.mg_conv1d_wgrad_grouped_scratch_floats(Co, Ci, K, G), device="cuda")
+    scratch1 = torch.empty(lib.mg_conv1d_wgrad_scratch_floats(Co, Ci, K), device="cuda")
+
+    def single(dy, x, alpha, acc, out):
+        mg._lib.check(lib.mg_conv1d_wgrad(cp(dy), cp(x), None, cp(out), cp(scratch1), B, Co, Ci, L, L, K, 1, 1, alpha, acc, None))
+        return out
+    dw = torch.empty(G, Co, Ci, K, device="cuda")
+    mg._lib.check(lib.mg_conv1d_wgrad_grouped(cp(dy_all), G * Co * L, Co * L, cp(x_all), Ci * L, B * Ci * L, cp(dw), 0,
+                                              cp(scratch), G, B, Co, Ci, L, L, K, 1, 1, 1.0, 0, None))
+    for g in range(G):
+        ref = single(dy_all[:, g * Co:(g + 1) * Co].contiguous(), x_all[g], 1.0, 0, torch.empty(Co, Ci, K, device="cuda"))
+        assert torch.equal(dw[g], ref), "grouped wgrad group %d" % g
+    w = torch.zeros(Co, Ci, K, requires_grad=True)
+    F.conv1d(x_all[1].cpu(), w, None, padding=1).backward(dy_all[:, Co:2 * Co].cpu())
+    assert_close(dw[1].cpu(), w.grad, 2e-5, "grouped wgrad vs autograd")
+    # shared dy (group stride 0), scaled and accumulated into an existing gradient
+    dw2 = torch.ones(G, Co, Ci, K, device="cuda")
+    mg._lib.check(lib.mg_conv1d_wgrad_grouped(cp(dy_all), G * Co * L, 0, cp(x_all), Ci * L, B * Ci * L, cp(dw2), 0,
+                                              cp(scratch), G, B, Co, Ci, L, L, K, 1, 1, 0.5, 1, None))
+    dy0 = dy_all[:, :Co].contiguous()
+    for g in range(G):
+        ref = single(dy0, x_all[g], 0.5, 1, torch.ones(Co, Ci, K, device="cuda"))
+        assert torch.equal(dw2[g], ref), "grouped wgrad shared dy, group %d" % g
