@@ -477,6 +477,26 @@ int mg_conv1d_wgrad_ex(const float *dy, long dy_bs, const float *x, long x_bs, f
 /* out[i] = dy[i] * (x[i] > 0 ? 1 : slope) (+ add[i]): a leaky ReLU's backward through its saved input, with the
  * residual branch's gradient added (add may be NULL; out may be dy or add). */
 int mg_lrelu_bwd(const float *dy, const float *x, const float *add, float *out, float slope, size_t n, void *stream);
+/* Backward of mg_conv1d_reflect_fwd (csrc/melgan_train.hip): y = act(alpha * W (*)_dil reflect_p(lrelu(x, in_slope)) + b),
+ * p = dil (K-1)/2, K = 3 at dil <= 9 or K = 7 at dil = 1, p < L (MG_ERR_SHAPE otherwise).  dy is the gradient in front of
+ * act.  Batch strides in floats, 0 = dense, never smaller than a plane.  No atomics: the bits repeat run to run.
+ *   wgrad: dw[co,ci,k] (+)= alpha * sum_{b,l} dy[b,co,l] lrelu(x)[b,ci, refl(l + k dil - p)], refl(j) = -j for j < 0 and
+ *          2(L-1) - j for j >= L; scratch of mg_conv1d_wgrad_scratch_floats(Co, Ci, K) floats.
+ *   dgrad: packed = mg_conv_pack(w, MG_PACK_DGRAD); dy [B, Co, L] dense -> the zero-padded correlation over the padded
+ *          length L + 2p into the workspace, then mg_reflect_fold_bwd with x [B, Ci, L] the saved pre-activation and the
+ *          optional residual gradient add; dx [B, Ci, L] dense (dx may be add when add is dense).
+ *   fold:  P [B, C, L + 2p] -> out [B, C, L] dense, out[b,c,i] = (P[i+p] + [1 <= i <= p] P[p-i] + [L-1-p <= i <= L-2] P[2(L-1)-i+p])
+ *          * (x > 0 ? 1 : slope) (+ add), x NULL = no mask, add NULL = none; out may be a dense add, and with
+ *          p = 0 a dense P: a leaky ReLU's backward with batch strides. */
+int mg_conv1d_reflect_wgrad(const float *dy, long dy_bs, const float *x, long x_bs, float *dw, float *scratch, int B,
+                            int Co, int Ci, int L, int K, int dil, float in_slope, float alpha, int accumulate,
+                            void *stream);
+size_t mg_conv1d_reflect_dgrad_workspace_floats(int B, int Ci, int L, int K, int dil);
+int mg_conv1d_reflect_dgrad(const float *dy, const float *packed, const float *x, long x_bs, const float *add, long add_bs,
+                            float *dx, float *workspace, size_t workspace_floats, int B, int Co, int Ci, int L, int K,
+                            int dil, float in_slope, float alpha, void *stream);
+int mg_reflect_fold_bwd(const float *P, long p_bs, const float *x, long x_bs, const float *add, long add_bs, float *out,
+                        int B, int C, int L, int p, float slope, void *stream);
 /* Backward of y = alpha * convT(lrelu(x, in_slope), w, stride u, padding u/2) (mg_conv_transpose1d_fwd), w [Ci, Co, 2u],
  * x [B, Ci, L], dy [B, Co, u L], u in {2,4,8}; out-of-range dy is 0.
  *   dgrad: dx[b,ci,l] = (x > 0 ? 1 : in_slope) * alpha * sum_{co,k} w[ci,co,k] dy[b,co, u l + k - u/2], dy read as u

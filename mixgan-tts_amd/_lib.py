@@ -233,6 +233,10 @@ def _signatures():
         "mg_dtw": (i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, sz, vp]),
         "mg_conv1d_wgrad_ex": (i, [vp, lg, vp, lg, vp, vp, i, i, i, i, i, i, i, i, f, f, i, vp]),
         "mg_lrelu_bwd": (i, [vp, vp, vp, vp, f, sz, vp]),
+        "mg_conv1d_reflect_wgrad": (i, [vp, lg, vp, lg, vp, vp, i, i, i, i, i, i, f, f, i, vp]),
+        "mg_conv1d_reflect_dgrad_workspace_floats": (sz, [i, i, i, i, i]),
+        "mg_conv1d_reflect_dgrad": (i, [vp, vp, vp, lg, vp, lg, vp, vp, sz, i, i, i, i, i, i, f, f, vp]),
+        "mg_reflect_fold_bwd": (i, [vp, lg, vp, lg, vp, lg, vp, i, i, i, i, f, vp]),
         "mg_conv_transpose1d_dgrad_workspace_floats": (sz, [i, i, i, i, i]),
         "mg_conv_transpose1d_dgrad": (i, [vp, vp, vp, vp, vp, sz, i, i, i, i, i, f, f, vp]),
         "mg_conv_transpose1d_wgrad_scratch_floats": (sz, [i, i, i]),

@@ -528,6 +528,82 @@ def voc_up(x, w, b, u, slope, alpha):
 
 
 # --------------------------------------------------------------------------------------------------
+# MelGAN generator (melgan.MelGANGenerator.forward_train; csrc/melgan_train.hip).  Effective weights, as above.
+# --------------------------------------------------------------------------------------------------
+class _MelConvReflectFn(torch.autograd.Function):
+    """y = act(alpha * conv1d(reflection_pad(leaky_relu(x, in_slope)), w, dilation) + b), act None or "tanh": the first
+    conv (in_slope 1, alpha the mel scale) and the last (tanh).  Saves x, w (and y for tanh)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, dil, in_slope, alpha, act):
+        Co, Ci, K = w.shape
+        y = ops.conv1d_reflect_packed(x, ops.pack_conv_weight(w, ops.PACK_PLAIN), b, Co, K, dil, in_slope, act, 0.0, alpha)
+        ctx.save_for_backward(x, w, y if act else None)
+        ctx.cfg = (dil, in_slope, alpha, act)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, y = ctx.saved_tensors
+        dil, in_slope, alpha, act = ctx.cfg
+        g = g.contiguous()
+        if act:
+            g = ops.act_bwd(g, y, act)
+        need = ctx.needs_input_grad
+        dx = ops.conv1d_reflect_dgrad(g, w, x, dil, in_slope, alpha) if need[0] else None
+        dw = ops.conv1d_reflect_wgrad(g, x, w.shape[2], dil, in_slope, alpha) if need[1] else None
+        db = ops.rowsum(g) if need[2] else None
+        return dx, dw, db, None, None, None, None
+
+
+class _MelResBlockFn(torch.autograd.Function):
+    """MelGAN ResnetBlock(C, dil): t = lrelu(conv3(reflection_pad(lrelu(x)), w1, dil) + b1), y = ws x + w2 t + bs + b2,
+    the last line one K = 1 GEMM over the [B, 2C, L] buffer [x ; t].  Saves that buffer -- x is the first leaky ReLU's
+    input, t the second's OUTPUT, whose sign is its input's -- and the weights; returns (y, buffer)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, ws, bs, dil, slope):
+        B, C, L = x.shape
+        buf = torch.empty(B, 2 * C, L, device=x.device, dtype=torch.float32)
+        buf[:, :C].copy_(x)
+        ops.conv1d_reflect_packed(buf, ops.pack_conv_weight(w1, ops.PACK_PLAIN), b1, C, 3, dil, slope, "lrelu_s", slope,
+                                  x_bs=2 * C * L, C=C, out=buf, out_bs=2 * C * L, out_off=C * L)
+        wmix = torch.cat([ws, w2], 1)
+        y = ops.conv1d_packed(buf, ops.pack_conv_weight(wmix, ops.PACK_PLAIN), bs + b2, C, 1)
+        ctx.save_for_backward(buf, w1, wmix)
+        ctx.cfg = (dil, slope)
+        ctx.mark_non_differentiable(buf)
+        return y, buf
+
+    @staticmethod
+    def backward(ctx, g, _gbuf):
+        buf, w1, wmix = ctx.saved_tensors
+        dil, slope = ctx.cfg
+        B, C2, L = buf.shape
+        C = C2 // 2
+        g = g.contiguous()
+        db = ops.rowsum(g)                                                        # db_s = db_2
+        dmix = ops.conv1d_wgrad(g, buf, 1)                                        # d[Ws | W2]  [C, 2C, 1]
+        dbuf = ops.conv1d_packed(g, ops.pack_conv_weight(wmix, ops.PACK_DGRAD), None, C2, 1)   # [d x (shortcut) ; d t]
+        dt = ops.lrelu_bwd_strided(dbuf, C * L, C2 * L, buf, C * L, C2 * L, B, C, L, slope)
+        dw1 = ops.conv1d_reflect_wgrad(dt, buf, 3, dil, slope, x_bs=C2 * L, C=C)
+        db1 = ops.rowsum(dt)
+        dx = ops.conv1d_reflect_dgrad(dt, w1, buf, dil, slope, add=dbuf, x_bs=C2 * L, add_bs=C2 * L, C=C)
+        return dx, dw1, db1, dmix[:, C:], db, dmix[:, :C], db, None, None
+
+
+def melgan_conv_reflect(x, w, b, dil, in_slope=1.0, alpha=1.0, act=None):
+    _require_cuda(x, w, b)
+    return _MelConvReflectFn.apply(x.contiguous(), w.contiguous(), b, dil, in_slope, alpha, act)
+
+
+def melgan_resblock(x, w1, b1, w2, b2, ws, bs, dil, slope):
+    """-> (y [B, C, L], [x ; t] [B, 2C, L] detached: the two leaky ReLUs' sign carriers)."""
+    _require_cuda(x, w1, w2, ws)
+    return _MelResBlockFn.apply(x.contiguous(), w1.contiguous(), b1, w2.contiguous(), b2, ws.contiguous(), bs, dil, slope)
+
+
+# --------------------------------------------------------------------------------------------------
 # HiFi-GAN multi-scale discriminator (csrc/msd.hip; hifigan_discriminators.py)
 # --------------------------------------------------------------------------------------------------
 class _ScaleStackFn(torch.autograd.Function):

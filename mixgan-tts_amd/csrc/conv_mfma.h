@@ -253,7 +253,9 @@ struct EpiBiasAct {
 //   1 = reflect padding (ReflectionPad1d in front of the conv, MelGAN mel2wav/modules.py): an input position l < 0
 //       stages in[-l], l >= Lin stages in[2 (Lin-1) - l] (a launcher guarantees pad < Lin), and every in-tile element
 //       is live -- K = 7 (first and last conv) and K = 3 with dilation <= 9 (the ResnetBlock convs);
-//   2 = the polyphase transposed conv writing a channel slice of a wider buffer (K = 3 only).
+//   2 = the polyphase transposed conv writing a channel slice of a wider buffer (K = 3 only);
+//   3 = zero padding, K = 3 with dilation <= 9: the data gradient of the reflect-padded ResnetBlock conv as the full
+//       correlation over the padded length (melgan_train.hip).
 template <class Epi>
 struct EpiMelGAN { static constexpr int value = 0; };
 
@@ -483,7 +485,8 @@ struct ConvShape {
 
 
 // Which instantiations an epilogue has, as the plan sees it.
-//   EpiMelGAN (above): 1 = reflect padding, 2 = the slice-writing polyphase store -- their own, small case lists;
+//   EpiMelGAN (above): 1 = reflect padding, 2 = the slice-writing polyphase store, 3 = the zero-padded dilation-9
+//       correlation -- their own, small case lists;
 //   EpiWide: also the vocoder shapes (K in {7,11,16,4}, dilations up to 5: hifigan/models.py:19-95,112-143), which only
 //       epilogues that opt in instantiate, to keep build time down;
 //   EpiNeedsWM2: the epilogue pairs two 32-row blocks of one wave (the denoiser's gate), so WM = 1 forms compute nothing.
@@ -505,6 +508,7 @@ static constexpr ConvEpiKind conv_epi_kind() { return ConvEpiKind{EpiMelGAN<Epi>
 #define MG_CONV_CASES_WIDE(X) X(3, 1, 32, 5) X(7, 1, 16, 5) X(11, 1, 16, 5) X(16, 1, 16, 1) X(4, 1, 16, 1)
 #define MG_CONV_CASES_REFLECT(X) X(3, 1, 32, 9) X(7, 1, 16, 1)
 #define MG_CONV_CASES_SLICE(X) X(3, 1, 32, 1)
+#define MG_CONV_CASES_DIL9(X) X(3, 1, 32, 9)
 
 // 256-frame tiles of the one-block form only while the slab fits the register staging (<= 32 elements per thread)
 static constexpr bool conv_big_slab(int kw, int stride, int ck, int dilmax)
@@ -530,6 +534,8 @@ static inline int conv_plan(int B, int Ci, int Lout, int Mrows, int K, int strid
         MG_CONV_CASES_REFLECT(MG_CONV_PICK)
     } else if (e.melgan == 2) {
         MG_CONV_CASES_SLICE(MG_CONV_PICK)
+    } else if (e.melgan == 3) {
+        MG_CONV_CASES_DIL9(MG_CONV_PICK)
     } else {
         MG_CONV_CASES_BASE(MG_CONV_PICK)
         if (e.wide) {
@@ -640,6 +646,8 @@ static int conv_launch(const ConvShape &s, const float *in, const float *in_vec,
         MG_CONV_CASES_REFLECT(MG_CONV_CASE)
     } else if constexpr (EpiMelGAN<Epi>::value == 2) {
         MG_CONV_CASES_SLICE(MG_CONV_CASE)
+    } else if constexpr (EpiMelGAN<Epi>::value == 3) {
+        MG_CONV_CASES_DIL9(MG_CONV_CASE)
     } else {
         MG_CONV_CASES_BASE(MG_CONV_CASE)
         if constexpr (EpiWide<Epi>::value) {

@@ -379,7 +379,10 @@ __device__ __forceinline__ float wg_lrelu(float v, float s) { return v > 0.f ? v
 // 32 and to conv_post's single row, and a 128 x 128 tile on a 32 x 32 gradient spends 15/16 of its MFMAs on zeros).
 // With 4 or more blocks every wave owns TM TN / 4 of them over the whole chunk; with fewer, the waves that share a
 // block split the chunk's 64 frames and their accumulators are added through LDS in wave order at the end.
-template <int TM, int TN>
+// REFLECT: the column operand is read through a ReflectionPad1d -- a position left of 0 or right of Lb - 1 is mirrored
+// about that end (MelGAN's convolutions, melgan_train.hip; the launcher guarantees pad < Lb, so one mirror lands inside)
+// instead of contributing zero.
+template <int TM, int TN, bool REFLECT = false>
 __global__ __launch_bounds__(256, 2) void wgrad_tile_kernel(WgradTileArgs a)
 {
     constexpr int MT = 32 * TM, NT = 32 * TN, NBLK = TM * TN;
@@ -416,7 +419,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_tile_kernel(WgradTileArgs a)
         const float *bb = a.bm + (size_t)b * a.b_bs;
         const int f = f0 + lane;                     // a wave reads 64 consecutive frames of one row
         const int fc = min(f, a.La - 1);
-        const long xf = (long)f * a.bstride + shift;
+        long xf = (long)f * a.bstride + shift;
+        if constexpr (REFLECT) {
+            xf = xf < 0 ? -xf : xf;
+            xf = xf >= a.Lb ? 2l * (a.Lb - 1) - xf : xf;   // rows past La may land outside: clamped below, value dropped
+        }
         const bool xok = f < a.La && xf >= 0 && xf < a.Lb;
         const int xc = xf < 0 ? 0 : (xf >= a.Lb ? a.Lb - 1 : (int)xf);
         // 32-bit offsets inside one batch item (the launcher refuses planes of 2^31 elements)
@@ -501,6 +508,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tile_kernel(WgradTileArgs a)
 }
 
 // Row offsets inside one batch item are 32-bit: planes of 2^31 elements (M * La, Nn * Lb) are refused.
+template <bool REFLECT = false>
 static int wgrad_tile_launch(const float *am, long a_bs, float a_slope, const float *bm, long b_bs, float b_slope, float *dw,
                              float *scratch, int B, int M, int Nn, int La, int Lb, int K, int bstride, int dil, int pad,
                              float alpha, int accumulate, hipStream_t st)
@@ -524,7 +532,7 @@ static int wgrad_tile_launch(const float *am, long a_bs, float a_slope, const fl
     a.b_slope = b_slope;
     const dim3 grid(nsplit, mg_cdiv(M, 32 * TM) * a.n_tiles, K);
 #define WG_TILE_CASE(TM_, TN_) \
-    if (TM == TM_ && TN == TN_) hipLaunchKernelGGL((wgrad_tile_kernel<TM_, TN_>), grid, dim3(256), 0, st, a);
+    if (TM == TM_ && TN == TN_) hipLaunchKernelGGL((wgrad_tile_kernel<TM_, TN_, REFLECT>), grid, dim3(256), 0, st, a);
     WG_TILE_CASE(1, 1) WG_TILE_CASE(1, 2) WG_TILE_CASE(1, 4)
     WG_TILE_CASE(2, 1) WG_TILE_CASE(2, 2) WG_TILE_CASE(2, 4)
     WG_TILE_CASE(4, 1) WG_TILE_CASE(4, 2) WG_TILE_CASE(4, 4)

@@ -10,7 +10,12 @@ path with its leaky ReLU in the staging.  A ResnetBlock in the general form is t
 (reflect padding, both leaky ReLUs fused) writes t next to x in a [B, 2C, L] buffer, and one K=1 GEMM over [x ; t]
 with the packs of shortcut and block.4 concatenated gives shortcut(x) + block(x).  With `fused_stack` (default), the
 three blocks of the 64- and 32-channel stages run as one launch each, holding a tile and its 13-sample halo in LDS.
-Inference only.
+
+Training (csrc/melgan_train.hip, autograd.melgan_conv_reflect / melgan_resblock / voc_up): `forward_train` is the same
+function as an autograd tensor, every stage in the general form, the backward in the HIP library: the reflect-padded
+weight gradient mirrors the frame index while it stages the saved pre-activation, the data gradient is the zero-padded
+correlation over the padded length folded back through the reflection, and a ResnetBlock's K = 1 gradients run once
+over [x ; t].  vocoder_train's trainers take a MelVocoder as they take a HiFi-GAN generator.
 """
 import ctypes
 import math
@@ -18,7 +23,7 @@ import math
 import torch
 from torch import nn
 
-from . import ops, _lib
+from . import ops, _lib, autograd as ag
 from ._lib import fptr, check, stream_ptr
 from .vocoder import _WNConv
 
@@ -41,9 +46,7 @@ class _MelWNConv(_WNConv):
         self.weight_v = nn.Parameter(v)
 
 
-def _ptr_at(t, float_offset):
-    fptr(t)
-    return ctypes.c_void_p(t.data_ptr() + 4 * float_offset)
+_ptr_at = ops._at
 
 
 def _conv_reflect(x, x_bs, conv, out, out_bs, B, Ci, L, Co, K, dil, in_slope=1.0, act=None, act_slope=0.0, alpha=1.0,
@@ -192,6 +195,49 @@ class MelGANGenerator(nn.Module):
         _conv_reflect(x, 0, m[len(m) - 2], wav, 0, B, C, L, 1, 7, 1, in_slope=SLOPE, act="tanh")
         return wav
 
+    def forward_train(self, mel, taps=None, scale=1.0):
+        """forward_scaled(mel, scale) as an autograd tensor: gradients reach every weight_g / weight_v (through the
+        torch expression effective_weight(); the effective weight's own gradient comes from the HIP backward), every
+        bias, and mel when it requires grad.  Every stage runs the general form.  taps (dict, optional) receives, under
+        its module path, what fixes each leaky ReLU's side: the input of "model.<i>" (the four in front of the
+        upsamplers and the one in front of the last conv) and of "model.<i>.block.0", and for "model.<i>.block.3" its
+        OUTPUT t, which the backward keeps instead of the input: same sign, same zeros, the negative side scaled by
+        the slope."""
+        nres = self.n_residual_layers
+        if nres > 3:
+            raise _lib.MixganHipError("MelGANGenerator: dilations above 9 are not taken by the HIP conv")
+        if self.ngf % 32:
+            raise _lib.MixganHipError("MelGANGenerator.forward_train: ngf = %d; the general form takes channel counts "
+                                      "that are multiples of 32" % self.ngf)
+        if not mel.is_cuda:
+            raise _lib.MixganHipError("MelGANGenerator on %s: the HIP path has no CPU fallback" % mel.device)
+        B, Ci, L = mel.shape
+        if Ci != self.input_size:
+            raise ValueError("MelGANGenerator: expected %d mel channels, got %d" % (self.input_size, Ci))
+        if L < 4:
+            raise ValueError("MelGANGenerator: %d frames; ReflectionPad1d(3) needs at least 4" % L)
+        m = self.model
+        x = ag.melgan_conv_reflect(mel.float(), m[1].effective_weight(), m[1].bias, 1, 1.0, float(scale))
+        for i, r in enumerate(RATIOS):
+            base = 2 + i * (2 + nres)
+            up = m[base + 1]
+            if taps is not None:
+                taps["model.%d" % base] = x
+            x = ag.voc_up(x, up.effective_weight(), up.bias, r, SLOPE, 1.0)
+            for j in range(nres):
+                blk = m[base + 2 + j]
+                c1, c2, cs = blk.block[2], blk.block[4], blk.shortcut
+                y, xt = ag.melgan_resblock(x, c1.effective_weight(), c1.bias, c2.effective_weight(), c2.bias,
+                                           cs.effective_weight(), cs.bias, blk.dilation, SLOPE)
+                if taps is not None:
+                    taps["model.%d.block.0" % (base + 2 + j)] = x
+                    taps["model.%d.block.3" % (base + 2 + j)] = xt[:, blk.dim:]
+                x = y
+        last = len(m) - 2
+        if taps is not None:
+            taps["model.%d" % (last - 2)] = x
+        return ag.melgan_conv_reflect(x, m[last].effective_weight(), m[last].bias, 1, SLOPE, 1.0, "tanh")
+
 
 class MelVocoder(nn.Module):
     """The parts of the hub's MelVocoder (mel2wav/interface.py) the reference uses: `.mel2wav` and `.inverse`."""
@@ -207,3 +253,9 @@ class MelVocoder(nn.Module):
 
     def forward(self, mel):
         return self.inverse(mel)
+
+    def forward_train(self, mel, taps=None):
+        """mel [B, 80, L] (natural log, as audio.TacotronSTFT gives it) -> [B, 1, 256 L] as an autograd tensor, the
+        1 / ln 10 of vocoder_infer on the first conv: what GeneratorTrainer / VocoderGANTrainer train, so that the
+        trained generator is used at inference as it was trained."""
+        return self.mel2wav.forward_train(mel, taps, 1.0 / math.log(10.0))

@@ -225,6 +225,73 @@ def lrelu_bwd(dy, x, slope, add=None, out=None):
     return out
 
 
+def _at(t, float_offset):
+    fptr(t)
+    return ctypes.c_void_p(t.data_ptr() + 4 * float_offset)
+
+
+def conv1d_reflect_packed(x, packed, bias, Co, K, dilation=1, in_slope=1.0, act=None, act_slope=0.0, alpha=1.0, x_bs=0,
+                          C=None, out=None, out_bs=0, out_off=0):
+    """act(alpha * conv1d(reflection_pad(leaky_relu(x, in_slope), dilation (K-1)/2), w, dilation) + bias) on the
+    MG_PACK_PLAIN pack.  x_bs / C: x is channels [0, C) of a buffer with that batch stride; out / out_bs / out_off:
+    write into a buffer at that float offset and batch stride."""
+    L = _lib.lib()
+    B, Lf = x.shape[0], x.shape[2]
+    Ci = x.shape[1] if C is None else C
+    if out is None:
+        out = torch.empty(B, Co, Lf, device=x.device, dtype=torch.float32)
+    check(L.mg_conv1d_reflect_fwd(fptr(x), x_bs, fptr(packed), fptr(bias, True), _at(out, out_off), out_bs, B, Ci, Lf,
+                                  Co, K, dilation, float(in_slope), ACT[act], float(act_slope), float(alpha),
+                                  stream_ptr()))
+    return out
+
+
+def conv1d_reflect_wgrad(dy, x, K, dilation=1, in_slope=1.0, alpha=1.0, out=None, accumulate=False, x_bs=0, C=None,
+                         dy_bs=0, Co=None):
+    """dW [Co, Ci, K] of conv1d_reflect_packed through the saved pre-activation x (channels [0, C) of a buffer with
+    batch stride x_bs when those are given); dy [B, Co, L], or channels [0, Co) of a buffer with batch stride dy_bs.
+    accumulate adds into `out`."""
+    L = _lib.lib()
+    B, Lf = dy.shape[0], dy.shape[2]
+    Co = dy.shape[1] if Co is None else Co
+    Ci = x.shape[1] if C is None else C
+    dw = out if out is not None else torch.empty(Co, Ci, K, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(L.mg_conv1d_wgrad_scratch_floats(Co, Ci, K), device=x.device, dtype=torch.float32)
+    check(L.mg_conv1d_reflect_wgrad(fptr(dy), dy_bs, fptr(x), x_bs, fptr(dw), fptr(scratch), B, Co, Ci, Lf, K, dilation,
+                                    float(in_slope), float(alpha), int(accumulate), stream_ptr()))
+    return dw
+
+
+def conv1d_reflect_dgrad(dy, w, x, dilation=1, in_slope=1.0, alpha=1.0, add=None, out=None, x_bs=0, add_bs=0, C=None):
+    """dx [B, Ci, L] of conv1d_reflect_packed: the zero-padded correlation of dy with the MG_PACK_DGRAD pack of
+    w [Co, Ci, K] over the padded length, folded back through the reflection, masked by the saved pre-activation x,
+    plus `add` (a residual gradient).  x / add may be channels [0, C) of buffers with batch strides x_bs / add_bs;
+    `out` may be a dense `add`."""
+    L = _lib.lib()
+    B, Co, Lf = dy.shape
+    K = w.shape[2]
+    Ci = x.shape[1] if C is None else C
+    n = L.mg_conv1d_reflect_dgrad_workspace_floats(B, Ci, Lf, K, dilation)
+    if n == 0:
+        raise _lib.MixganHipError("reflect-padded conv: K = %d at dilation %d has no HIP backward" % (K, dilation))
+    ws = torch.empty(n, device=dy.device, dtype=torch.float32)
+    dx = out if out is not None else torch.empty(B, Ci, Lf, device=dy.device, dtype=torch.float32)
+    check(L.mg_conv1d_reflect_dgrad(fptr(dy), fptr(pack_conv_weight(w, PACK_DGRAD)), fptr(x), x_bs, fptr(add, True),
+                                    add_bs, fptr(dx), fptr(ws), n, B, Co, Ci, Lf, K, dilation, float(in_slope),
+                                    float(alpha), stream_ptr()))
+    return dx
+
+
+def lrelu_bwd_strided(dy, dy_off, dy_bs, x, x_off, x_bs, B, C, Lf, slope, out=None):
+    """lrelu_bwd on channel slices: dy and x start dy_off / x_off floats into buffers with batch strides dy_bs / x_bs
+    (mg_reflect_fold_bwd with no padding); out [B, C, L] dense."""
+    if out is None:
+        out = torch.empty(B, C, Lf, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().mg_reflect_fold_bwd(_at(dy, dy_off), dy_bs, _at(x, x_off), x_bs, None, 0, fptr(out), B, C, Lf, 0,
+                                         float(slope), stream_ptr()))
+    return out
+
+
 def conv_transpose1d_dgrad(dy, w, x, in_slope=1.0, alpha=1.0):
     """dx of alpha * conv_transpose1d(leaky_relu(x, in_slope), w [Ci,Co,2u], stride u, padding u/2); dy [B,Co,u*L]."""
     L = _lib.lib()

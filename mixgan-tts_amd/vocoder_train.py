@@ -6,6 +6,10 @@ GeneratorTrainer trains on the mel term alone.  VocoderGANTrainer is HiFi-GAN's 
 the generator phase with the adversarial and feature-matching terms (losses.hifigan_*: the fused HIP loss kernels), over
 any discriminator modules with the published calling convention.  The discriminators themselves (MPD / MSD) are not
 native yet: they are ordinary torch modules.
+
+Both trainers need only .parameters(), .forward_train(mel[, taps]) and .state_dict() of their generator, so a
+melgan.MelVocoder trains in them as a vocoder.Generator does; export_melgan_generator writes what get_vocoder loads for
+MelGAN.
 """
 import torch
 import torch.nn.functional as F
@@ -52,6 +56,13 @@ def _mel_l1(stft, y_hat, y):
 
 def _cpu_state(module):
     return {k: v.detach().cpu() for k, v in module.state_dict().items()}
+
+
+def export_melgan_generator(vocoder, path):
+    """Write the bare `mel2wav` state dict of a melgan.MelVocoder (or of a MelGANGenerator) -- the layout of the
+    melgan-neurips hub files -- which vocoder.get_vocoder({"vocoder": {"model": "MelGAN", ...}}, checkpoint_path=path)
+    loads."""
+    torch.save(_cpu_state(getattr(vocoder, "mel2wav", vocoder)), path)
 
 
 def _load_present(ckpt, **targets):
