@@ -124,27 +124,40 @@ class _PosteriorFn(torch.autograd.Function):
 # differentiable building blocks for the JCU discriminator and the FFT blocks: every forward and
 # backward below is a call into the HIP library; torch.autograd only chains them.
 # --------------------------------------------------------------------------------------------------
+def _pack(w, mode=ops.PACK_PLAIN):
+    """MFMA pack of a convolution weight.  A module parameter (or a view of one) keeps its pack in ops.pack_cached,
+    refreshed in place so that a captured graph goes on reading the same address; anything else -- an effective weight,
+    or several weights stacked by torch.cat (the attention's q/k/v, the linguistic encoder's stacked convolutions), is a
+    fresh tensor every step -- is packed here and the pack dies with its use."""
+    owner = w._base if w._base is not None else w
+    return ops.pack_cached(w, mode) if isinstance(owner, torch.nn.Parameter) else ops.pack_conv_weight(w, mode)
+
+
 class _Conv1dFn(torch.autograd.Function):
-    """y = act(conv1d(x (+ in_vec), W, b)); x [B,Ci,L] channel-major."""
+    """y = act(conv1d(x (+ in_vec), W, b)); x [B,Ci,L] channel-major.  act "lrelu_s" is leaky ReLU with the runtime
+    slope act_slope, differentiated through the activated y (slope > 0 keeps the sign)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, in_vec, stride, padding, act):
+    def forward(ctx, x, weight, bias, in_vec, stride, padding, act, act_slope):
         _require_cuda(x)
         x = x.contiguous()
         Co, Ci, K = weight.shape
-        y = ops.conv1d_packed(x, ops.pack_cached(weight), None if bias is None else bias.detach(), Co, K, stride,
-                              padding, act, in_vec=None if in_vec is None else in_vec.detach().contiguous(), split=True)
+        y = ops.conv1d_packed(x, _pack(weight), None if bias is None else bias.detach(), Co, K, stride, padding, act,
+                              in_vec=None if in_vec is None else in_vec.detach().contiguous(), act_slope=act_slope,
+                              split=True)
         ctx.save_for_backward(x, weight, y if act else None, in_vec)
-        ctx.cfg = (stride, padding, act, bias is not None)
+        ctx.cfg = (stride, padding, act, act_slope, bias is not None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, weight, y, in_vec = ctx.saved_tensors
-        stride, padding, act, has_bias = ctx.cfg
+        stride, padding, act, act_slope, has_bias = ctx.cfg
         Co, Ci, K = weight.shape
         gy = gy.contiguous()
-        dpre = ops.act_bwd(gy, y, act) if act else gy
+        dpre = gy
+        if act:
+            dpre = ops.lrelu_bwd(gy, y, act_slope) if act == "lrelu_s" else ops.act_bwd(gy, y, act)
         need = ctx.needs_input_grad
         vec = None if in_vec is None else in_vec.detach().contiguous()
         dw = ops.conv1d_wgrad(dpre, x, K, stride, padding, x_vec=vec) if need[1] else None
@@ -155,15 +168,15 @@ class _Conv1dFn(torch.autograd.Function):
             src = dpre
             if stride > 1:
                 src = ops.upsample_zero(dpre, stride, (dpre.shape[2] - 1) * stride + 1)
-            dx = ops.conv1d_packed(src, ops.pack_cached(weight, ops.PACK_DGRAD), None, Ci, K, 1, K - 1 - padding,
-                                   Lout=Lin, split=True)
+            dx = ops.conv1d_packed(src, _pack(weight, ops.PACK_DGRAD), None, Ci, K, 1, K - 1 - padding, Lout=Lin,
+                                   split=True)
             if in_vec is not None and need[3]:
                 dvec = ops.rowsum(dx, per_batch=True)
-        return dx if need[0] else None, dw, db, dvec, None, None, None
+        return dx if need[0] else None, dw, db, dvec, None, None, None, None
 
 
-def conv1d(x, weight, bias=None, stride=1, padding=0, act=None, in_vec=None):
-    return _Conv1dFn.apply(x, weight, bias, in_vec, stride, padding, act)
+def conv1d(x, weight, bias=None, stride=1, padding=0, act=None, in_vec=None, act_slope=0.0):
+    return _Conv1dFn.apply(x, weight, bias, in_vec, stride, padding, act, act_slope)
 
 
 class _StepMlpFn(torch.autograd.Function):
@@ -385,6 +398,11 @@ def batchnorm_act(x, gamma, beta, keep, drop_scale, act, eps, group=None):
 # (vocoder.Generator.forward_train).  The HIP side differentiates with respect to the EFFECTIVE weight; weight norm is
 # a torch expression in front of these functions.
 # --------------------------------------------------------------------------------------------------
+def weight_norm(v, g):
+    """The effective weight of torch.nn.utils.weight_norm(dim=0): g v / |v| per output row."""
+    return v * (g / v.flatten(1).norm(dim=1).view(-1, 1, 1))
+
+
 class _MelDiffFn(torch.autograd.Function):
     """log-mel of x [B, N] (mg_stft_mel); the gradient recomputes each frame's spectrum (mg_stft_mel_bwd)."""
 
@@ -425,16 +443,25 @@ def mel_diff(x, stft):
     return _MelDiffFn.apply(x, stft)
 
 
-def _voc_conv_bwd(g, x, w, dil, pad, in_slope, alpha, need=(True, True, True), add=None):
+REFLECT = "reflect"   # voc_conv's `pad`: ReflectionPad1d(dil (K - 1) / 2) in front of the convolution (MelGAN)
+
+
+def _voc_conv_bwd(g, x, w, dil, pad, in_slope, alpha, need=(True, True, True), add=None, x_bs=0, add_bs=0, C=None):
     """(dw, db, dx), each where `need` asks for it, of alpha * conv1d(leaky_relu(x, in_slope), w [Co,Ci,K], dilation dil,
     padding pad) + b, from the output's gradient g and the saved pre-activation x.  The data gradient is the forward
     kernel on the transposed, tap-flipped pack with pad' = dil (K-1) - pad, then masked in place; `add` (a residual
-    branch's gradient) joins in the mask's pass."""
+    branch's gradient) joins in the mask's pass.  pad = REFLECT: the reflect-padded kernels (csrc/melgan_train.hip), which
+    also take x / add as channels [0, C) of buffers with batch strides x_bs / add_bs."""
     Ci, K = w.shape[1], w.shape[2]
-    dw = ops.conv1d_wgrad_ex(g, x, K, dil, pad, in_slope, alpha) if need[0] else None
+    dw = dx = None
+    if need[0] and pad == REFLECT:
+        dw = ops.conv1d_reflect_wgrad(g, x, K, dil, in_slope, alpha, x_bs=x_bs, C=C)
+    elif need[0]:
+        dw = ops.conv1d_wgrad_ex(g, x, K, dil, pad, in_slope, alpha)
     db = ops.rowsum(g) if need[1] else None
-    dx = None
-    if need[2]:
+    if need[2] and pad == REFLECT:
+        dx = ops.conv1d_reflect_dgrad(g, w, x, dil, in_slope, alpha, add=add, x_bs=x_bs, add_bs=add_bs, C=C)
+    elif need[2]:
         dx = ops.conv1d_packed(g, ops.pack_conv_weight(w, ops.PACK_DGRAD), None, Ci, K, 1, dil * (K - 1) - pad,
                                alpha=alpha, Lout=x.shape[2], dilation=dil)
         if in_slope != 1.0 or add is not None:
@@ -444,13 +471,17 @@ def _voc_conv_bwd(g, x, w, dil, pad, in_slope, alpha, need=(True, True, True), a
 
 class _VocConvFn(torch.autograd.Function):
     """y = act(alpha * conv1d(leaky_relu(x, in_slope), w, dilation, padding) + b), act None or "tanh" (conv_pre and
-    conv_post).  Saves x, w (and y for tanh)."""
+    conv_post; with pad = REFLECT, MelGAN's first conv -- in_slope 1, alpha the mel scale -- and its last).  Saves x, w
+    (and y for tanh)."""
 
     @staticmethod
     def forward(ctx, x, w, b, dil, pad, in_slope, alpha, act):
         Co, Ci, K = w.shape
-        y = ops.conv1d_packed(x, ops.pack_conv_weight(w, ops.PACK_PLAIN), b, Co, K, 1, pad, act=act, alpha=alpha,
-                              dilation=dil, in_slope=in_slope)
+        packed = ops.pack_conv_weight(w, ops.PACK_PLAIN)
+        if pad == REFLECT:
+            y = ops.conv1d_reflect_packed(x, packed, b, Co, K, dil, in_slope, act, 0.0, alpha)
+        else:
+            y = ops.conv1d_packed(x, packed, b, Co, K, 1, pad, act=act, alpha=alpha, dilation=dil, in_slope=in_slope)
         ctx.save_for_backward(x, w, y if act else None)
         ctx.cfg = (dil, pad, in_slope, alpha, act)
         return y
@@ -516,7 +547,9 @@ class _VocUpFn(torch.autograd.Function):
 
 
 def voc_conv(x, w, b, dil, pad, in_slope=1.0, alpha=1.0, act=None):
-    return _VocConvFn.apply(x, w.contiguous(), b, dil, pad, in_slope, alpha, act)
+    """pad: zero padding per side, or REFLECT."""
+    _require_cuda(x, w, b)
+    return _VocConvFn.apply(x.contiguous(), w.contiguous(), b, dil, pad, in_slope, alpha, act)
 
 
 def voc_pair(r, w1, b1, w2, b2, dil, pad1, pad2, slope):
@@ -530,32 +563,6 @@ def voc_up(x, w, b, u, slope, alpha):
 # --------------------------------------------------------------------------------------------------
 # MelGAN generator (melgan.MelGANGenerator.forward_train; csrc/melgan_train.hip).  Effective weights, as above.
 # --------------------------------------------------------------------------------------------------
-class _MelConvReflectFn(torch.autograd.Function):
-    """y = act(alpha * conv1d(reflection_pad(leaky_relu(x, in_slope)), w, dilation) + b), act None or "tanh": the first
-    conv (in_slope 1, alpha the mel scale) and the last (tanh).  Saves x, w (and y for tanh)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, dil, in_slope, alpha, act):
-        Co, Ci, K = w.shape
-        y = ops.conv1d_reflect_packed(x, ops.pack_conv_weight(w, ops.PACK_PLAIN), b, Co, K, dil, in_slope, act, 0.0, alpha)
-        ctx.save_for_backward(x, w, y if act else None)
-        ctx.cfg = (dil, in_slope, alpha, act)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, y = ctx.saved_tensors
-        dil, in_slope, alpha, act = ctx.cfg
-        g = g.contiguous()
-        if act:
-            g = ops.act_bwd(g, y, act)
-        need = ctx.needs_input_grad
-        dx = ops.conv1d_reflect_dgrad(g, w, x, dil, in_slope, alpha) if need[0] else None
-        dw = ops.conv1d_reflect_wgrad(g, x, w.shape[2], dil, in_slope, alpha) if need[1] else None
-        db = ops.rowsum(g) if need[2] else None
-        return dx, dw, db, None, None, None, None
-
-
 class _MelResBlockFn(torch.autograd.Function):
     """MelGAN ResnetBlock(C, dil): t = lrelu(conv3(reflection_pad(lrelu(x)), w1, dil) + b1), y = ws x + w2 t + bs + b2,
     the last line one K = 1 GEMM over the [B, 2C, L] buffer [x ; t].  Saves that buffer -- x is the first leaky ReLU's
@@ -586,15 +593,8 @@ class _MelResBlockFn(torch.autograd.Function):
         dmix = ops.conv1d_wgrad(g, buf, 1)                                        # d[Ws | W2]  [C, 2C, 1]
         dbuf = ops.conv1d_packed(g, ops.pack_conv_weight(wmix, ops.PACK_DGRAD), None, C2, 1)   # [d x (shortcut) ; d t]
         dt = ops.lrelu_bwd_strided(dbuf, C * L, C2 * L, buf, C * L, C2 * L, B, C, L, slope)
-        dw1 = ops.conv1d_reflect_wgrad(dt, buf, 3, dil, slope, x_bs=C2 * L, C=C)
-        db1 = ops.rowsum(dt)
-        dx = ops.conv1d_reflect_dgrad(dt, w1, buf, dil, slope, add=dbuf, x_bs=C2 * L, add_bs=C2 * L, C=C)
+        dw1, db1, dx = _voc_conv_bwd(dt, buf, w1, dil, REFLECT, slope, 1.0, add=dbuf, x_bs=C2 * L, add_bs=C2 * L, C=C)
         return dx, dw1, db1, dmix[:, C:], db, dmix[:, :C], db, None, None
-
-
-def melgan_conv_reflect(x, w, b, dil, in_slope=1.0, alpha=1.0, act=None):
-    _require_cuda(x, w, b)
-    return _MelConvReflectFn.apply(x.contiguous(), w.contiguous(), b, dil, in_slope, alpha, act)
 
 
 def melgan_resblock(x, w1, b1, w2, b2, ws, bs, dil, slope):
@@ -669,42 +669,6 @@ class _ScaleStackFn(torch.autograd.Function):
 
 def scale_stack(x, slope, layers, *params):
     return _ScaleStackFn.apply(x, slope, tuple(layers), *params)
-
-
-class _ConvSlopeFn(torch.autograd.Function):
-    """y = leaky_relu(conv1d(x, W, b, padding), slope) (slope None: no activation), stride 1, through the MFMA
-    convolution kernel and its DGRAD pack: _Conv1dFn with a runtime slope.  Saves x, W and the activated y."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, padding, slope):
-        _require_cuda(x)
-        x, w = x.contiguous(), w.detach().contiguous()
-        Co, _, K = w.shape
-        y = ops.conv1d_packed(x, ops.pack_conv_weight(w), b.detach(), Co, K, 1, padding,
-                              act=None if slope is None else "lrelu_s", act_slope=slope or 0.0, split=True)
-        ctx.save_for_backward(x, w, None if slope is None else y)
-        ctx.cfg = (padding, slope)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, y = ctx.saved_tensors
-        padding, slope = ctx.cfg
-        Co, Ci, K = w.shape
-        g = g.contiguous()
-        d = g if slope is None else ops.lrelu_bwd(g, y, slope)
-        need = ctx.needs_input_grad
-        dw = ops.conv1d_wgrad(d, x, K, 1, padding) if need[1] else None
-        db = ops.rowsum(d) if need[2] else None
-        dx = None
-        if need[0]:
-            dx = ops.conv1d_packed(d, ops.pack_conv_weight(w, ops.PACK_DGRAD), None, Ci, K, 1, K - 1 - padding,
-                                   Lout=x.shape[2], split=True)
-        return dx, dw, db, None, None
-
-
-def conv1d_slope(x, w, b, padding, slope=None):
-    return _ConvSlopeFn.apply(x, w, b, padding, slope)
 
 
 class _AvgPool4s2Fn(torch.autograd.Function):

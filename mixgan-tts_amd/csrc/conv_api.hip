@@ -73,21 +73,18 @@ extern "C" int mg_conv_transpose_pack(const float *w, float *packed, int Ci, int
     return MG_OK;
 }
 
-template <>
-struct EpiWide<EpiBiasAct> { static constexpr bool value = true; };
-
-// conv_plan for an entry point's epilogue: EpiBiasAct as this file instantiates it, the MelGAN epilogues of melgan.hip
-// (EpiMelGAN 1 / 2), the denoiser's gate (EpiNeedsWM2, base cases only).
+// conv_plan for an entry point's launches: this file's (the path's cases and the wide ones), melgan.hip's reflect-padded
+// and slice-writing ones, the denoiser's gate (EpiNeedsWM2, the path's cases only).
 extern "C" int mg_conv1d_fwd_plan(int B, int Ci, int Lout, int rows, int K, int stride, int dil, size_t scratch_floats,
                                   int epi, mg_conv_plan *out)
 {
     if (!out) return MG_ERR_ARG;
     ConvEpiKind kind;
     switch (epi) {
-    case MG_CONV_EPI_PLAIN: kind = conv_epi_kind<EpiBiasAct>(); break;
-    case MG_CONV_EPI_REFLECT: kind = ConvEpiKind{1, false, false}; break;
-    case MG_CONV_EPI_PHASES_SLICE: kind = ConvEpiKind{2, false, false}; break;
-    case MG_CONV_EPI_NEEDS_WM2: kind = ConvEpiKind{0, false, true}; break;
+    case MG_CONV_EPI_PLAIN: kind = ConvEpiKind{CONV_CASES_PATH_WIDE, false}; break;
+    case MG_CONV_EPI_REFLECT: kind = ConvEpiKind{CONV_CASES_REFLECT, false}; break;
+    case MG_CONV_EPI_PHASES_SLICE: kind = ConvEpiKind{CONV_CASES_SLICE, false}; break;
+    case MG_CONV_EPI_NEEDS_WM2: kind = ConvEpiKind{CONV_CASES_PATH, true}; break;
     default: return MG_ERR_ARG;
     }
     mg_conv_plan p{};
@@ -103,7 +100,7 @@ extern "C" int mg_conv_transpose1d_fwd(const float *in, const float *packed, con
     if (B <= 0 || Lin <= 0 || !tpose_ok(Ci, Co, u)) return MG_ERR_SHAPE;
     ConvShape s{B, Ci, Lin, Lin, 3, 1, 1, Co * u, 0, 0, 1, in_slope};
     EpiBiasAct::Params ep{out, bias, nullptr, alpha, Co, MG_ACT_NONE, 0, 0, nullptr, 0.f, u};
-    return conv_launch<EpiBiasAct>(s, in, nullptr, packed, ep, (hipStream_t)stream);
+    return conv_launch<EpiBiasAct, CONV_CASES_PATH_WIDE>(s, in, nullptr, packed, ep, (hipStream_t)stream);
 }
 
 extern "C" int mg_conv1d_fwd_split(const float *in, const float *in_vec, const float *packed, const float *bias,
@@ -116,7 +113,7 @@ extern "C" int mg_conv1d_fwd_split(const float *in, const float *in_vec, const f
     if (B <= 0 || Ci <= 0 || Co <= 0 || Lin <= 0 || Lout <= 0 || pad < 0 || dil < 1) return MG_ERR_SHAPE;
     ConvShape s{B, Ci, Lin, Lout, K, stride, pad, Co, 0, 0, dil, in_slope, scratch, scratch ? scratch_floats : 0};
     EpiBiasAct::Params ep{out, bias, add, alpha, Co, act, accumulate, 0, nullptr, act_slope};
-    return conv_launch<EpiBiasAct>(s, in, in_vec, packed, ep, (hipStream_t)stream);
+    return conv_launch<EpiBiasAct, CONV_CASES_PATH_WIDE>(s, in, in_vec, packed, ep, (hipStream_t)stream);
 }
 
 extern "C" int mg_conv1d_fwd_ex(const float *in, const float *in_vec, const float *packed, const float *bias,
@@ -144,7 +141,7 @@ extern "C" int mg_conv1x1_fwd_strided(const float *in, long in_bs, const float *
     if ((in_bs != 0 && in_bs < (long)Ci * L) || (out_bs != 0 && out_bs < (long)Co * L)) return MG_ERR_SHAPE;
     ConvShape s{B, Ci, L, L, 1, 1, 0, Co, in_bs, 0};
     EpiBiasAct::Params ep{out, bias, nullptr, 1.f, Co, MG_ACT_NONE, 0, out_bs, nullptr, 0.f};
-    return conv_launch<EpiBiasAct>(s, in, nullptr, packed, ep, (hipStream_t)stream);
+    return conv_launch<EpiBiasAct, CONV_CASES_PATH_WIDE>(s, in, nullptr, packed, ep, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

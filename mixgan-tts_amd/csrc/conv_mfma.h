@@ -249,21 +249,17 @@ struct EpiBiasAct {
     }
 };
 
-// Epilogues that serve the MelGAN generator only (melgan.hip) opt in here, and instantiate only its shapes (conv_launch):
-//   1 = reflect padding (ReflectionPad1d in front of the conv, MelGAN mel2wav/modules.py): an input position l < 0
-//       stages in[-l], l >= Lin stages in[2 (Lin-1) - l] (a launcher guarantees pad < Lin), and every in-tile element
-//       is live -- K = 7 (first and last conv) and K = 3 with dilation <= 9 (the ResnetBlock convs);
-//   2 = the polyphase transposed conv writing a channel slice of a wider buffer (K = 3 only);
-//   3 = zero padding, K = 3 with dilation <= 9: the data gradient of the reflect-padded ResnetBlock conv as the full
-//       correlation over the padded length (melgan_train.hip).
+// An epilogue whose kernels stage their input through reflect padding (ReflectionPad1d in front of the conv, MelGAN
+// mel2wav/modules.py) says so here: an input position l < 0 stages in[-l], l >= Lin stages in[2 (Lin-1) - l] (a launcher
+// guarantees pad < Lin), and every in-tile element is live.
 template <class Epi>
-struct EpiMelGAN { static constexpr int value = 0; };
+struct EpiReflectPad { static constexpr bool value = false; };
 
 // ---------------------------------------------------------------------------------------------
 template <int KW, int STRIDE, int CK, int DILMAX, int MW, int WM, int NNB, class Epi>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvArgs a, typename Epi::Params ep)
 {
-    constexpr bool REFLECT = EpiMelGAN<Epi>::value == 1;
+    constexpr bool REFLECT = EpiReflectPad<Epi>::value;
     static_assert(MW == 2 || (MW == 1 && WM == 1), "wave layouts: 2(M) x 2(N), or 1 x 4 for <= 32 output rows");
     constexpr int NW = 4 / MW;         // waves along the frame axis
     constexpr int NT = NW * 32 * NNB;  // output frames per workgroup
@@ -484,31 +480,39 @@ struct ConvShape {
 
 
 
-// Which instantiations an epilogue has, as the plan sees it.
-//   EpiMelGAN (above): 1 = reflect padding, 2 = the slice-writing polyphase store, 3 = the zero-padded dilation-9
-//       correlation -- their own, small case lists;
-//   EpiWide: also the vocoder shapes (K in {7,11,16,4}, dilations up to 5: hifigan/models.py:19-95,112-143), which only
-//       epilogues that opt in instantiate, to keep build time down;
-//   EpiNeedsWM2: the epilogue pairs two 32-row blocks of one wave (the denoiser's gate), so WM = 1 forms compute nothing.
+// EpiNeedsWM2: the epilogue pairs two 32-row blocks of one wave (the denoiser's gate), so WM = 1 forms compute nothing.
 template <class Epi>
 struct EpiNeedsWM2 { static constexpr bool value = false; };
-template <class Epi>
-struct EpiWide { static constexpr bool value = false; };
 
-struct ConvEpiKind {
-    int melgan;
-    bool wide, needs_wm2;
+// The (K, stride, CK, DILMAX) cases, in matching order; CK must match mg_conv_ck().  A launch names its list
+// (conv_launch's template argument), conv_plan picks from that list and conv_launch instantiates from it.
+enum ConvCases {
+    CONV_CASES_PATH,       // the path's own convolutions: the default
+    CONV_CASES_PATH_WIDE,  // + the vocoder shapes (K in {7,11,16,4}, dilations up to 5: hifigan/models.py:19-95,112-143),
+                           //   which only conv_api.hip's launches ask for, to keep build time down
+    CONV_CASES_REFLECT,    // reflect padding: K = 7 (MelGAN's first and last conv), K = 3 with dilation <= 9 (its ResnetBlocks)
+    CONV_CASES_SLICE,      // the polyphase transposed conv writing a channel slice of a wider buffer (K = 3 only)
+    CONV_CASES_DIL9,       // zero padding, K = 3 with dilation <= 9: the data gradient of the reflect-padded ResnetBlock
+                           //   conv as the full correlation over the padded length (melgan_train.hip)
 };
-template <class Epi>
-static constexpr ConvEpiKind conv_epi_kind() { return ConvEpiKind{EpiMelGAN<Epi>::value, EpiWide<Epi>::value, EpiNeedsWM2<Epi>::value}; }
-
-// The (K, stride, CK, DILMAX) cases, in matching order; CK must match mg_conv_ck().  conv_plan picks from these lists and
-// conv_launch instantiates from them.  BASE: the path's own convolutions, always instantiated.
 #define MG_CONV_CASES_BASE(X) X(1, 1, 32, 1) X(3, 1, 32, 1) X(5, 1, 16, 1) X(9, 1, 16, 1) X(5, 2, 16, 1)
 #define MG_CONV_CASES_WIDE(X) X(3, 1, 32, 5) X(7, 1, 16, 5) X(11, 1, 16, 5) X(16, 1, 16, 1) X(4, 1, 16, 1)
 #define MG_CONV_CASES_REFLECT(X) X(3, 1, 32, 9) X(7, 1, 16, 1)
 #define MG_CONV_CASES_SLICE(X) X(3, 1, 32, 1)
 #define MG_CONV_CASES_DIL9(X) X(3, 1, 32, 9)
+// Every list with its cases: LIST(id, the list's X(...) cases).  The one chain conv_plan and conv_launch both expand.
+#define MG_CONV_LISTS(LIST, X)                                                   \
+    LIST(CONV_CASES_PATH, MG_CONV_CASES_BASE(X))                                 \
+    LIST(CONV_CASES_PATH_WIDE, MG_CONV_CASES_BASE(X) MG_CONV_CASES_WIDE(X))      \
+    LIST(CONV_CASES_REFLECT, MG_CONV_CASES_REFLECT(X))                           \
+    LIST(CONV_CASES_SLICE, MG_CONV_CASES_SLICE(X))                               \
+    LIST(CONV_CASES_DIL9, MG_CONV_CASES_DIL9(X))
+
+// What the plan needs to know of a launch: its case list, and whether its epilogue needs WM = 2.
+struct ConvEpiKind {
+    ConvCases cases;
+    bool needs_wm2;
+};
 
 // 256-frame tiles of the one-block form only while the slab fits the register staging (<= 32 elements per thread)
 static constexpr bool conv_big_slab(int kw, int stride, int ck, int dilmax)
@@ -530,18 +534,12 @@ static inline int conv_plan(int B, int Ci, int Lout, int Mrows, int K, int strid
         p->kw = KW_, p->stride = ST_, p->ck = CK_, p->dilmax = DM_; \
         found = true;                                            \
     }
-    if (e.melgan == 1) {
-        MG_CONV_CASES_REFLECT(MG_CONV_PICK)
-    } else if (e.melgan == 2) {
-        MG_CONV_CASES_SLICE(MG_CONV_PICK)
-    } else if (e.melgan == 3) {
-        MG_CONV_CASES_DIL9(MG_CONV_PICK)
-    } else {
-        MG_CONV_CASES_BASE(MG_CONV_PICK)
-        if (e.wide) {
-            MG_CONV_CASES_WIDE(MG_CONV_PICK)
-        }
+#define MG_CONV_LIST(ID_, CASES_) \
+    if (e.cases == ID_) {         \
+        CASES_                    \
     }
+    MG_CONV_LISTS(MG_CONV_LIST, MG_CONV_PICK)
+#undef MG_CONV_LIST
 #undef MG_CONV_PICK
     if (!found) return MG_ERR_SHAPE;
     const int nchunks = mg_round_up(Ci, p->ck) / p->ck;
@@ -633,27 +631,21 @@ static int conv_launch_k(const ConvShape &s, const mg_conv_plan &pl, const float
     return MG_ERR_SHAPE;
 }
 
-template <class Epi>
+template <class Epi, ConvCases CASES = CONV_CASES_PATH>
 static int conv_launch(const ConvShape &s, const float *in, const float *in_vec, const float *wp,
                        const typename Epi::Params &ep, hipStream_t st)
 {
     mg_conv_plan pl;
     MG_TRY(conv_plan(s.B, s.Ci, s.Lout, s.Mrows, s.K, s.stride, s.dil, s.scratch != nullptr, s.scratch_floats,
-                     conv_epi_kind<Epi>(), &pl));
+                     ConvEpiKind{CASES, EpiNeedsWM2<Epi>::value}, &pl));
 #define MG_CONV_CASE(KW_, ST_, CK_, DM_) \
     if (pl.kw == KW_ && pl.stride == ST_ && pl.dilmax == DM_) return conv_launch_k<KW_, ST_, CK_, DM_, Epi>(s, pl, in, in_vec, wp, ep, st);
-    if constexpr (EpiMelGAN<Epi>::value == 1) {
-        MG_CONV_CASES_REFLECT(MG_CONV_CASE)
-    } else if constexpr (EpiMelGAN<Epi>::value == 2) {
-        MG_CONV_CASES_SLICE(MG_CONV_CASE)
-    } else if constexpr (EpiMelGAN<Epi>::value == 3) {
-        MG_CONV_CASES_DIL9(MG_CONV_CASE)
-    } else {
-        MG_CONV_CASES_BASE(MG_CONV_CASE)
-        if constexpr (EpiWide<Epi>::value) {
-            MG_CONV_CASES_WIDE(MG_CONV_CASE)
-        }
+#define MG_CONV_LIST(ID_, CASES_)      \
+    if constexpr (CASES == ID_) {      \
+        CASES_                         \
     }
+    MG_CONV_LISTS(MG_CONV_LIST, MG_CONV_CASE)
+#undef MG_CONV_LIST
 #undef MG_CONV_CASE
     return MG_ERR_SHAPE;
 }

@@ -27,11 +27,11 @@
 #include "conv_mfma.h"
 
 // ---------------------------------------------------------------------------------------------
-// Reflect-padded convolution and the slice-writing upsampler (conv_mfma.h, EpiMelGAN)
+// Reflect-padded convolution and the slice-writing upsampler, each with a case list of its own (conv_mfma.h, ConvCases)
 // ---------------------------------------------------------------------------------------------
 struct EpiReflect : EpiBiasAct {};
 template <>
-struct EpiMelGAN<EpiReflect> { static constexpr int value = 1; };
+struct EpiReflectPad<EpiReflect> { static constexpr bool value = true; };
 
 // EpiBiasAct::run_phases with the batch stride out_bs (0 -> Co * u * Lin): the upsampler of a general-form stage writes
 // channels [0, C) of the first block's [B, 2C, L] buffer.
@@ -78,8 +78,6 @@ struct EpiPhasesSlice {
         }
     }
 };
-template <>
-struct EpiMelGAN<EpiPhasesSlice> { static constexpr int value = 2; };
 
 extern "C" int mg_conv1d_reflect_fwd(const float *in, long in_bs, const float *packed, const float *bias, float *out,
                                      long out_bs, int B, int Ci, int L, int Co, int K, int dil, float in_slope, int act,
@@ -93,7 +91,7 @@ extern "C" int mg_conv1d_reflect_fwd(const float *in, long in_bs, const float *p
     if (L <= pad) return MG_ERR_SHAPE;   // ReflectionPad1d needs pad < L
     ConvShape s{B, Ci, L, L, K, 1, pad, Co, in_bs, 0, dil, in_slope};
     EpiBiasAct::Params ep{out, bias, nullptr, alpha, Co, act, 0, out_bs, nullptr, act_slope};
-    return conv_launch<EpiReflect>(s, in, nullptr, packed, ep, (hipStream_t)stream);
+    return conv_launch<EpiReflect, CONV_CASES_REFLECT>(s, in, nullptr, packed, ep, (hipStream_t)stream);
 }
 
 extern "C" int mg_conv_transpose1d_fwd_slice(const float *in, const float *packed, const float *bias, float *out,
@@ -106,7 +104,7 @@ extern "C" int mg_conv_transpose1d_fwd_slice(const float *in, const float *packe
     if (out_bs != 0 && out_bs < (long)Co * u * Lin) return MG_ERR_SHAPE;
     ConvShape s{B, Ci, Lin, Lin, 3, 1, 1, Co * u, 0, 0, 1, in_slope};
     EpiBiasAct::Params ep{out, bias, nullptr, alpha, Co, MG_ACT_NONE, 0, out_bs, nullptr, 0.f, u};
-    return conv_launch<EpiPhasesSlice>(s, in, nullptr, packed, ep, (hipStream_t)stream);
+    return conv_launch<EpiPhasesSlice, CONV_CASES_SLICE>(s, in, nullptr, packed, ep, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 //                             finalize, so the bits repeat run to run
 //   mg_conv1d_reflect_dgrad   (a) P = alpha * dy (*) W^T with the taps flipped, zero padding 2p, over the PADDED length
 //                                 L + 2p: the forward conv kernel on the MG_PACK_DGRAD pack (K = 3 at dilation <= 9 has
-//                                 its own case list, EpiDil9; K = 7 is mg_conv1d_fwd_ex's)
+//                                 its own case list, CONV_CASES_DIL9; K = 7 is mg_conv1d_fwd_ex's)
 //                             (b) mg_reflect_fold_bwd
 //   mg_reflect_fold_bwd       da[i] = P[i+p] + [1 <= i <= p] P[p-i] + [L-1-p <= i <= L-2] P[2(L-1)-i+p] (the gradient of
 //                             each mirrored position returns to the sample it copied; for L <= 2p both mirrors can
@@ -21,9 +21,7 @@
 #include "conv_mfma.h"
 #include "wgrad_mfma.h"
 
-struct EpiDil9 : EpiBiasAct {};
-template <>
-struct EpiMelGAN<EpiDil9> { static constexpr int value = 3; };
+struct EpiDil9 : EpiBiasAct {};   // EpiBiasAct under the name this file's kernels carry; its cases are CONV_CASES_DIL9
 
 namespace {
 
@@ -113,7 +111,7 @@ extern "C" int mg_conv1d_reflect_dgrad(const float *dy, const float *packed, con
     if (K == 3) {
         ConvShape s{B, Co, L, Lp, 3, 1, 2 * p, Ci, 0, 0, dil, 1.f};
         EpiBiasAct::Params ep{workspace, nullptr, nullptr, alpha, Ci, MG_ACT_NONE, 0, 0, nullptr, 0.f};
-        MG_TRY(conv_launch<EpiDil9>(s, dy, nullptr, packed, ep, (hipStream_t)stream));
+        MG_TRY((conv_launch<EpiDil9, CONV_CASES_DIL9>(s, dy, nullptr, packed, ep, (hipStream_t)stream)));
     } else {
         MG_TRY(mg_conv1d_fwd_ex(dy, nullptr, packed, nullptr, nullptr, workspace, B, Co, L, Ci, Lp, K, 1, 2 * p, 1, 1.f,
                                 MG_ACT_NONE, 0.f, alpha, 0, stream));

@@ -47,8 +47,7 @@ class NormConv1d(nn.Module):
     def effective_weight(self):
         """weight_norm: g v / |v| per output row.  spectral_norm: W / sigma after this call's power iteration."""
         if not self.spectral:
-            v = self.weight_v
-            return v * (self.weight_g / v.flatten(1).norm(dim=1).view(-1, 1, 1))
+            return A.weight_norm(self.weight_v, self.weight_g)
         W = self.weight_orig
         mat = W.flatten(1)
         u, v = self.weight_u, self.weight_v
@@ -76,8 +75,9 @@ class DiscriminatorS(nn.Module):
         layers = [g[3:] for g in MSD_LAYERS[:_STACK]]
         fmap = list(A.scale_stack(x, LRELU_SLOPE, layers, *params))
         last = self.convs[_STACK]
-        fmap.append(A.conv1d_slope(fmap[-1], last.effective_weight(), last.bias, last.geometry[5], LRELU_SLOPE))
-        x = A.conv1d_slope(fmap[-1], self.conv_post.effective_weight(), self.conv_post.bias, MSD_POST[5], None)
+        fmap.append(A.conv1d(fmap[-1], last.effective_weight(), last.bias, 1, last.geometry[5], "lrelu_s",
+                             act_slope=LRELU_SLOPE))
+        x = A.conv1d(fmap[-1], self.conv_post.effective_weight(), self.conv_post.bias, 1, MSD_POST[5])
         fmap.append(x)
         return torch.flatten(x, 1, -1), fmap
 

@@ -11,8 +11,8 @@ path with its leaky ReLU in the staging.  A ResnetBlock in the general form is t
 with the packs of shortcut and block.4 concatenated gives shortcut(x) + block(x).  With `fused_stack` (default), the
 three blocks of the 64- and 32-channel stages run as one launch each, holding a tile and its 13-sample halo in LDS.
 
-Training (csrc/melgan_train.hip, autograd.melgan_conv_reflect / melgan_resblock / voc_up): `forward_train` is the same
-function as an autograd tensor, every stage in the general form, the backward in the HIP library: the reflect-padded
+Training (csrc/melgan_train.hip, autograd.voc_conv with pad = REFLECT / melgan_resblock / voc_up): `forward_train` is
+the same function as an autograd tensor, every stage in the general form, the backward in the HIP library: the reflect-padded
 weight gradient mirrors the frame index while it stages the saved pre-activation, the data gradient is the zero-padded
 correlation over the padded length folded back through the reflection, and a ResnetBlock's K = 1 gradients run once
 over [x ; t].  vocoder_train's trainers take a MelVocoder as they take a HiFi-GAN generator.
@@ -44,16 +44,6 @@ class _MelWNConv(_WNConv):
         self.bias = nn.Parameter(torch.empty(bias_n).uniform_(-bound, bound))
         self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1).clone())
         self.weight_v = nn.Parameter(v)
-
-
-_ptr_at = ops._at
-
-
-def _conv_reflect(x, x_bs, conv, out, out_bs, B, Ci, L, Co, K, dil, in_slope=1.0, act=None, act_slope=0.0, alpha=1.0,
-                  x_off=0, out_off=0):
-    check(_lib.lib().mg_conv1d_reflect_fwd(_ptr_at(x, x_off), x_bs, fptr(conv.packed(ops.PACK_PLAIN)),
-                                           fptr(conv.bias.detach()), _ptr_at(out, out_off), out_bs, B, Ci, L, Co, K, dil,
-                                           float(in_slope), ops.ACT[act], float(act_slope), float(alpha), stream_ptr()))
 
 
 class ResnetBlock(nn.Module):
@@ -103,8 +93,9 @@ class ResnetBlock(nn.Module):
     def forward_general(self, buf, out, out_bs, B, L):
         """buf [B, 2C, L] with x in channels [0, C): t -> channels [C, 2C); the block output -> out (batch stride out_bs)."""
         C = self.dim
-        _conv_reflect(buf, 2 * C * L, self.block[2], buf, 2 * C * L, B, C, L, C, 3, self.dilation, in_slope=SLOPE,
-                      act="lrelu_s", act_slope=SLOPE, out_off=C * L)
+        c1 = self.block[2]
+        ops.conv1d_reflect_packed(buf, c1.packed(ops.PACK_PLAIN), c1.bias.detach(), C, 3, self.dilation, SLOPE, "lrelu_s",
+                                  SLOPE, x_bs=2 * C * L, C=C, out=buf, out_bs=2 * C * L, out_off=C * L)
         packed, bias = self.mix_pack(False)
         check(_lib.lib().mg_conv1x1_fwd_strided(fptr(buf), 2 * C * L, fptr(packed), fptr(bias), fptr(out), out_bs, B,
                                                 2 * C, L, C, stream_ptr()))
@@ -150,9 +141,8 @@ class MelGANGenerator(nn.Module):
     def forward(self, mel):
         return self.forward_scaled(mel, 1.0)
 
-    @torch.no_grad()
-    def forward_scaled(self, mel, scale):
-        """forward(mel * scale), the scale riding on the first conv's alpha (no pass over the mel)."""
+    def _check_input(self, mel):
+        """(B, Ci, L) of a mel both forwards can take."""
         if not mel.is_cuda:
             raise _lib.MixganHipError("MelGANGenerator on %s: the HIP path has no CPU fallback" % mel.device)
         B, Ci, L = mel.shape
@@ -162,11 +152,16 @@ class MelGANGenerator(nn.Module):
             raise ValueError("MelGANGenerator: %d frames; ReflectionPad1d(3) needs at least 4" % L)
         if self.n_residual_layers > 3:
             raise _lib.MixganHipError("MelGANGenerator: dilations above 9 are not taken by the HIP conv")
+        return B, Ci, L
+
+    @torch.no_grad()
+    def forward_scaled(self, mel, scale):
+        """forward(mel * scale), the scale riding on the first conv's alpha (no pass over the mel)."""
+        B, Ci, L = self._check_input(mel)
         mel = mel.float().contiguous()
         m = self.model
         C = 16 * self.ngf
-        x = torch.empty(B, C, L, device=mel.device, dtype=torch.float32)
-        _conv_reflect(mel, 0, m[1], x, 0, B, Ci, L, C, 7, 1, alpha=scale)
+        x = ops.conv1d_reflect_packed(mel, m[1].packed(ops.PACK_PLAIN), m[1].bias.detach(), C, 7, alpha=scale)
         nres = self.n_residual_layers
         for i, r in enumerate(RATIOS):
             base = 2 + i * (2 + nres)
@@ -191,9 +186,9 @@ class MelGANGenerator(nn.Module):
                 else:
                     x = torch.empty(B, C, L, device=mel.device, dtype=torch.float32)
                     blk.forward_general(bufs[j % 2], x, 0, B, L)
-        wav = torch.empty(B, 1, L, device=mel.device, dtype=torch.float32)
-        _conv_reflect(x, 0, m[len(m) - 2], wav, 0, B, C, L, 1, 7, 1, in_slope=SLOPE, act="tanh")
-        return wav
+        last = m[len(m) - 2]
+        return ops.conv1d_reflect_packed(x, last.packed(ops.PACK_PLAIN), last.bias.detach(), 1, 7, in_slope=SLOPE,
+                                         act="tanh")
 
     def forward_train(self, mel, taps=None, scale=1.0):
         """forward_scaled(mel, scale) as an autograd tensor: gradients reach every weight_g / weight_v (through the
@@ -203,21 +198,13 @@ class MelGANGenerator(nn.Module):
         upsamplers and the one in front of the last conv) and of "model.<i>.block.0", and for "model.<i>.block.3" its
         OUTPUT t, which the backward keeps instead of the input: same sign, same zeros, the negative side scaled by
         the slope."""
-        nres = self.n_residual_layers
-        if nres > 3:
-            raise _lib.MixganHipError("MelGANGenerator: dilations above 9 are not taken by the HIP conv")
+        self._check_input(mel)
         if self.ngf % 32:
             raise _lib.MixganHipError("MelGANGenerator.forward_train: ngf = %d; the general form takes channel counts "
                                       "that are multiples of 32" % self.ngf)
-        if not mel.is_cuda:
-            raise _lib.MixganHipError("MelGANGenerator on %s: the HIP path has no CPU fallback" % mel.device)
-        B, Ci, L = mel.shape
-        if Ci != self.input_size:
-            raise ValueError("MelGANGenerator: expected %d mel channels, got %d" % (self.input_size, Ci))
-        if L < 4:
-            raise ValueError("MelGANGenerator: %d frames; ReflectionPad1d(3) needs at least 4" % L)
+        nres = self.n_residual_layers
         m = self.model
-        x = ag.melgan_conv_reflect(mel.float(), m[1].effective_weight(), m[1].bias, 1, 1.0, float(scale))
+        x = ag.voc_conv(mel.float(), m[1].effective_weight(), m[1].bias, 1, ag.REFLECT, 1.0, float(scale))
         for i, r in enumerate(RATIOS):
             base = 2 + i * (2 + nres)
             up = m[base + 1]
@@ -236,7 +223,7 @@ class MelGANGenerator(nn.Module):
         last = len(m) - 2
         if taps is not None:
             taps["model.%d" % (last - 2)] = x
-        return ag.melgan_conv_reflect(x, m[last].effective_weight(), m[last].bias, 1, SLOPE, 1.0, "tanh")
+        return ag.voc_conv(x, m[last].effective_weight(), m[last].bias, 1, ag.REFLECT, SLOPE, 1.0, "tanh")
 
 
 class MelVocoder(nn.Module):

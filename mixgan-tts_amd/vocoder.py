@@ -16,7 +16,8 @@ one buffer and the 1/3 is folded into the next convolution (leaky ReLU is positi
 The network is walked in one place, Generator._walk, with one of two site sets: _Infer (`forward`: no_grad, cached packs,
 post-activations fused into epilogues) or _Train (`forward_train`: autograd Functions that keep each pre-activation and
 differentiate in csrc/vocoder_train.hip; weight norm stays a torch expression).  vocoder_train's trainers put HiFi-GAN's
-mel loss and the full GAN step (over torch discriminators: the MPD / MSD are not native yet) on forward_train.
+mel loss and the full GAN step on forward_train (the multi-scale discriminator is native, hifigan_discriminators.py; the
+multi-period one is still a torch module).
 """
 import math
 
@@ -45,8 +46,7 @@ class _WNConv(nn.Module):
     def effective_weight(self):
         if "weight" in self._parameters:
             return self.weight
-        v = self.weight_v
-        return v * (self.weight_g / v.flatten(1).norm(dim=1).view(-1, 1, 1))
+        return ag.weight_norm(self.weight_v, self.weight_g)
 
     def remove_weight_norm(self):
         if "weight" not in self._parameters:

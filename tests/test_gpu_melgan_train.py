@@ -1,4 +1,4 @@
-"""GPU parity of MelGAN generator training (csrc/melgan_train.hip, autograd.melgan_conv_reflect / melgan_resblock,
+"""GPU parity of MelGAN generator training (csrc/melgan_train.hip, autograd.voc_conv with pad = REFLECT / melgan_resblock,
 MelGANGenerator.forward_train, the two vocoder trainers over a MelVocoder) against float64 torch autograd on the CPU,
 computed here.  The reference conv is F.conv1d(F.pad(F.leaky_relu(x, s), (p, p), mode="reflect"), w, dilation=dil).
 
