@@ -630,7 +630,14 @@ int mg_loss_grad(const float *a, const float *b, float c, int mode, const float 
  * out[1+MG_LOSS_GROUPS+k] = mean_k; fixed summation order.  scratch:
  * mg_multi_loss_scratch_floats() floats, ZERO before the first call (the kernel keeps a ticket in it and re-arms it),
  * private to one stream.  mg_multi_loss_bwd: da_k = g[0] * weight_k / n_k * {2(a-c) | sign(a-b)} for every term
- * whose da is not NULL. */
+ * whose da is not NULL.
+ * Two more modes for MelGAN's hinge objective: mode 2 = mean max(0, 1 + c a) (c = -1 on real logits, +1 on generated
+ * ones; da = c where 1 + c a > 0, else 0) and mode 3 = mean a (da = 1), each times g[0] weight / n.  Any other mode is
+ * MG_ERR_SHAPE before any launch. */
+#define MG_LOSSMODE_MSE 0
+#define MG_LOSSMODE_L1 1
+#define MG_LOSSMODE_HINGE 2
+#define MG_LOSSMODE_MEAN 3
 #define MG_LOSS_MAX_TERMS 16
 #define MG_LOSS_GROUPS 4
 typedef struct MgLossTerm {
@@ -638,7 +645,7 @@ typedef struct MgLossTerm {
     const float *b;   /* mode 1 only */
     float *da;        /* backward only; NULL = no gradient wanted */
     size_t n;
-    float c;          /* mode 0 only */
+    float c;          /* mode 0: the constant; mode 2: the sign */
     float weight;
     int32_t mode;
     int32_t group;
@@ -961,7 +968,13 @@ int mg_dtw(const float *a, const float *b, const int *a_len, const int *b_len, i
  * a null pointer MG_ERR_ARG.  `packed` is a derived cache in MFMA fragment order, per group:
  *   MG_GCONV_FWD   [G][Cog/32 up][K][Cig/2][64]: lane -> w[row lane&31, ci 2q + lane>>5, tap]
  *   MG_GCONV_DGRAD [G][Cig/32 up][K taps ordered by (k mod s, k div s)][Cog/2][64]: lane -> w[co 2q + lane>>5, row lane&31, tap]
- * rows past Cog (Cig) are zero. */
+ * rows past Cog (Cig) are zero.
+ * MelGAN's discriminator (Kumar et al. 2019) has four input channels per group: (4,16,41,4) and (4,4,41,4) are
+ * instantiated too, behind the same entry points and with the same semantics, on VALU kernels that put 16 (Cog = 4) or
+ * 4 (Cog = 16) groups side by side in a workgroup and several in every wave (csrc/gconv_c4.h).  Their packs are plain
+ * transposes, G Cog 4 K floats in either mode:
+ *   MG_GCONV_FWD   [G][ci 4][K][Cog]: four consecutive output rows of one (ci, tap) are one 16-byte load
+ *   MG_GCONV_DGRAD [G][Cog][K][ci 4]: the four input channels of one (co, tap) are one 16-byte load */
 #define MG_GCONV_FWD 0
 #define MG_GCONV_DGRAD 1
 size_t mg_gconv_packed_floats(int Ci, int Co, int K, int stride, int groups, int mode);
@@ -997,6 +1010,17 @@ int mg_conv1d_c1_wgrad(const float *dy, const float *x, float *dw, float *db, fl
  * dx[r, m] = (dy[r, (m + 2) / 2] + dy[r, (m + 2) / 2 - 1]) / 4 over the outputs that exist. */
 int mg_avgpool4s2_fwd(const float *in, float *out, int rows, int L, void *stream);
 int mg_avgpool4s2_bwd(const float *dy, float *dx, int rows, int L, void *stream);
+/* MelGAN's pool, AvgPool1d(4, 2, padding 1, count_include_pad = False): in [rows, L] -> out [rows, (L - 2) / 2 + 1],
+ * out[r, i] = mean of in[r, 2 i - 1 .. 2 i + 2] over the samples in range (the edge windows divide by 3, or by 2 where
+ * L = 2), and its backward.  L < 2 is MG_ERR_SHAPE. */
+int mg_avgpool4s2p1_fwd(const float *in, float *out, int rows, int L, void *stream);
+int mg_avgpool4s2p1_bwd(const float *dy, float *dx, int rows, int L, void *stream);
+/* ReflectionPad1d(p) on rows of T samples: out [rows, T + 2 p], out[r, i] = in[r, reflect(i - p)], reflect(j) = -j below
+ * 0 and 2 (T - 1) - j past T - 1; and its backward dx [rows, T]: dx[r, m] = dy[r, m + p] plus the mirrored pad samples
+ * that read m (m in [1, p] from the left pad, m in [T - 1 - p, T - 2] from the right), added in that fixed order.
+ * p < 0 or T <= p is MG_ERR_SHAPE. */
+int mg_reflect_pad1d_fwd(const float *in, float *out, int rows, int T, int p, void *stream);
+int mg_reflect_pad1d_bwd(const float *dy, float *dx, int rows, int T, int p, void *stream);
 
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3

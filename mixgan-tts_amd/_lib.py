@@ -37,6 +37,7 @@ MG_PITCH_N, MG_PITCH_W, MG_PITCH_K, MG_PITCH_PARAMS = 1024, 512, 4, 7
 MG_ALIGN_MAX_D, MG_ALIGN_MAX_G, MG_ALIGN_MAX_S, MG_ALIGN_MAX_T = 128, 1024, 2048, 4096
 MG_CEPSTRA_MAX_M, MG_DTW_MAX_T, MG_DTW_MAX_D = 128, 4096, 64
 MG_GCONV_FWD, MG_GCONV_DGRAD = 0, 1                                               # mg_gconv_pack modes
+MG_LOSSMODE_MSE, MG_LOSSMODE_L1, MG_LOSSMODE_HINGE, MG_LOSSMODE_MEAN = range(4)    # MgLossTerm.mode
 
 
 class LossTerm(ctypes.Structure):
@@ -255,6 +256,10 @@ def _signatures():
         "mg_conv1d_c1_wgrad": (i, [vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]),
         "mg_avgpool4s2_fwd": (i, [vp, vp, i, i, vp]),
         "mg_avgpool4s2_bwd": (i, [vp, vp, i, i, vp]),
+        "mg_avgpool4s2p1_fwd": (i, [vp, vp, i, i, vp]),
+        "mg_avgpool4s2p1_bwd": (i, [vp, vp, i, i, vp]),
+        "mg_reflect_pad1d_fwd": (i, [vp, vp, i, i, i, vp]),
+        "mg_reflect_pad1d_bwd": (i, [vp, vp, i, i, i, vp]),
     }
 
 

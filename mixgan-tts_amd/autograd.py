@@ -687,3 +687,41 @@ class _AvgPool4s2Fn(torch.autograd.Function):
 
 def avgpool4s2(x):
     return _AvgPool4s2Fn.apply(x)
+
+
+# --------------------------------------------------------------------------------------------------
+# MelGAN's discriminator (melgan_discriminators.py): its pool and the reflection pad in front of layer 0.  The grouped
+# layers are scale_stack's, on the four-channel-group kernels of csrc/gconv_c4.h.
+# --------------------------------------------------------------------------------------------------
+class _AvgPool4s2p1Fn(torch.autograd.Function):
+    """AvgPool1d(4, 2, padding=1, count_include_pad=False)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_cuda(x)
+        ctx.Lin = x.shape[2]
+        return ops.avgpool4s2p1_fwd(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.avgpool4s2p1_bwd(g.contiguous(), ctx.Lin)
+
+
+def avgpool4s2p1(x):
+    return _AvgPool4s2p1Fn.apply(x)
+
+
+class _ReflectPad1dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p):
+        _require_cuda(x)
+        ctx.p = p
+        return ops.reflect_pad1d_fwd(x.contiguous(), p)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.reflect_pad1d_bwd(g.contiguous(), ctx.p), None
+
+
+def reflect_pad1d(x, p):
+    return _ReflectPad1dFn.apply(x, p)

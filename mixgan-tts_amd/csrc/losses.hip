@@ -216,6 +216,10 @@ __global__ __launch_bounds__(256) void multi_loss_fwd_kernel(MultiLossArgs a)
     const int nb = a.first_block[k + 1] - a.first_block[k], lb = blockIdx.x - a.first_block[k];
     float s = 0.f;
     for (size_t i = (size_t)lb * 256 + threadIdx.x; i < t.n; i += (size_t)nb * 256) {
+        if (t.mode >= MG_LOSSMODE_HINGE) {
+            s += t.mode == MG_LOSSMODE_HINGE ? fmaxf(0.f, fmaf(t.c, t.a[i], 1.f)) : t.a[i];
+            continue;
+        }
         const float d = t.mode == 0 ? t.a[i] - t.c : t.a[i] - t.b[i];
         s += t.mode == 0 ? d * d : fabsf(d);
     }
@@ -268,6 +272,10 @@ __global__ __launch_bounds__(256) void multi_loss_bwd_kernel(MultiLossArgs a)
     const int nb = a.first_block[k + 1] - a.first_block[k], lb = blockIdx.x - a.first_block[k];
     const float kk = a.g[0] * t.weight / a.div[k];
     for (size_t i = (size_t)lb * 256 + threadIdx.x; i < t.n; i += (size_t)nb * 256) {
+        if (t.mode >= MG_LOSSMODE_HINGE) {
+            t.da[i] = t.mode == MG_LOSSMODE_MEAN ? kk : (fmaf(t.c, t.a[i], 1.f) > 0.f ? kk * t.c : 0.f);
+            continue;
+        }
         const float d = t.mode == 0 ? t.a[i] - t.c : t.a[i] - t.b[i];
         t.da[i] = t.mode == 0 ? 2.f * kk * d : (d > 0.f ? kk : (d < 0.f ? -kk : 0.f));
     }
@@ -284,8 +292,8 @@ static int multi_loss_fill(MultiLossArgs &a, const MgLossTerm *terms, int nterms
     int at = 0;
     for (int k = 0; k < nterms; ++k) {
         const MgLossTerm &t = terms[k];
-        if (!t.a || (t.mode == 1 && !t.b) || t.mode < 0 || t.mode > 1 || t.group < 0 || t.group >= MG_LOSS_GROUPS)
-            return MG_ERR_ARG;
+        if (t.mode < MG_LOSSMODE_MSE || t.mode > MG_LOSSMODE_MEAN) return MG_ERR_SHAPE;
+        if (!t.a || (t.mode == 1 && !t.b) || t.group < 0 || t.group >= MG_LOSS_GROUPS) return MG_ERR_ARG;
         if (t.n == 0) return MG_ERR_SHAPE;
         a.t[k] = t;
         a.div[k] = den ? (float)den[k] : (float)t.n;

@@ -7,10 +7,12 @@
 // columns) on the B / C columns, so that a wave's 32 lanes read 32 consecutive floats of LDS and store 128 contiguous
 // bytes.
 #include "common.h"
+#include "gconv_c4.h"
 
 namespace {
 
 constexpr int GC_K = 41;
+static_assert(GC_K == C4_K, "one kernel size for every grouped form");
 
 __device__ __forceinline__ int gc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
@@ -441,8 +443,109 @@ __global__ void avgpool_bwd_kernel(const float *__restrict__ dy, float *__restri
 
 int blocks_for(long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
 
-// ---- which (Cig, Cog, K, s) exist: one list for the size queries, the checks and the launchers
-#define GC_FORMS(X) X(32, 32, 2) X(8, 16, 2) X(16, 32, 4) X(32, 64, 4) X(64, 64, 1)
+// ---------------------------------------------------------------------------------------------------------------
+// AvgPool1d(4, 2, padding 1), padding not counted (MelGAN): window i = samples 2 i - 1 .. 2 i + 2 within [0, L)
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float pool_p1_rcp(int i, int L)
+{
+    const int lo = 2 * i - 1 < 0 ? 0 : 2 * i - 1, hi = 2 * i + 2 > L - 1 ? L - 1 : 2 * i + 2;
+    return 1.f / (float)(hi - lo + 1);
+}
+
+__global__ void avgpool_p1_fwd_kernel(const float *__restrict__ in, float *__restrict__ out, long rows, int L, int Lout)
+{
+    const long total = rows * Lout;
+    for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
+        const long rrow = e / Lout;
+        const int i = e % Lout;
+        const float *src = in + rrow * L;
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int p = 2 * i - 1 + t;
+            if (p >= 0 && p < L) s += src[p];
+        }
+        out[e] = s * pool_p1_rcp(i, L);
+    }
+}
+
+__global__ void avgpool_p1_bwd_kernel(const float *__restrict__ dy, float *__restrict__ dx, long rows, int L, int Lout)
+{
+    const long total = rows * L;
+    for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
+        const long rrow = e / L;
+        const int m = e % L, i = (m + 1) / 2;      // windows i - 1 and i hold sample m
+        const float *src = dy + rrow * Lout;
+        float s = 0.f;
+        if (i >= 1 && i - 1 < Lout) s += src[i - 1] * pool_p1_rcp(i - 1, L);
+        if (i < Lout) s += src[i] * pool_p1_rcp(i, L);
+        dx[e] = s;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// ReflectionPad1d(p) and its fold-back
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void reflect_pad_fwd_kernel(const float *__restrict__ in, float *__restrict__ out, long rows, int T, int p)
+{
+    const int Tp = T + 2 * p;
+    const long total = rows * Tp;
+    for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
+        const long rrow = e / Tp;
+        int j = (int)(e % Tp) - p;
+        j = j < 0 ? -j : (j >= T ? 2 * (T - 1) - j : j);
+        out[e] = in[rrow * T + j];
+    }
+}
+
+__global__ void reflect_pad_bwd_kernel(const float *__restrict__ dy, float *__restrict__ dx, long rows, int T, int p)
+{
+    const int Tp = T + 2 * p;
+    const long total = rows * T;
+    for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
+        const long rrow = e / T;
+        const int m = e % T;
+        const float *src = dy + rrow * Tp;
+        float s = src[m + p];
+        if (m >= 1 && m <= p) s += src[p - m];
+        if (m >= T - 1 - p && m <= T - 2) s += src[p + 2 * (T - 1) - m];
+        dx[e] = s;
+    }
+}
+
+// ---- which (Cig, Cog, K, s) exist: one list for the size queries, the checks and the launchers.  Cig = 4 forms run the
+// kernels of gconv_c4.h, the others the MFMA kernels above.
+#define GC_FORMS(X) X(32, 32, 2) X(8, 16, 2) X(16, 32, 4) X(32, 64, 4) X(64, 64, 1) X(4, 16, 4) X(4, 4, 4)
+
+template <int CIG, int COG, int S>
+void gc_launch_fwd(hipStream_t st, const float *in, const float *packed, const float *bias, float *out, int N, int Ci,
+                   int Lin, int Co, int Lout, int pad, int groups, int act, float slope)
+{
+    if constexpr (CIG == C4_CIG) {
+        static_assert(S == C4_S, "");
+        hipLaunchKernelGGL((c4_fwd_kernel<COG>), dim3(mg_cdiv(Lout, C4F_NT), mg_cdiv(groups, c4_gpb<COG>()), N), dim3(256),
+                           0, st, in, packed, bias, out, Ci, Lin, Co, Lout, pad, groups, act, slope);
+    } else {
+        hipLaunchKernelGGL((gc_fwd_kernel<CIG, COG, S>), dim3(mg_cdiv(Lout, gc_fwd_nt<CIG, S>()), groups, N), dim3(256), 0,
+                           st, in, packed, bias, out, Ci, Lin, Co, Lout, pad, act, slope);
+    }
+}
+
+template <int CIG, int COG, int S>
+void gc_launch_dgrad(hipStream_t st, const float *dy, const float *packed, const float *map, const float *add, float *dx,
+                     int N, int Ci, int Lin, int Co, int Lout, int pad, int groups, float slope)
+{
+    // m + pad = s u + f for m in [0, Lin): u up to (Lin - 1 + pad) / s
+    const int umax = (int)(((long)Lin - 1 + pad) / S);
+    if constexpr (CIG == C4_CIG) {
+        hipLaunchKernelGGL((c4_dgrad_kernel<COG>), dim3(umax / c4d_nu<COG>() + 1, mg_cdiv(groups, c4_gpb<COG>()), N),
+                           dim3(256), 0, st, dy, packed, map, add, dx, Ci, Lin, Co, Lout, pad, groups, slope);
+    } else {
+        // a workgroup takes 128 / s values of u
+        hipLaunchKernelGGL((gc_dgrad_kernel<CIG, COG, S>), dim3(umax / (128 / S) + 1, groups, N), dim3(256), 0, st, dy,
+                           packed, map, add, dx, Ci, Lin, Co, Lout, pad, slope);
+    }
+}
 
 bool gc_form_ok(int Cig, int Cog, int K, int s)
 {
@@ -468,12 +571,26 @@ int gc_check(int N, int Ci, int Lin, int Co, int Lout, int K, int s, int pad, in
 int gw_colchunks(int Cig) { return mg_cdiv(mg_cdiv(Cig * GC_K, 32), GW_CBW); }
 
 // splits of the (n, 64-frame chunk) range of the weight gradient: about 1024 workgroups, at most 64 partial copies
-int gw_nsplit(int N, int Lout, int Cig, int G)
+int gw_nsplit(int N, int Lout, int Cig, int Cog, int G)
 {
+    if (Cig == C4_CIG) return c4w_nsplit(N, Lout, Cog, G);
     const long chunks = (long)N * mg_cdiv(Lout, GW_LT);
     long n = 1024 / ((long)G * gw_colchunks(Cig));
     n = n < 1 ? 1 : n > 64 ? 64 : n;
     return (int)(n > chunks ? chunks : n);
+}
+
+template <int CIG, int COG, int S>
+void gc_launch_wgrad(hipStream_t st, const float *dy, const float *x, float *scratch, int N, int Ci, int Lin, int Co,
+                     int Lout, int pad, int groups, int nsplit)
+{
+    if constexpr (CIG == C4_CIG) {
+        hipLaunchKernelGGL((c4_wgrad_kernel<COG>), dim3(mg_cdiv(groups, c4_gpb<COG>()), nsplit), dim3(256), 0, st, dy, x,
+                           scratch, N, Ci, Lin, Co, Lout, pad, groups, mg_cdiv(N * mg_cdiv(Lout, C4W_LT), nsplit));
+    } else {
+        hipLaunchKernelGGL((gc_wgrad_kernel<CIG, COG, S>), dim3(gw_colchunks(CIG), groups, nsplit), dim3(256), 0, st, dy, x,
+                           scratch, N, Ci, Lin, Co, Lout, pad, mg_cdiv(N * mg_cdiv(Lout, GW_LT), nsplit));
+    }
 }
 
 int c1_nsplit(int N, int Lout)
@@ -489,6 +606,7 @@ extern "C" size_t mg_gconv_packed_floats(int Ci, int Co, int K, int stride, int 
     if (groups <= 0 || Ci <= 0 || Co <= 0 || Ci % groups || Co % groups) return 0;
     const int Cig = Ci / groups, Cog = Co / groups;
     if (!gc_form_ok(Cig, Cog, K, stride)) return 0;
+    if (Cig == C4_CIG) return mode == MG_GCONV_FWD || mode == MG_GCONV_DGRAD ? (size_t)Co * Cig * GC_K : 0;
     if (mode == MG_GCONV_FWD) return (size_t)groups * mg_cdiv(Cog, 32) * GC_K * (Cig / 2) * 64;
     if (mode == MG_GCONV_DGRAD) return (size_t)groups * mg_cdiv(Cig, 32) * GC_K * (Cog / 2) * 64;
     return 0;
@@ -502,7 +620,10 @@ extern "C" int mg_gconv_pack(const float *w, float *packed, int Ci, int Co, int 
     const size_t n = mg_gconv_packed_floats(Ci, Co, K, stride, groups, mode);
     if (!n) return MG_ERR_SHAPE;
     const int Cig = Ci / groups, Cog = Co / groups;
-    if (mode == MG_GCONV_FWD)
+    if (Cig == C4_CIG)
+        hipLaunchKernelGGL(c4_pack_kernel, dim3(blocks_for((long)n)), dim3(256), 0, (hipStream_t)stream, w, packed, Cog,
+                           groups, mode);
+    else if (mode == MG_GCONV_FWD)
         hipLaunchKernelGGL(gc_pack_fwd_kernel, dim3(blocks_for((long)n)), dim3(256), 0, (hipStream_t)stream, w, packed, Cig,
                            Cog, groups);
     else
@@ -520,10 +641,9 @@ extern "C" int mg_gconv1d_fwd(const float *in, const float *packed, const float 
     MG_TRY(gc_check(N, Ci, Lin, Co, Lout, K, stride, pad, groups));
     const int Cig = Ci / groups, Cog = Co / groups;
     hipStream_t st = (hipStream_t)stream;
-#define X(a, b, c)                                                                                                        \
-    if (Cig == a && Cog == b && stride == c)                                                                              \
-        hipLaunchKernelGGL((gc_fwd_kernel<a, b, c>), dim3(mg_cdiv(Lout, gc_fwd_nt<a, c>()), groups, N), dim3(256), 0, st, \
-                           in, packed, bias, out, Ci, Lin, Co, Lout, pad, act, slope);
+#define X(a, b, c)                           \
+    if (Cig == a && Cog == b && stride == c) \
+        gc_launch_fwd<a, b, c>(st, in, packed, bias, out, N, Ci, Lin, Co, Lout, pad, groups, act, slope);
     GC_FORMS(X)
 #undef X
     MG_LAUNCH_CHECK();
@@ -537,13 +657,10 @@ extern "C" int mg_gconv1d_dgrad(const float *dy, const float *packed, const floa
     if (!dy || !packed || !dx) return MG_ERR_ARG;
     MG_TRY(gc_check(N, Ci, Lin, Co, Lout, K, stride, pad, groups));
     const int Cig = Ci / groups, Cog = Co / groups;
-    // m + pad = s u + f for m in [0, Lin): u up to (Lin - 1 + pad) / s; a workgroup takes 128 / s values of u
-    const int tiles = (int)(((long)Lin - 1 + pad) / stride / (128 / stride) + 1);
     hipStream_t st = (hipStream_t)stream;
-#define X(a, b, c)                                                                                                     \
-    if (Cig == a && Cog == b && stride == c)                                                                           \
-        hipLaunchKernelGGL((gc_dgrad_kernel<a, b, c>), dim3(tiles, groups, N), dim3(256), 0, st, dy, packed, map, add, \
-                           dx, Ci, Lin, Co, Lout, pad, slope);
+#define X(a, b, c)                           \
+    if (Cig == a && Cog == b && stride == c) \
+        gc_launch_dgrad<a, b, c>(st, dy, packed, map, add, dx, N, Ci, Lin, Co, Lout, pad, groups, slope);
     GC_FORMS(X)
 #undef X
     MG_LAUNCH_CHECK();
@@ -554,7 +671,7 @@ extern "C" size_t mg_gconv1d_wgrad_scratch_floats(int N, int Ci, int Co, int Lou
 {
     if (N <= 0 || Lout <= 0 || groups <= 0 || Ci <= 0 || Co <= 0 || Ci % groups || Co % groups) return 0;
     if (!gc_form_ok(Ci / groups, Co / groups, K, stride)) return 0;
-    return (size_t)gw_nsplit(N, Lout, Ci / groups, groups) * Co * (Ci / groups) * GC_K;
+    return (size_t)gw_nsplit(N, Lout, Ci / groups, Co / groups, groups) * Co * (Ci / groups) * GC_K;
 }
 
 extern "C" int mg_gconv1d_wgrad(const float *dy, const float *x, float *dw, float *scratch, size_t scratch_floats, int N,
@@ -563,15 +680,13 @@ extern "C" int mg_gconv1d_wgrad(const float *dy, const float *x, float *dw, floa
     if (!dy || !x || !dw || !scratch) return MG_ERR_ARG;
     MG_TRY(gc_check(N, Ci, Lin, Co, Lout, K, stride, pad, groups));
     const int Cig = Ci / groups, Cog = Co / groups;
-    const int nsplit = gw_nsplit(N, Lout, Cig, groups);
+    const int nsplit = gw_nsplit(N, Lout, Cig, Cog, groups);
     const long nw = (long)Co * Cig * GC_K;
     if (scratch_floats < (size_t)nsplit * nw) return MG_ERR_WORKSPACE;
-    const int cps = mg_cdiv(N * mg_cdiv(Lout, GW_LT), nsplit);
     hipStream_t st = (hipStream_t)stream;
-#define X(a, b, c)                                                                                                       \
-    if (Cig == a && Cog == b && stride == c)                                                                             \
-        hipLaunchKernelGGL((gc_wgrad_kernel<a, b, c>), dim3(gw_colchunks(a), groups, nsplit), dim3(256), 0, st, dy, x,   \
-                           scratch, N, Ci, Lin, Co, Lout, pad, cps);
+#define X(a, b, c)                           \
+    if (Cig == a && Cog == b && stride == c) \
+        gc_launch_wgrad<a, b, c>(st, dy, x, scratch, N, Ci, Lin, Co, Lout, pad, groups, nsplit);
     GC_FORMS(X)
 #undef X
     MG_LAUNCH_CHECK();
@@ -653,6 +768,47 @@ extern "C" int mg_avgpool4s2_bwd(const float *dy, float *dx, int rows, int L, vo
     if (rows <= 0 || L <= 0) return MG_ERR_SHAPE;
     hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(blocks_for((long)rows * L)), dim3(256), 0, (hipStream_t)stream, dy, dx,
                        (long)rows, L, L / 2 + 1);
+    MG_LAUNCH_CHECK();
+    return MG_OK;
+}
+
+extern "C" int mg_avgpool4s2p1_fwd(const float *in, float *out, int rows, int L, void *stream)
+{
+    if (!in || !out) return MG_ERR_ARG;
+    if (rows <= 0 || L < 2) return MG_ERR_SHAPE;
+    const int Lout = (L - 2) / 2 + 1;
+    hipLaunchKernelGGL(avgpool_p1_fwd_kernel, dim3(blocks_for((long)rows * Lout)), dim3(256), 0, (hipStream_t)stream, in,
+                       out, (long)rows, L, Lout);
+    MG_LAUNCH_CHECK();
+    return MG_OK;
+}
+
+extern "C" int mg_avgpool4s2p1_bwd(const float *dy, float *dx, int rows, int L, void *stream)
+{
+    if (!dy || !dx) return MG_ERR_ARG;
+    if (rows <= 0 || L < 2) return MG_ERR_SHAPE;
+    hipLaunchKernelGGL(avgpool_p1_bwd_kernel, dim3(blocks_for((long)rows * L)), dim3(256), 0, (hipStream_t)stream, dy, dx,
+                       (long)rows, L, (L - 2) / 2 + 1);
+    MG_LAUNCH_CHECK();
+    return MG_OK;
+}
+
+extern "C" int mg_reflect_pad1d_fwd(const float *in, float *out, int rows, int T, int p, void *stream)
+{
+    if (!in || !out) return MG_ERR_ARG;
+    if (rows <= 0 || p < 0 || T <= p || (long)T + 2l * p >= (1l << 30)) return MG_ERR_SHAPE;
+    hipLaunchKernelGGL(reflect_pad_fwd_kernel, dim3(blocks_for((long)rows * (T + 2 * p))), dim3(256), 0,
+                       (hipStream_t)stream, in, out, (long)rows, T, p);
+    MG_LAUNCH_CHECK();
+    return MG_OK;
+}
+
+extern "C" int mg_reflect_pad1d_bwd(const float *dy, float *dx, int rows, int T, int p, void *stream)
+{
+    if (!dy || !dx) return MG_ERR_ARG;
+    if (rows <= 0 || p < 0 || T <= p || (long)T + 2l * p >= (1l << 30)) return MG_ERR_SHAPE;
+    hipLaunchKernelGGL(reflect_pad_bwd_kernel, dim3(blocks_for((long)rows * T)), dim3(256), 0, (hipStream_t)stream, dy, dx,
+                       (long)rows, T, p);
     MG_LAUNCH_CHECK();
     return MG_OK;
 }

@@ -67,7 +67,7 @@ def _multi_scratch(dev):
 class _WeightedMeansFn(torch.autograd.Function):
     """total = sum_k weight_k * mean_k in ONE launch (mg_multi_loss_fwd), gradients of all terms in one more.
     spec: tuple of (mode, c, weight, group) per term, mode 0 = mean (x - c)^2, mode 1 = mean |x - y| with gradient
-    to x only; tensors: the x of every term, then the y of the mode-1 terms in order.
+    to x only, mode 2 = mean max(0, 1 + c x), mode 3 = mean x; tensors: the x of every term, then the y of the mode-1 terms in order.
     Returns the [1 + groups + nterms] result vector (total, group subtotals, per-term means); differentiate [0]."""
 
     @staticmethod
@@ -111,7 +111,8 @@ class _WeightedMeansFn(torch.autograd.Function):
 
 
 def weighted_means(terms):
-    """terms: list of ("mse", x, c, weight[, group]) / ("l1", x, y, weight[, group]).  Returns the result vector of
+    """terms: list of ("mse", x, c, weight[, group]) / ("l1", x, y, weight[, group]) / ("hinge", x, sign, weight[, group])
+    = weight * mean(max(0, 1 + sign * x)) / ("mean", x, None, weight[, group]).  Returns the result vector of
     _WeightedMeansFn: [0] total (differentiable w.r.t. every x), [1:1+4] group subtotals, then per-term means."""
     spec, xs, ys = [], [], []
     for t in terms:
@@ -122,6 +123,10 @@ def weighted_means(terms):
         elif kind == "l1":
             spec.append((1, 0.0, float(w), grp))
             ys.append(other)
+        elif kind == "hinge":
+            spec.append((_lib.MG_LOSSMODE_HINGE, float(other), float(w), grp))
+        elif kind == "mean":
+            spec.append((_lib.MG_LOSSMODE_MEAN, 0.0, float(w), grp))
         else:
             raise ValueError(kind)
         xs.append(x)
@@ -167,6 +172,41 @@ def hifigan_feature_loss(fmap_r, fmap_g):
     terms = [("l1", g, r, 2.0) for dr, dg in zip(fmap_r, fmap_g) for r, g in zip(dr, dg)]
     if not terms:
         raise ValueError("no feature maps")
+    return _means_in_calls(terms)[0]
+
+
+# --------------------------------------------------------------------------------------------------
+# MelGAN's objective (Kumar et al. 2019, scripts/train.py) over melgan_discriminators.Discriminator's outputs: one list of
+# maps per scale, the last map the raw logits.
+# --------------------------------------------------------------------------------------------------
+def melgan_discriminator_loss(D_real, D_fake):
+    """sum over the scales of mean(relu(1 - real[-1])) + mean(relu(1 + fake[-1]))."""
+    if len(D_real) != len(D_fake) or not D_real:
+        raise ValueError("one real and one generated list of maps per scale")
+    terms = []
+    for r, f in zip(D_real, D_fake):
+        terms += [("hinge", r[-1], -1.0, 1.0), ("hinge", f[-1], 1.0, 1.0)]
+    return _means_in_calls(terms)[0]
+
+
+def melgan_generator_loss(D_fake):
+    """sum over the scales of -mean(fake[-1])."""
+    if not D_fake:
+        raise ValueError("no discriminator outputs")
+    return _means_in_calls([("mean", f[-1], None, -1.0) for f in D_fake])[0]
+
+
+def melgan_feature_loss(D_real, D_fake):
+    """sum over the scales and over every map but the last of wt * mean|fake - real.detach()|,
+    wt = (1 / num_D) * 4 / (n_layers + 1), n_layers + 3 maps per scale."""
+    if len(D_real) != len(D_fake) or not D_real:
+        raise ValueError("one real and one generated list of maps per scale")
+    terms = []
+    for r, f in zip(D_real, D_fake):
+        if len(r) != len(f) or len(f) < 4:
+            raise ValueError("a scale returns n_layers + 3 maps")
+        wt = (1.0 / len(D_fake)) * 4.0 / (len(f) - 2)
+        terms += [("l1", fm, rm, wt) for rm, fm in zip(r[:-1], f[:-1])]
     return _means_in_calls(terms)[0]
 
 

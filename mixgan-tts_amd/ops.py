@@ -700,3 +700,35 @@ def avgpool4s2_bwd(dy, Lin):
     dx = torch.empty(N, C, Lin, device=dy.device, dtype=torch.float32)
     check(_lib.lib().mg_avgpool4s2_bwd(fptr(dy), fptr(dx), N * C, Lin, stream_ptr()))
     return dx
+
+
+# ---- MelGAN's discriminator (csrc/msd.hip): the uncounted-padding pool and the reflection pad in front of layer 0
+def avgpool4s2p1_fwd(x):
+    """AvgPool1d(4, 2, padding=1, count_include_pad=False) of x [N, C, L] -> [N, C, (L - 2) / 2 + 1]."""
+    N, C, Lin = x.shape
+    out = torch.empty(N, C, max((Lin - 2) // 2 + 1, 0), device=x.device, dtype=torch.float32)
+    check(_lib.lib().mg_avgpool4s2p1_fwd(fptr(x), fptr(out), N * C, Lin, stream_ptr()))
+    return out
+
+
+def avgpool4s2p1_bwd(dy, Lin):
+    N, C, _ = dy.shape
+    dx = torch.empty(N, C, Lin, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().mg_avgpool4s2p1_bwd(fptr(dy), fptr(dx), N * C, Lin, stream_ptr()))
+    return dx
+
+
+def reflect_pad1d_fwd(x, p):
+    """ReflectionPad1d(p) of x [N, C, T] -> [N, C, T + 2 p]."""
+    N, C, T = x.shape
+    out = torch.empty(N, C, T + 2 * p, device=x.device, dtype=torch.float32)
+    check(_lib.lib().mg_reflect_pad1d_fwd(fptr(x), fptr(out), N * C, T, p, stream_ptr()))
+    return out
+
+
+def reflect_pad1d_bwd(dy, p):
+    """The fold-back: dy [N, C, T + 2 p] -> [N, C, T], the mirrored pad samples added into the positions they read."""
+    N, C, Tp = dy.shape
+    dx = torch.empty(N, C, max(Tp - 2 * p, 0), device=dy.device, dtype=torch.float32)
+    check(_lib.lib().mg_reflect_pad1d_bwd(fptr(dy), fptr(dx), N * C, Tp - 2 * p, p, stream_ptr()))
+    return dx

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .losses import hifigan_discriminator_loss, hifigan_generator_loss, hifigan_feature_loss
+from .losses import melgan_discriminator_loss, melgan_generator_loss, melgan_feature_loss
 
 
 def sample_segments(mels, wavs, mel_lens, frames=32, generator=None, hop=256):
@@ -132,10 +133,20 @@ class VocoderGANTrainer:
     maps -- as the published MultiPeriodDiscriminator / MultiScaleDiscriminator do.  Defaults as GeneratorTrainer: two
     AdamW optimizers (2e-4, betas 0.8 / 0.99), two ExponentialLR(0.999) schedulers stepped by end_epoch(),
     lambda_mel = 45.
-    optimizer: None -> torch.optim.AdamW; a class is built as optimizer(params, lr=lr) for each side."""
+    optimizer: None -> torch.optim.AdamW; a class is built as optimizer(params, lr=lr) for each side.
+
+    objective="melgan" is MelGAN's step (Kumar et al. 2019, scripts/train.py) in the same frame: a discriminator is a
+    melgan_discriminators.Discriminator, called as forward_pair(y, y_hat) -> (D_real, D_fake), one list of maps per
+    scale; the D phase is the hinge loss, the G phase adv + lambda_feat * fm + lambda_mel * mel_l1 with the hinge
+    generator term and the weighted feature matching of losses.melgan_*.  lambda_mel = 0 (upstream has no mel term)
+    skips the mel term's computation; "mel_l1" is then a zero.  taps "d" / "g" hold (D_real, D_fake)."""
 
     def __init__(self, generator, stft, discriminators, optimizer=None, lr=2e-4, betas=(0.8, 0.99), lr_decay=0.999,
-                 lambda_mel=45.0):
+                 lambda_mel=45.0, objective="hifigan", lambda_feat=10.0):
+        if objective not in ("hifigan", "melgan"):
+            raise ValueError("objective: 'hifigan' or 'melgan', got %r" % (objective,))
+        self.objective = objective
+        self.lambda_feat = float(lambda_feat)
         if not discriminators:
             raise ValueError("VocoderGANTrainer needs at least one discriminator")
         for name in discriminators:
@@ -169,6 +180,8 @@ class VocoderGANTrainer:
         y_hat = self.generator.forward_train(mel, None if taps is None else taps["generator"])
         if y_hat.shape != y.shape:
             raise ValueError("wav must be %s, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
+        if self.objective == "melgan":
+            return self._step_melgan(y, y_hat, taps)
 
         self.optim_d.zero_grad(set_to_none=True)
         y_hat_d = y_hat.detach()
@@ -202,6 +215,44 @@ class VocoderGANTrainer:
         self.optim_g.step()
         self.steps += 1
         return {"loss_d": loss_d.detach(), "loss_g": loss_g.detach(), "mel_l1": mel_l1.detach(), "adv": adv.detach(),
+                "fm": fm.detach()}
+
+    def _step_melgan(self, y, y_hat, taps):
+        self.optim_d.zero_grad(set_to_none=True)
+        y_hat_d = y_hat.detach()
+        loss_d = None
+        for name, d in self.discriminators.items():
+            D_real, D_fake = d.forward_pair(y, y_hat_d)
+            if taps is not None:
+                taps["d"][name] = (D_real, D_fake)
+            part = melgan_discriminator_loss(D_real, D_fake)
+            loss_d = part if loss_d is None else loss_d + part
+        loss_d.backward()
+        self.optim_d.step()
+
+        self.optim_g.zero_grad(set_to_none=True)
+        mel_l1 = _mel_l1(self.stft, y_hat.squeeze(1), y.squeeze(1)) if self.lambda_mel != 0.0 else None
+        for p in self._d_params:
+            p.requires_grad_(False)
+        try:
+            adv = fm = None
+            for name, d in self.discriminators.items():
+                D_real, D_fake = d.forward_pair(y, y_hat)
+                if taps is not None:
+                    taps["g"][name] = (D_real, D_fake)
+                a, f = melgan_generator_loss(D_fake), melgan_feature_loss(D_real, D_fake)
+                adv, fm = (a, f) if adv is None else (adv + a, fm + f)
+            loss_g = adv + self.lambda_feat * fm
+            if mel_l1 is not None:
+                loss_g = loss_g + self.lambda_mel * mel_l1
+            loss_g.backward()
+        finally:
+            for p in self._d_params:
+                p.requires_grad_(True)
+        self.optim_g.step()
+        self.steps += 1
+        mel_l1 = torch.zeros_like(loss_g.detach()) if mel_l1 is None else mel_l1.detach()
+        return {"loss_d": loss_d.detach(), "loss_g": loss_g.detach(), "mel_l1": mel_l1, "adv": adv.detach(),
                 "fm": fm.detach()}
 
     def end_epoch(self):
