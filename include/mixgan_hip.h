@@ -156,7 +156,8 @@ int mg_conv1d_fwd_plan(int B, int Ci, int Lout, int rows, int K, int stride, int
 /* diffuse_fn + q_sample (model/diffusion.py:177-185, 147-153), fused with norm_spec (:228),
  * the [B,L,M] -> [B,1,M,L] transpose and the mask multiply of :206-207.
  *   mel [B, L, M]; t int64 [B] (t<0 rows return the clean normalised mel); noise [B, M, L];
- *   keep uint8 [B, L] (1 = valid frame) or NULL; out [B, M, L].                                   */
+ *   keep uint8 [B, L] (1 = valid frame) or NULL; out [B, M, L].
+ * M <= mg_transpose_max_m() (below), MG_ERR_SHAPE beyond it.                                      */
 int mg_diffuse_fwd(const float *mel, const int64_t *t, const float *noise, const uint8_t *keep,
                    const float *spec_min, const float *spec_max, const float *sqrt_ac,
                    const float *sqrt_1mac, float *out, int B, int L, int M, int T, void *stream);
@@ -192,6 +193,10 @@ int mg_transpose_bml(const float *in, float *out, const float *spec_min, const f
 int mg_transpose_bml_strided(const float *in, float *out, const float *spec_min, const float *spec_max,
                              const uint8_t *keep, int to_blm, int mode, int B, int L, int M, long bml_bs,
                              void *stream);
+/* Largest M of the two transposes and of mg_diffuse_fwd on the current device: they stage a [64][M + 1] float tile
+ * in dynamic LDS, so M <= (dynamic LDS a workgroup of these kernels can get) / 256 - 1, and never above 1024.  639 on
+ * an MI355X (163,840 bytes).  A wider M is refused with MG_ERR_SHAPE before anything is launched.  0 without a device. */
+int mg_transpose_max_m(void);
 
 /* ------------------------------------------------------------------ Denoiser (model/modules.py:382-446)
  * The pointer table of mg_denoiser_pack (weights) and mg_denoiser_bwd (gradients): MG_DEN_HEAD_PTRS head slots, then
@@ -519,14 +524,17 @@ int mg_stft_mel_bwd(const float *x, long x_bs, const int *lengths, int B, int L,
                     float *dx, long dx_bs, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Step-embedding MLP: out = W2 mish(W0 [sin|cos](t * freq)).  Denoiser: model/modules.py:398-403,434;
- * JCUDiscriminator: model/mixgantts.py:203-208,265.  emb [B,D0], pre/h [B,D1] are saved for backward. */
+ * JCUDiscriminator: model/mixgantts.py:203-208,265.  emb [B,D0], pre/h [B,D1] are saved for backward.
+ * Where D0 % 256 == 0, W0 and emb must be 16-byte aligned, and where D1 % 256 == 0, W2 and h (those reductions run on
+ * 16-byte loads); MG_ERR_ARG otherwise. */
 int mg_step_mlp_fwd(const int64_t *t, const float *freq, const float *W0, const float *W2, float *emb,
                     float *pre, float *h, float *out, int B, int D0, int D1, int D2, void *stream);
 /* g_out [B,D2] -> dW0 [D1,D0], dW2 [D2,D1]; scratch 2*B*D1 floats. */
 int mg_step_mlp_bwd(const float *g_out, const float *emb, const float *pre, const float *h,
                     const float *W2, float *dW0, float *dW2, float *scratch, int B, int D0, int D1, int D2,
                     void *stream);
-/* Bias-free per-sample Linear (LinearNorm on [B,K] vectors: speaker projections, spk_mlp). */
+/* Bias-free per-sample Linear (LinearNorm on [B,K] vectors: speaker projections, spk_mlp).  Where K % 256 == 0 the
+ * forward reads x and W with 16-byte loads: both must be 16-byte aligned then, MG_ERR_ARG otherwise. */
 int mg_linear_small_fwd(const float *x, const float *W, float *out, int B, int N, int K, void *stream);
 int mg_linear_small_bwd(const float *g, const float *x, const float *W, float *dx, float *dW, int B,
                         int N, int K, void *stream);

@@ -145,6 +145,7 @@ def _signatures():
         "mg_denoiser_fwd_pair": (i, [dp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, i, i, vp]),
         "mg_denoiser_fwd_plan": (i, [dp, i, i, i, i, i, ctypes.POINTER(FwdPlan)]),
         "mg_transpose_bml_strided": (i, [vp] * 5 + [i, i, i, i, i, lg, vp]),
+        "mg_transpose_max_m": (i, []),
         "mg_act_bwd": (i, [vp, vp, vp, i, sz, vp]),
         "mg_upsample_zero": (i, [vp, vp, i, i, i, i, vp]),
         "mg_step_mlp_fwd": (i, [vp] * 8 + [i, i, i, i, vp]),

@@ -2,8 +2,11 @@
 // One pass over each tensor, 16-byte accesses where the row pitch allows, LDS-tiled transposes so
 // that both the [B,L,M] side and the [B,M,L] side are read/written in full 256-byte segments.
 #include "common.h"
+#include <atomic>
 
 #define TL 64  // frames per transpose tile
+
+static int lds_tile_max_m();  // widest M of the LDS-tiled kernels on the current device (below the transposes)
 
 // norm_spec, exactly the reference's op order (model/diffusion.py:228-229)
 __device__ __forceinline__ float norm1(float x, float mn, float mx) { return (x - mn) / (mx - mn) * 2.f - 1.f; }
@@ -79,7 +82,7 @@ extern "C" int mg_diffuse_fwd(const float *mel, const int64_t *t, const float *n
                               const float *sqrt_1mac, float *out, int B, int L, int M, int T, void *stream)
 {
     if (!mel || !t || !noise || !spec_min || !spec_max || !sqrt_ac || !sqrt_1mac || !out) return MG_ERR_ARG;
-    if (B <= 0 || L <= 0 || M <= 0 || M > 1024 || T <= 0) return MG_ERR_SHAPE;
+    if (B <= 0 || L <= 0 || M <= 0 || M > lds_tile_max_m() || T <= 0) return MG_ERR_SHAPE;
     dim3 grid(mg_cdiv(L, TL), B);
     const bool vec = M % 4 == 0 && L % 4 == 0 && ((((uintptr_t)mel | (uintptr_t)noise | (uintptr_t)out) & 15) == 0);
     if (vec)
@@ -272,6 +275,47 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float *__restrict_
     }
 }
 
+// The transposes and diffuse hold a [TL][M + 1] float tile in dynamic LDS, so the widest M they can launch follows from
+// the dynamic LDS a workgroup of these kernels can get on the current device: the smaller of what the runtime reports
+// for the kernels themselves (they have no static LDS and nothing raises their limit) and the device's per-workgroup
+// figure.  Asked once per device.  0 without a device.
+static int lds_tile_max_m()
+{
+    constexpr int MAXDEV = 64;
+    static std::atomic<int> cache[MAXDEV];   // 0 = not asked yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (dev >= 0 && dev < MAXDEV) {
+        const int c = cache[dev].load(std::memory_order_relaxed);
+        if (c) return c;
+    }
+    int bytes = 0;
+    if (hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || bytes <= 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const void *kernels[] = {(const void *)&diffuse_kernel<true>, (const void *)&diffuse_kernel<false>,
+                             (const void *)&transpose_kernel<true, TL>, (const void *)&transpose_kernel<false, TL>};
+    for (const void *k : kernels) {
+        hipFuncAttributes a;
+        if (hipFuncGetAttributes(&a, k) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
+        if (a.maxDynamicSharedSizeBytes > 0 && a.maxDynamicSharedSizeBytes < bytes) bytes = a.maxDynamicSharedSizeBytes;
+    }
+    int m = bytes / (int)(TL * sizeof(float)) - 1;
+    if (m > 1024) m = 1024;
+    if (m < 0) m = 0;
+    if (m > 0 && dev >= 0 && dev < MAXDEV) cache[dev].store(m, std::memory_order_relaxed);
+    return m;
+}
+
+extern "C" int mg_transpose_max_m(void) { return lds_tile_max_m(); }
+
 extern "C" int mg_transpose_bml_strided(const float *in, float *out, const float *spec_min, const float *spec_max,
                                         const uint8_t *keep, int to_blm, int mode, int B, int L, int M, long bml_bs,
                                         void *stream);
@@ -288,7 +332,7 @@ extern "C" int mg_transpose_bml_strided(const float *in, float *out, const float
 {
     if (!in || !out) return MG_ERR_ARG;
     if (mode < 0 || mode > 2 || (mode != 0 && (!spec_min || !spec_max))) return MG_ERR_ARG;
-    if (B <= 0 || L <= 0 || M <= 0 || M > 1024) return MG_ERR_SHAPE;
+    if (B <= 0 || L <= 0 || M <= 0 || M > lds_tile_max_m()) return MG_ERR_SHAPE;
     dim3 grid(mg_cdiv(L, TL), B);
     const long bs = bml_bs ? bml_bs : (long)M * L;
     const bool vec = M % 4 == 0 && L % 4 == 0 && bs % 4 == 0 && ((((uintptr_t)in | (uintptr_t)out) & 15) == 0);

@@ -64,6 +64,14 @@ extern "C" int mg_upsample_zero(const float *in, float *out, int rows, int Lin, 
     return mg_upsample_zero_act(in, out, rows, Lin, stride, Lup, 1.f, stream);
 }
 
+// small_linear_kernel reads W and its input with 16-byte loads whenever K % 256 == 0 and does not look at the pointers
+// (the denoiser hands it offsets that are aligned by construction); the entry points below take caller pointers, so
+// they hold them to that here.  Rows are K floats apart, so aligned bases make every row aligned.
+static inline bool linear_operands_aligned(const float *W, const float *in, int K)
+{
+    return (K & 255) != 0 || ((((uintptr_t)W | (uintptr_t)in) & 15) == 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // step MLP: out = W2 mish(W0 emb(t))        emb [B,D0], pre/h [B,D1], out [B,D2]
 // ---------------------------------------------------------------------------------------------
@@ -72,6 +80,7 @@ extern "C" int mg_step_mlp_fwd(const int64_t *t, const float *freq, const float 
 {
     if (!t || !freq || !W0 || !W2 || !emb || !pre || !h || !out) return MG_ERR_ARG;
     if (B <= 0 || D0 <= 0 || D0 % 2 || D1 <= 0 || D2 <= 0) return MG_ERR_SHAPE;
+    if (!linear_operands_aligned(W0, emb, D0) || !linear_operands_aligned(W2, h, D1)) return MG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(step_embed_kernel, dim3(mg_cdiv(B * (D0 / 2), 256)), dim3(256), 0, st, t, freq, emb, B, D0);
     MG_LAUNCH_CHECK();
@@ -121,6 +130,7 @@ extern "C" int mg_linear_small_fwd(const float *x, const float *W, float *out, i
 {
     if (!x || !W || !out) return MG_ERR_ARG;
     if (B <= 0 || N <= 0 || K <= 0) return MG_ERR_SHAPE;
+    if (!linear_operands_aligned(W, x, K)) return MG_ERR_ARG;
     return small_linear(W, 0, x, out, 0, nullptr, 0, nullptr, B, N, K, 1, 0, (hipStream_t)stream);
 }
 

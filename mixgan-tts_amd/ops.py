@@ -361,12 +361,24 @@ def split_transpose(g, M):
     return outs
 
 
+def transpose_max_m():
+    """Largest M of transpose_bml / cat_transpose / split_transpose / diffuse on the current device."""
+    return _lib.lib().mg_transpose_max_m()
+
+
+def _aligned16(t, K):
+    """t, or a fresh copy of it when the 16-byte loads of the small linears (K % 256 == 0) would read it misaligned:
+    a view that starts a few floats into its storage."""
+    return t.clone() if K % 256 == 0 and t.data_ptr() % 16 else t
+
+
 def step_mlp_fwd(t, freq, W0, W2):
     L = _lib.lib()
     B = t.shape[0]
     D1, D0 = W0.shape
     D2 = W2.shape[0]
     dev = W0.device
+    W0, W2 = _aligned16(W0, D0), _aligned16(W2, D1)
     emb, pre, h = (torch.empty(B, d, device=dev) for d in (D0, D1, D1))
     out = torch.empty(B, D2, device=dev)
     check(L.mg_step_mlp_fwd(iptr(t, torch.int64), fptr(freq), fptr(W0), fptr(W2), fptr(emb), fptr(pre), fptr(h),
@@ -391,6 +403,7 @@ def linear_small_fwd(x, W):
     B, K = x.shape
     N = W.shape[0]
     out = torch.empty(B, N, device=x.device)
+    x, W = _aligned16(x, K), _aligned16(W, K)
     check(L.mg_linear_small_fwd(fptr(x), fptr(W), fptr(out), B, N, K, stream_ptr()))
     return out
 

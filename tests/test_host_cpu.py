@@ -120,6 +120,24 @@ def test_error_strings_and_arg_checks():
     assert L.mg_conv1d_wgrad_scratch_floats(256, 80, 1) == 128 * 256 * 80                     # 2 tiles, 256-workgroup target
     assert L.mg_conv1d_wgrad_scratch_floats(512, 128, 5) == 25 * 512 * 128 * 5                # k=5: split kernel, 20 tiles
     assert L.mg_conv1d_wgrad_grouped(None, 0, 0, None, 0, 0, None, 0, None, 2, 1, 8, 8, 8, 8, 1, 1, 0, 1.0, 0, None) == _lib.MG_ERR_ARG
+    # the small diffusion, step-MLP, loss and index entry points: every one refuses null operands before it asks anything
+    # of a device (name -> the integer / float arguments after the pointers, all valid)
+    small = {"mg_transpose_bml": (0, 0, 1, 8, 4), "mg_transpose_bml_strided": (0, 0, 1, 8, 4, 0), "mg_diffuse_fwd": (1, 8, 4, 4),
+             "mg_posterior_sample_fwd": (1, 1, 8, 4, 4), "mg_posterior_sample_bwd": (1, 1, 8, 4, 4),
+             "mg_spec_affine": (1, 32, 4), "mg_act_bwd": (_lib.MG_ACT_RELU, 8), "mg_gate_bwd": (1, 2, 4), "mg_mish_fwd": (8,),
+             "mg_mish_bwd": (8,), "mg_upsample_zero_act": (1, 4, 2, 8, 1.0), "mg_upsample_zero": (1, 4, 2, 8),
+             "mg_step_embed": (1, 4), "mg_step_mlp_fwd": (1, 4, 6, 5), "mg_step_mlp_bwd": (1, 4, 6, 5),
+             "mg_linear_small_fwd": (1, 5, 7), "mg_linear_small_bwd": (1, 5, 7), "mg_loss_sum": (0.0, 1, 8),
+             "mg_loss_grad": (0.0, 1), "mg_mel_l1_fwd": (8, 4), "mg_mel_l1_bwd": (8, 4), "mg_mel_count_rows": (8, 4),
+             "mg_length_regulate_fwd": (1, 4, 3, 8), "mg_length_regulate_bwd": (1, 4, 3, 8),
+             "mg_word_pool_fwd": (1, 9, 4, 3, 4, 0), "mg_word_pool_bwd": (1, 9, 4, 3, 4, 0), "mg_mapping_mask": (1, 4, 8, 9),
+             "mg_rel_coef": (1, 4, 8)}
+    sig = _lib._signatures()
+    for name, values in small.items():
+        vals = iter(values)
+        args = [None if a is ctypes.c_void_p else next(vals, 8) for a in sig[name][1]]
+        assert getattr(L, name)(*args) == _lib.MG_ERR_ARG, name
+    assert L.mg_transpose_max_m() >= 0           # 0: no device to ask
 
 
 def test_bgemm_tile_choice_and_pin(monkeypatch):
