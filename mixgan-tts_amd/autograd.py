@@ -672,45 +672,28 @@ def scale_stack(x, slope, layers, *params):
 
 
 class _AvgPool4s2Fn(torch.autograd.Function):
-    """AvgPool1d(4, 2, padding=2), padding counted."""
+    """AvgPool1d(4, 2, padding, count_include_pad=...): (2, True) is HiFi-GAN's MeanPool, (1, False) MelGAN's
+    Downsample."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, padding, count_include_pad):
         _require_cuda(x)
-        ctx.Lin = x.shape[2]
-        return ops.avgpool4s2_fwd(x.contiguous())
+        ctx.cfg = (x.shape[2], padding, count_include_pad)
+        return ops.avgpool4s2_fwd(x.contiguous(), padding, count_include_pad)
 
     @staticmethod
     def backward(ctx, g):
-        return ops.avgpool4s2_bwd(g.contiguous(), ctx.Lin)
+        return ops.avgpool4s2_bwd(g.contiguous(), *ctx.cfg), None, None
 
 
-def avgpool4s2(x):
-    return _AvgPool4s2Fn.apply(x)
+def avgpool4s2(x, padding=2, count_include_pad=True):
+    return _AvgPool4s2Fn.apply(x, padding, count_include_pad)
 
 
 # --------------------------------------------------------------------------------------------------
-# MelGAN's discriminator (melgan_discriminators.py): its pool and the reflection pad in front of layer 0.  The grouped
-# layers are scale_stack's, on the four-channel-group kernels of csrc/gconv_c4.h.
+# MelGAN's discriminator (melgan_discriminators.py): the reflection pad in front of layer 0.  The grouped layers are
+# scale_stack's, on the four-channel-group kernels of csrc/gconv_c4.h; the pool is avgpool4s2(x, 1, False).
 # --------------------------------------------------------------------------------------------------
-class _AvgPool4s2p1Fn(torch.autograd.Function):
-    """AvgPool1d(4, 2, padding=1, count_include_pad=False)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        _require_cuda(x)
-        ctx.Lin = x.shape[2]
-        return ops.avgpool4s2p1_fwd(x.contiguous())
-
-    @staticmethod
-    def backward(ctx, g):
-        return ops.avgpool4s2p1_bwd(g.contiguous(), ctx.Lin)
-
-
-def avgpool4s2p1(x):
-    return _AvgPool4s2p1Fn.apply(x)
-
-
 class _ReflectPad1dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):

@@ -408,8 +408,18 @@ __global__ void c1_wgrad_finalize_kernel(const float *__restrict__ part, float *
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// AvgPool1d(4, 2, padding 2), count_include_pad
+// AvgPool1d(4, 2, padding PAD): window i = samples 2 i - PAD .. 2 i - PAD + 3 within [0, L).  COUNT_PAD: a window
+// divides by 4 (HiFi-GAN, PAD 2); otherwise by its in-range count (MelGAN, PAD 1, count_include_pad=False)
 // ---------------------------------------------------------------------------------------------------------------
+template <int PAD, bool COUNT_PAD>
+__device__ __forceinline__ float pool_rcp(int i, int L)
+{
+    if constexpr (COUNT_PAD) return 0.25f;
+    const int lo = 2 * i - PAD < 0 ? 0 : 2 * i - PAD, hi = 2 * i - PAD + 3 > L - 1 ? L - 1 : 2 * i - PAD + 3;
+    return 1.f / (float)(hi - lo + 1);
+}
+
+template <int PAD, bool COUNT_PAD>
 __global__ void avgpool_fwd_kernel(const float *__restrict__ in, float *__restrict__ out, long rows, int L, int Lout)
 {
     const long total = rows * Lout;
@@ -420,68 +430,31 @@ __global__ void avgpool_fwd_kernel(const float *__restrict__ in, float *__restri
         float s = 0.f;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int p = 2 * i - 2 + t;
+            const int p = 2 * i - PAD + t;
             if (p >= 0 && p < L) s += src[p];
         }
-        out[e] = 0.25f * s;
+        out[e] = s * pool_rcp<PAD, COUNT_PAD>(i, L);
     }
 }
 
+// Sample m lies in windows i - 1 and i, i = (m + PAD) / 2.  COUNT_PAD scales the SUM of the two taps, once: the
+// results are pinned bit for bit, and 0.25f * (a + b) and a * 0.25f + b * 0.25f differ where a product is subnormal
+template <int PAD, bool COUNT_PAD>
 __global__ void avgpool_bwd_kernel(const float *__restrict__ dy, float *__restrict__ dx, long rows, int L, int Lout)
 {
     const long total = rows * L;
     for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
         const long rrow = e / L;
-        const int m = e % L, i = (m + 2) / 2;
+        const int m = e % L, i = (m + PAD) / 2;
         const float *src = dy + rrow * Lout;
         float s = 0.f;
-        if (i < Lout) s += src[i];
-        if (i - 1 < Lout) s += src[i - 1];      // i >= 1 always
-        dx[e] = 0.25f * s;
+        if (i >= 1 && i - 1 < Lout) s += COUNT_PAD ? src[i - 1] : src[i - 1] * pool_rcp<PAD, false>(i - 1, L);
+        if (i < Lout) s += COUNT_PAD ? src[i] : src[i] * pool_rcp<PAD, false>(i, L);
+        dx[e] = COUNT_PAD ? 0.25f * s : s;
     }
 }
 
 int blocks_for(long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
-
-// ---------------------------------------------------------------------------------------------------------------
-// AvgPool1d(4, 2, padding 1), padding not counted (MelGAN): window i = samples 2 i - 1 .. 2 i + 2 within [0, L)
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pool_p1_rcp(int i, int L)
-{
-    const int lo = 2 * i - 1 < 0 ? 0 : 2 * i - 1, hi = 2 * i + 2 > L - 1 ? L - 1 : 2 * i + 2;
-    return 1.f / (float)(hi - lo + 1);
-}
-
-__global__ void avgpool_p1_fwd_kernel(const float *__restrict__ in, float *__restrict__ out, long rows, int L, int Lout)
-{
-    const long total = rows * Lout;
-    for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
-        const long rrow = e / Lout;
-        const int i = e % Lout;
-        const float *src = in + rrow * L;
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int p = 2 * i - 1 + t;
-            if (p >= 0 && p < L) s += src[p];
-        }
-        out[e] = s * pool_p1_rcp(i, L);
-    }
-}
-
-__global__ void avgpool_p1_bwd_kernel(const float *__restrict__ dy, float *__restrict__ dx, long rows, int L, int Lout)
-{
-    const long total = rows * L;
-    for (long e = blockIdx.x * 256l + threadIdx.x; e < total; e += gridDim.x * 256l) {
-        const long rrow = e / L;
-        const int m = e % L, i = (m + 1) / 2;      // windows i - 1 and i hold sample m
-        const float *src = dy + rrow * Lout;
-        float s = 0.f;
-        if (i >= 1 && i - 1 < Lout) s += src[i - 1] * pool_p1_rcp(i - 1, L);
-        if (i < Lout) s += src[i] * pool_p1_rcp(i, L);
-        dx[e] = s;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // ReflectionPad1d(p) and its fold-back
@@ -756,8 +729,8 @@ extern "C" int mg_avgpool4s2_fwd(const float *in, float *out, int rows, int L, v
     if (!in || !out) return MG_ERR_ARG;
     if (rows <= 0 || L <= 0) return MG_ERR_SHAPE;
     const int Lout = L / 2 + 1;
-    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(blocks_for((long)rows * Lout)), dim3(256), 0, (hipStream_t)stream, in, out,
-                       (long)rows, L, Lout);
+    hipLaunchKernelGGL((avgpool_fwd_kernel<2, true>), dim3(blocks_for((long)rows * Lout)), dim3(256), 0,
+                       (hipStream_t)stream, in, out, (long)rows, L, Lout);
     MG_LAUNCH_CHECK();
     return MG_OK;
 }
@@ -766,8 +739,8 @@ extern "C" int mg_avgpool4s2_bwd(const float *dy, float *dx, int rows, int L, vo
 {
     if (!dy || !dx) return MG_ERR_ARG;
     if (rows <= 0 || L <= 0) return MG_ERR_SHAPE;
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(blocks_for((long)rows * L)), dim3(256), 0, (hipStream_t)stream, dy, dx,
-                       (long)rows, L, L / 2 + 1);
+    hipLaunchKernelGGL((avgpool_bwd_kernel<2, true>), dim3(blocks_for((long)rows * L)), dim3(256), 0,
+                       (hipStream_t)stream, dy, dx, (long)rows, L, L / 2 + 1);
     MG_LAUNCH_CHECK();
     return MG_OK;
 }
@@ -777,8 +750,8 @@ extern "C" int mg_avgpool4s2p1_fwd(const float *in, float *out, int rows, int L,
     if (!in || !out) return MG_ERR_ARG;
     if (rows <= 0 || L < 2) return MG_ERR_SHAPE;
     const int Lout = (L - 2) / 2 + 1;
-    hipLaunchKernelGGL(avgpool_p1_fwd_kernel, dim3(blocks_for((long)rows * Lout)), dim3(256), 0, (hipStream_t)stream, in,
-                       out, (long)rows, L, Lout);
+    hipLaunchKernelGGL((avgpool_fwd_kernel<1, false>), dim3(blocks_for((long)rows * Lout)), dim3(256), 0,
+                       (hipStream_t)stream, in, out, (long)rows, L, Lout);
     MG_LAUNCH_CHECK();
     return MG_OK;
 }
@@ -787,8 +760,8 @@ extern "C" int mg_avgpool4s2p1_bwd(const float *dy, float *dx, int rows, int L, 
 {
     if (!dy || !dx) return MG_ERR_ARG;
     if (rows <= 0 || L < 2) return MG_ERR_SHAPE;
-    hipLaunchKernelGGL(avgpool_p1_bwd_kernel, dim3(blocks_for((long)rows * L)), dim3(256), 0, (hipStream_t)stream, dy, dx,
-                       (long)rows, L, (L - 2) / 2 + 1);
+    hipLaunchKernelGGL((avgpool_bwd_kernel<1, false>), dim3(blocks_for((long)rows * L)), dim3(256), 0,
+                       (hipStream_t)stream, dy, dx, (long)rows, L, (L - 2) / 2 + 1);
     MG_LAUNCH_CHECK();
     return MG_OK;
 }

@@ -59,6 +59,21 @@ class NormConv1d(nn.Module):
         return W / torch.dot(u, torch.mv(mat, v))
 
 
+def scale_walk(convs, x, slope, stack):
+    """One discriminator scale over its NormConv1d list, effective weights taken in layer order: convs[:stack] (the
+    one-channel first layer and the grouped layers) as one node of msd.hip kernels, then the dense K = 5 layer and the
+    logit layer through the MFMA conv kernel.  x [N, 1, T] -> [len(convs) - 1 activated maps, the raw logit map]."""
+    params = []
+    for conv in convs[:stack]:
+        params += [conv.effective_weight(), conv.bias]
+    maps = list(A.scale_stack(x, slope, [conv.geometry[3:] for conv in convs[:stack]], *params))
+    dense, post = convs[stack:]
+    maps.append(A.conv1d(maps[-1], dense.effective_weight(), dense.bias, 1, dense.geometry[5], "lrelu_s",
+                         act_slope=slope))
+    maps.append(A.conv1d(maps[-1], post.effective_weight(), post.bias, 1, post.geometry[5]))
+    return maps
+
+
 class DiscriminatorS(nn.Module):
     def __init__(self, use_spectral_norm=False):
         super().__init__()
@@ -69,25 +84,16 @@ class DiscriminatorS(nn.Module):
         """x [N, 1, T] -> (logits [N, T'], [seven activated maps, conv_post's raw map])."""
         if not x.is_cuda:
             raise MixganHipError("DiscriminatorS: tensors must be on the GPU (no CPU fallback)")
-        params = []
-        for conv in self.convs[:_STACK]:
-            params += [conv.effective_weight(), conv.bias]
-        layers = [g[3:] for g in MSD_LAYERS[:_STACK]]
-        fmap = list(A.scale_stack(x, LRELU_SLOPE, layers, *params))
-        last = self.convs[_STACK]
-        fmap.append(A.conv1d(fmap[-1], last.effective_weight(), last.bias, 1, last.geometry[5], "lrelu_s",
-                             act_slope=LRELU_SLOPE))
-        x = A.conv1d(fmap[-1], self.conv_post.effective_weight(), self.conv_post.bias, 1, MSD_POST[5])
-        fmap.append(x)
-        return torch.flatten(x, 1, -1), fmap
+        fmap = scale_walk([*self.convs, self.conv_post], x, LRELU_SLOPE, _STACK)
+        return torch.flatten(fmap[-1], 1, -1), fmap
 
 
 class MeanPool(nn.Module):
     """AvgPool1d(4, 2, padding=2)."""
-    kernel_size, stride, padding = 4, 2, 2
+    kernel_size, stride, padding, count_include_pad = 4, 2, 2, True
 
     def forward(self, x):
-        return A.avgpool4s2(x)
+        return A.avgpool4s2(x, self.padding, self.count_include_pad)
 
 
 class MultiScaleDiscriminator(nn.Module):

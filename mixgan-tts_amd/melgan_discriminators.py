@@ -21,7 +21,7 @@ from torch import nn
 
 from . import autograd as A
 from ._lib import MixganHipError
-from .hifigan_discriminators import NormConv1d
+from .hifigan_discriminators import NormConv1d, scale_walk
 
 LRELU_SLOPE = 0.2
 _PAD0 = 7
@@ -69,18 +69,8 @@ class NLayerDiscriminator(nn.Module):
         """x [N, 1, T], T > 7 -> [n_layers + 2 activated maps, the raw logit map]."""
         if not x.is_cuda:
             raise MixganHipError("NLayerDiscriminator: tensors must be on the GPU (no CPU fallback)")
-        convs = self.convs()
-        stack = self.n_layers + 1      # layer_0 and the grouped layers: one node
-        params = []
-        for conv in convs[:stack]:
-            params += [conv.effective_weight(), conv.bias]
-        layers = [g[3:] for g in self.geometry[:stack]]
-        maps = list(A.scale_stack(A.reflect_pad1d(x, _PAD0), LRELU_SLOPE, layers, *params))
-        dense, post = convs[stack], convs[stack + 1]
-        maps.append(A.conv1d(maps[-1], dense.effective_weight(), dense.bias, 1, dense.geometry[5], "lrelu_s",
-                             act_slope=LRELU_SLOPE))
-        maps.append(A.conv1d(maps[-1], post.effective_weight(), post.bias, 1, post.geometry[5]))
-        return maps
+        # layer_0 and the grouped layers: one node
+        return scale_walk(self.convs(), A.reflect_pad1d(x, _PAD0), LRELU_SLOPE, self.n_layers + 1)
 
 
 class Downsample(nn.Module):
@@ -88,7 +78,7 @@ class Downsample(nn.Module):
     kernel_size, stride, padding, count_include_pad = 4, 2, 1, False
 
     def forward(self, x):
-        return A.avgpool4s2p1(x)
+        return A.avgpool4s2(x, self.padding, self.count_include_pad)
 
 
 class Discriminator(nn.Module):

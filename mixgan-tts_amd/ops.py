@@ -700,37 +700,32 @@ def conv1d_c1_wgrad(dy, x, K, padding):
     return dw, db
 
 
-def avgpool4s2_fwd(x):
-    """AvgPool1d(4, 2, padding=2) of x [N, C, L] -> [N, C, L / 2 + 1]."""
+def _avgpool4s2_export(padding, count_include_pad, which):
+    if (padding, bool(count_include_pad)) not in ((2, True), (1, False)):
+        raise ValueError("avgpool4s2: the library has (padding 2, count_include_pad True) and (1, False), got (%r, %r)"
+                         % (padding, count_include_pad))
+    return getattr(_lib.lib(), "mg_avgpool4s2%s_%s" % ("" if padding == 2 else "p1", which))
+
+
+def avgpool4s2_fwd(x, padding=2, count_include_pad=True):
+    """AvgPool1d(4, 2, padding, count_include_pad=...) of x [N, C, L] -> [N, C, (L + 2 padding - 4) / 2 + 1]:
+    (2, True) is HiFi-GAN's, (1, False) MelGAN's, whose windows divide by their in-range count."""
+    export = _avgpool4s2_export(padding, count_include_pad, "fwd")
     N, C, Lin = x.shape
-    out = torch.empty(N, C, Lin // 2 + 1, device=x.device, dtype=torch.float32)
-    check(_lib.lib().mg_avgpool4s2_fwd(fptr(x), fptr(out), N * C, Lin, stream_ptr()))
+    out = torch.empty(N, C, max((Lin + 2 * padding - 4) // 2 + 1, 0), device=x.device, dtype=torch.float32)
+    check(export(fptr(x), fptr(out), N * C, Lin, stream_ptr()))
     return out
 
 
-def avgpool4s2_bwd(dy, Lin):
+def avgpool4s2_bwd(dy, Lin, padding=2, count_include_pad=True):
+    export = _avgpool4s2_export(padding, count_include_pad, "bwd")
     N, C, _ = dy.shape
     dx = torch.empty(N, C, Lin, device=dy.device, dtype=torch.float32)
-    check(_lib.lib().mg_avgpool4s2_bwd(fptr(dy), fptr(dx), N * C, Lin, stream_ptr()))
+    check(export(fptr(dy), fptr(dx), N * C, Lin, stream_ptr()))
     return dx
 
 
-# ---- MelGAN's discriminator (csrc/msd.hip): the uncounted-padding pool and the reflection pad in front of layer 0
-def avgpool4s2p1_fwd(x):
-    """AvgPool1d(4, 2, padding=1, count_include_pad=False) of x [N, C, L] -> [N, C, (L - 2) / 2 + 1]."""
-    N, C, Lin = x.shape
-    out = torch.empty(N, C, max((Lin - 2) // 2 + 1, 0), device=x.device, dtype=torch.float32)
-    check(_lib.lib().mg_avgpool4s2p1_fwd(fptr(x), fptr(out), N * C, Lin, stream_ptr()))
-    return out
-
-
-def avgpool4s2p1_bwd(dy, Lin):
-    N, C, _ = dy.shape
-    dx = torch.empty(N, C, Lin, device=dy.device, dtype=torch.float32)
-    check(_lib.lib().mg_avgpool4s2p1_bwd(fptr(dy), fptr(dx), N * C, Lin, stream_ptr()))
-    return dx
-
-
+# ---- MelGAN's discriminator (csrc/msd.hip): the reflection pad in front of layer 0
 def reflect_pad1d_fwd(x, p):
     """ReflectionPad1d(p) of x [N, C, T] -> [N, C, T + 2 p]."""
     N, C, T = x.shape

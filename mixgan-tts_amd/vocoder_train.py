@@ -11,6 +11,8 @@ Both trainers need only .parameters(), .forward_train(mel[, taps]) and .state_di
 melgan.MelVocoder trains in them as a vocoder.Generator does; export_melgan_generator writes what get_vocoder loads for
 MelGAN.
 """
+import collections
+
 import torch
 import torch.nn.functional as F
 
@@ -125,6 +127,26 @@ class GeneratorTrainer:
         return self
 
 
+# What VocoderGANTrainer.step takes from its objective.  call(d, y, y_hat) -> one discriminator's outputs `out`;
+# tap(out): what taps["d"] / taps["g"] record; d_loss(out): the D-phase term; adv_fm(out): the G-phase pair.
+# weighs_fm: fm enters the total times lambda_feat.  mel_optional: lambda_mel == 0 skips the mel term's computation.
+_Objective = collections.namedtuple("_Objective", "call tap d_loss adv_fm weighs_fm mel_optional")
+_OBJECTIVES = {
+    "hifigan": _Objective(      # out = (y_d_rs, y_d_gs, fmap_rs, fmap_gs)
+        call=lambda d, y, y_hat: d(y, y_hat),
+        tap=lambda out: (out[2], out[3]),
+        d_loss=lambda out: hifigan_discriminator_loss(out[0], out[1])[0],
+        adv_fm=lambda out: (hifigan_generator_loss(out[1])[0], hifigan_feature_loss(out[2], out[3])),
+        weighs_fm=False, mel_optional=False),
+    "melgan": _Objective(       # out = (D_real, D_fake)
+        call=lambda d, y, y_hat: d.forward_pair(y, y_hat),
+        tap=tuple,
+        d_loss=lambda out: melgan_discriminator_loss(out[0], out[1]),
+        adv_fm=lambda out: (melgan_generator_loss(out[1]), melgan_feature_loss(out[0], out[1])),
+        weighs_fm=True, mel_optional=True),
+}
+
+
 class VocoderGANTrainer:
     """HiFi-GAN's training step (Kong et al. 2020, train.py) over a vocoder.Generator and a dict name -> discriminator.
 
@@ -143,7 +165,7 @@ class VocoderGANTrainer:
 
     def __init__(self, generator, stft, discriminators, optimizer=None, lr=2e-4, betas=(0.8, 0.99), lr_decay=0.999,
                  lambda_mel=45.0, objective="hifigan", lambda_feat=10.0):
-        if objective not in ("hifigan", "melgan"):
+        if objective not in _OBJECTIVES:
             raise ValueError("objective: 'hifigan' or 'melgan', got %r" % (objective,))
         self.objective = objective
         self.lambda_feat = float(lambda_feat)
@@ -171,7 +193,8 @@ class VocoderGANTrainer:
         through the UPDATED discriminators, whose parameters need no gradient for the duration, and steps.
         Returns {"loss_d", "loss_g", "mel_l1", "adv", "fm"} as device scalars; nothing here reads the device.
         taps: a dict that receives what fixes the step's leaky-ReLU sign patterns: "generator" (forward_train's taps)
-        and "d" / "g": name -> (fmap_rs, fmap_gs) of the discriminator and of the generator phase."""
+        and "d" / "g": name -> (fmap_rs, fmap_gs) of the discriminator and of the generator phase.  _OBJECTIVES holds
+        what objective="melgan" does differently (the class docstring)."""
         if not mel.is_cuda or not wav.is_cuda:
             raise _lib.MixganHipError("VocoderGANTrainer.step: tensors must be on the GPU (no CPU fallback)")
         y = wav.unsqueeze(1) if wav.dim() == 2 else wav
@@ -180,69 +203,34 @@ class VocoderGANTrainer:
         y_hat = self.generator.forward_train(mel, None if taps is None else taps["generator"])
         if y_hat.shape != y.shape:
             raise ValueError("wav must be %s, got %s" % (tuple(y_hat.shape), tuple(y.shape)))
-        if self.objective == "melgan":
-            return self._step_melgan(y, y_hat, taps)
+        obj = _OBJECTIVES[self.objective]
 
         self.optim_d.zero_grad(set_to_none=True)
         y_hat_d = y_hat.detach()
         loss_d = None
         for name, d in self.discriminators.items():
-            y_d_rs, y_d_gs, fmap_rs, fmap_gs = d(y, y_hat_d)
+            out = obj.call(d, y, y_hat_d)
             if taps is not None:
-                taps["d"][name] = (fmap_rs, fmap_gs)
-            part = hifigan_discriminator_loss(y_d_rs, y_d_gs)[0]
+                taps["d"][name] = obj.tap(out)
+            part = obj.d_loss(out)
             loss_d = part if loss_d is None else loss_d + part
         loss_d.backward()
         self.optim_d.step()
 
         self.optim_g.zero_grad(set_to_none=True)
-        mel_l1 = _mel_l1(self.stft, y_hat.squeeze(1), y.squeeze(1))
+        skip_mel = obj.mel_optional and self.lambda_mel == 0.0
+        mel_l1 = None if skip_mel else _mel_l1(self.stft, y_hat.squeeze(1), y.squeeze(1))
         for p in self._d_params:
             p.requires_grad_(False)
         try:
             adv = fm = None
             for name, d in self.discriminators.items():
-                _, y_d_gs, fmap_rs, fmap_gs = d(y, y_hat)
+                out = obj.call(d, y, y_hat)
                 if taps is not None:
-                    taps["g"][name] = (fmap_rs, fmap_gs)
-                a, f = hifigan_generator_loss(y_d_gs)[0], hifigan_feature_loss(fmap_rs, fmap_gs)
+                    taps["g"][name] = obj.tap(out)
+                a, f = obj.adv_fm(out)
                 adv, fm = (a, f) if adv is None else (adv + a, fm + f)
-            loss_g = adv + fm + self.lambda_mel * mel_l1
-            loss_g.backward()
-        finally:
-            for p in self._d_params:
-                p.requires_grad_(True)
-        self.optim_g.step()
-        self.steps += 1
-        return {"loss_d": loss_d.detach(), "loss_g": loss_g.detach(), "mel_l1": mel_l1.detach(), "adv": adv.detach(),
-                "fm": fm.detach()}
-
-    def _step_melgan(self, y, y_hat, taps):
-        self.optim_d.zero_grad(set_to_none=True)
-        y_hat_d = y_hat.detach()
-        loss_d = None
-        for name, d in self.discriminators.items():
-            D_real, D_fake = d.forward_pair(y, y_hat_d)
-            if taps is not None:
-                taps["d"][name] = (D_real, D_fake)
-            part = melgan_discriminator_loss(D_real, D_fake)
-            loss_d = part if loss_d is None else loss_d + part
-        loss_d.backward()
-        self.optim_d.step()
-
-        self.optim_g.zero_grad(set_to_none=True)
-        mel_l1 = _mel_l1(self.stft, y_hat.squeeze(1), y.squeeze(1)) if self.lambda_mel != 0.0 else None
-        for p in self._d_params:
-            p.requires_grad_(False)
-        try:
-            adv = fm = None
-            for name, d in self.discriminators.items():
-                D_real, D_fake = d.forward_pair(y, y_hat)
-                if taps is not None:
-                    taps["g"][name] = (D_real, D_fake)
-                a, f = melgan_generator_loss(D_fake), melgan_feature_loss(D_real, D_fake)
-                adv, fm = (a, f) if adv is None else (adv + a, fm + f)
-            loss_g = adv + self.lambda_feat * fm
+            loss_g = adv + (self.lambda_feat * fm if obj.weighs_fm else fm)
             if mel_l1 is not None:
                 loss_g = loss_g + self.lambda_mel * mel_l1
             loss_g.backward()

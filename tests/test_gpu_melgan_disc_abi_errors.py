@@ -97,7 +97,7 @@ def test_pool_and_reflect_pad(mg):
     assert L.mg_reflect_pad1d_bwd(fptr(padded), fptr(dx), 3, 16, 7, s) == MG_OK
     assert not untouched(out) and not untouched(dx) and not untouched(padded)
     with pytest.raises(mg.MixganHipError):
-        mg.ops.avgpool4s2p1_fwd(torch.zeros(1, 1, 1).cuda())
+        mg.ops.avgpool4s2_fwd(torch.zeros(1, 1, 1).cuda(), padding=1, count_include_pad=False)
     with pytest.raises(mg.MixganHipError):
         mg.ops.reflect_pad1d_fwd(torch.zeros(1, 1, 7).cuda(), 7)
 

@@ -257,6 +257,21 @@ def test_trainer_sgd_two_steps_match_float64(mg, manifest, stft):
     assert all(p.requires_grad for d in tr.discriminators.values() for p in d.parameters())
 
 
+def test_hifigan_step_computes_the_mel_term_at_weight_zero(mg, manifest, stft):
+    """objective="hifigan" with lambda_mel = 0 still evaluates the mel term (only objective="melgan" may skip it):
+    "mel_l1" is the real value, the bits of _mel_l1 on the pre-step weights, and loss_g is adv + fm."""
+    tr, _, _, _ = build_trainer(mg, manifest, stft, lambda_mel=0.0)
+    mel, wav = (t.cuda() for t in trainer_batch())
+    with torch.no_grad():
+        expected = mg.vocoder_train._mel_l1(stft, tr.generator.forward_train(mel).squeeze(1), wav)
+    out = tr.step(mel, wav)
+    print("mel_l1 %.6f (expected %.6f)  loss_g %.6f  adv %.6f  fm %.6f"
+          % tuple(float(v) for v in (out["mel_l1"], expected, out["loss_g"], out["adv"], out["fm"])))
+    assert bool(torch.isfinite(out["mel_l1"])) and float(out["mel_l1"]) != 0.0
+    assert torch.equal(out["mel_l1"], expected)
+    assert torch.equal(out["loss_g"], out["adv"] + out["fm"])
+
+
 def test_trainer_defaults_and_checkpoint(mg, manifest, stft, tmp_path):
     tr, Wg, Wp, _ = build_trainer(mg, manifest, stft)
     assert isinstance(tr.optim_g, torch.optim.AdamW) and isinstance(tr.optim_d, torch.optim.AdamW)
