@@ -140,6 +140,8 @@ int mg_conv1d_fwd_split(const float *in, const float *in_vec, const float *packe
 #define MG_CONV_EPI_PHASES_SLICE 2 /* mg_conv_transpose1d_fwd_slice: K = 3 */
 #define MG_CONV_EPI_NEEDS_WM2 3    /* an epilogue that pairs 32-row blocks (the denoiser's gate): K in {1,3,5,9}, never
                                     * the one-block-per-wave forms */
+#define MG_CONV_EPI_PERIOD 5       /* mg_period_conv_fwd / _dgrad: K = 5 at stride 3 and 1, K = 3, K = 2 (the two-tap
+                                    * polyphase GEMM of the stride-3 data gradient).  (4 names nothing: MG_ERR_ARG.) */
 typedef struct mg_conv_plan {
     int32_t kw, stride, ck, dilmax; /* the (K, stride, chunk channels, largest dilation) case */
     int32_t mw, wm, nnb;            /* waves along the rows, 32-row blocks and 32-frame blocks per wave:
@@ -1029,6 +1031,45 @@ int mg_avgpool4s2p1_bwd(const float *dy, float *dx, int rows, int L, void *strea
  * p < 0 or T <= p is MG_ERR_SHAPE. */
 int mg_reflect_pad1d_fwd(const float *in, float *out, int rows, int T, int p, void *stream);
 int mg_reflect_pad1d_bwd(const float *dy, float *dx, int rows, int T, int p, void *stream);
+
+/* ------------------------------------------------------------------ HiFi-GAN multi-period discriminator (mpd.hip)
+ * DiscriminatorP(p) as six plain 1-D convolutions on a SLOTTED flat axis.  For T samples, reflect-padded on the right
+ * to a multiple of p, mg_period_geometry writes the heights H[0..6] (H[0] = ceil(T / p), H[j+1] = (H[j] - 1) / 3 + 1
+ * for the four stride-3 layers, H[5] = H[6] = H[4]) and the slot widths S[0..6] (S[4] = S[5] = S[6] = H[4] + 2,
+ * S[j] = 3 S[j+1] below).  Map j is channel-major [C, R S[j]], R = N p: row r = n p + w owns columns [r S[j], r S[j] +
+ * H[j]), element (n, c, h, w) of the published [N, C, H[j], p] map is column (n p + w) S[j] + h of channel c, and every
+ * other column (the slack) holds exactly 0.  Because S[j] = stride S[j+1] and S[j] >= H[j] + 2, Conv2d((K,1), (stride,1),
+ * ((K-1)/2, 0)) over all rows is ONE Conv1d(K, stride, (K-1)/2) along the flat axis: a row's zero padding is its
+ * neighbour's slack, and Lout = R S[j+1] exactly.  No GPU work; MG_ERR_SHAPE for T < 1, p < 1, a reflect pad that does
+ * not fit (T <= p - 1 - (T - 1) mod p) or widths past int; MG_ERR_ARG for a null array. */
+int mg_period_geometry(int T, int p, int *H, int *S);
+/* The fold: in0[(n p + w) S0 + h] = y[n, reflect(h p + w)] for h < H0, else 0 (y [N, T], in0 [N p S0]), and its backward
+ * dy[n, t] = din0 at t's own column plus, where a pad sample mirrors t, that sample's column, added in that order.
+ * H0, S0 are those of mg_period_geometry(T, p); N p S0 past 2^30 is MG_ERR_SHAPE. */
+int mg_period_fold_fwd(const float *y, float *in0, int N, int T, int p, void *stream);
+int mg_period_fold_bwd(const float *din0, float *dy, int N, int T, int p, void *stream);
+/* One layer on the slotted axis: in [Ci, Lin], Lin = R S_in; out [Co, Lout], Lout = R S_out, S_in = stride S_out:
+ *   out[co, l] = (l mod S_out < H_out) ? act(sum_{ci,k} w[co,ci,k] in[ci, l stride + k - (K-1)/2] + bias[co]) : 0,
+ * act MG_ACT_NONE or MG_ACT_LRELU with `slope`; (K, stride) in {(5,3), (5,1), (3,1)}; packed = mg_conv_pack(w,
+ * MG_PACK_PLAIN).  scratch (may be NULL): the split-reduction scratch of mg_conv1d_fwd_split, for the deep layers whose
+ * output is a few tiles.  Lin != R S_in, Lout != R S_out, S_in != stride S_out, H_out > S_out - 2 or H_out < 1, another
+ * (K, stride), or R S_in past 2^30 are MG_ERR_SHAPE before any launch; null in / packed / out MG_ERR_ARG. */
+int mg_period_conv_fwd(const float *in, const float *packed, const float *bias, float *out, int R, int Ci, int Lin,
+                       int S_in, int Co, int Lout, int S_out, int H_out, int K, int stride, int act, float slope,
+                       float *scratch, size_t scratch_floats, void *stream);
+/* Its data gradient, d [Co, Lout] -> dx [Ci, Lin]:
+ *   dx[ci, m] = (m mod S_in < H_in) ? (sum_{co,k : m + (K-1)/2 - k = stride l} w[co,ci,k] d[co,l] + add[ci,m]) * mask : 0,
+ * mask = map[ci,m] > 0 ? 1 : slope from the stored activated map of the layer below (NULL: 1), add (NULL: 0) a gradient
+ * that reaches that map from outside; positions no output reads get exactly add * mask, the slack exactly 0.
+ * Stride 1: packed = mg_conv_pack(w, MG_PACK_DGRAD).  Stride 3: packed = mg_period_dgrad3_pack(w), a polyphase two-tap
+ * GEMM with 3 Ci rows over d -- with m = 3 q + f: f = 0 reads w[.,.,2] d[q]; f = 1 w[.,.,0] d[q+1] + w[.,.,3] d[q];
+ * f = 2 w[.,.,1] d[q+1] + w[.,.,4] d[q] -- 6/5 of the forward's flops, no zero insertion; GEMM row ci 3 + f, column q
+ * is written to dx[ci, 3 q + f].  Checks as mg_period_conv_fwd, with H_in against S_in. */
+size_t mg_period_dgrad3_packed_floats(int Co, int Ci);
+int mg_period_dgrad3_pack(const float *w, float *packed, int Co, int Ci, void *stream);
+int mg_period_conv_dgrad(const float *d, const float *packed, const float *map, const float *add, float *dx, int R,
+                         int Ci, int Lin, int S_in, int H_in, int Co, int Lout, int S_out, int K, int stride,
+                         float slope, float *scratch, size_t scratch_floats, void *stream);
 
 /* ------------------------------------------------------------------ measurement hooks (bench.py)
  * While a session is open, mg_denoiser_fwd brackets each launch of its dominant kernel (the k=3

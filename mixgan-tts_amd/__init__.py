@@ -47,6 +47,7 @@ from .vocoder_train import GeneratorTrainer, VocoderGANTrainer, sample_segments 
 from .losses import hifigan_discriminator_loss, hifigan_generator_loss, hifigan_feature_loss  # noqa: F401
 from . import hifigan_discriminators  # noqa: F401
 from .hifigan_discriminators import DiscriminatorS, MultiScaleDiscriminator  # noqa: F401
+from .hifigan_discriminators import DiscriminatorP, MultiPeriodDiscriminator  # noqa: F401
 from . import melgan_discriminators  # noqa: F401
 from .losses import melgan_discriminator_loss, melgan_generator_loss, melgan_feature_loss  # noqa: F401
 

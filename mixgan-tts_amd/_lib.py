@@ -23,6 +23,7 @@ MG_PLAN_PER_LAYER, MG_PLAN_SINGLE = 0, 1                                        
 MG_PLAN_PERSIST, MG_PLAN_PERSIST16, MG_PLAN_TEAM16 = 0, 1, 2                      # mg_fwd_plan.family
 MG_STATUS_TICKET, MG_STATUS_ERROR, MG_STATUS_LAUNCHES, MG_STATUS_DONE, MG_STATUS_WORDS = range(5)   # mg_denoiser_*_status
 MG_CONV_EPI_PLAIN, MG_CONV_EPI_REFLECT, MG_CONV_EPI_PHASES_SLICE, MG_CONV_EPI_NEEDS_WM2 = range(4)   # mg_conv1d_fwd_plan
+MG_CONV_EPI_PERIOD = 5                                                            # (4 names no list: MG_ERR_ARG)
 # the denoiser's weight / gradient pointer table: head slots, then MG_DEN_LAYER_PTRS slots per residual layer
 MG_DEN_HEAD_PTRS, MG_DEN_LAYER_PTRS = 8, 9
 (MG_DEN_IN_W, MG_DEN_IN_B, MG_DEN_MLP0_W, MG_DEN_MLP2_W, MG_DEN_SKIP_W, MG_DEN_SKIP_B, MG_DEN_OUT_W,
@@ -261,6 +262,13 @@ def _signatures():
         "mg_avgpool4s2p1_bwd": (i, [vp, vp, i, i, vp]),
         "mg_reflect_pad1d_fwd": (i, [vp, vp, i, i, i, vp]),
         "mg_reflect_pad1d_bwd": (i, [vp, vp, i, i, i, vp]),
+        "mg_period_geometry": (i, [i, i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+        "mg_period_fold_fwd": (i, [vp, vp, i, i, i, vp]),
+        "mg_period_fold_bwd": (i, [vp, vp, i, i, i, vp]),
+        "mg_period_conv_fwd": (i, [vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, f, vp, sz, vp]),
+        "mg_period_dgrad3_packed_floats": (sz, [i, i]),
+        "mg_period_dgrad3_pack": (i, [vp, vp, i, i, vp]),
+        "mg_period_conv_dgrad": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, f, vp, sz, vp]),
     }
 
 

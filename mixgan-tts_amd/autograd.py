@@ -708,3 +708,72 @@ class _ReflectPad1dFn(torch.autograd.Function):
 
 def reflect_pad1d(x, p):
     return _ReflectPad1dFn.apply(x, p)
+
+
+# --------------------------------------------------------------------------------------------------
+# HiFi-GAN multi-period discriminator (csrc/mpd.hip; hifigan_discriminators.py)
+# --------------------------------------------------------------------------------------------------
+class _PeriodStackFn(torch.autograd.Function):
+    """DiscriminatorP(p) as ONE node: the fold of x [N, 1, T] onto the slotted axis, the five leaky-ReLU layers and
+    conv_post; returns the six slotted maps [1, C, N p S[j]] (slack exactly 0).  params = (w0, b0, ..., w5, b5),
+    effective [Co, Ci, K] weights.  Stores only the activated maps (slope > 0 keeps the sign); a map's gradient from
+    outside (feature matching) and the mask of the layer below ride in the data-gradient epilogue of the layer above;
+    weight / bias / data gradients are computed only where asked for."""
+
+    @staticmethod
+    def forward(ctx, x, p, slope, *params):
+        _require_cuda(x)
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise _lib.MixganHipError("period_stack: expected a waveform [N, 1, T], got %s" % (tuple(x.shape),))
+        x = x.contiguous()
+        N, _, T = x.shape
+        H, S = ops.period_geometry(T, p)
+        ws = [w.detach().contiguous() for w in params[0::2]]
+        bs = [b.detach() for b in params[1::2]]
+        n = len(ws)
+        bufs = [ops.period_fold_fwd(x, p)]
+        for j in range(n):
+            bufs.append(ops.period_conv_fwd(bufs[-1], ws[j], bs[j], N * p, S[j], S[j + 1], H[j + 1], S[j] // S[j + 1],
+                                            slope if j < n - 1 else None))
+        ctx.save_for_backward(*bufs[:-1], *ws)
+        ctx.cfg = (N, T, p, slope, H, S)
+        ctx.set_materialize_grads(False)
+        return tuple(bufs[1:])
+
+    @staticmethod
+    def backward(ctx, *gs):
+        N, T, p, slope, H, S = ctx.cfg
+        n = len(gs)
+        saved = ctx.saved_tensors
+        bufs, ws = saved[:n], saved[n:]        # bufs[j]: the input of layer j (the fold, then the activated maps)
+        need = ctx.needs_input_grad
+        need_w = [need[3 + 2 * j] for j in range(n)]
+        need_b = [need[4 + 2 * j] for j in range(n)]
+        lowest = 0 if need[0] else min([j for j in range(n) if need_w[j] or need_b[j]], default=n)
+        grads = [None] * (3 + 2 * n)
+        R = N * p
+        d = None                                   # gradient of layer j's PRE-activation, slotted
+        for j in range(n - 1, lowest - 1, -1):
+            if d is None:
+                if gs[j] is None:
+                    continue
+                d = gs[j].contiguous()
+                if j < n - 1:
+                    d = ops.lrelu_bwd(d, bufs[j + 1], slope)
+            K, stride = ws[j].shape[2], S[j] // S[j + 1]
+            if need_w[j]:
+                grads[3 + 2 * j] = ops.conv1d_wgrad(d, bufs[j], K, stride, (K - 1) // 2)
+            if need_b[j]:
+                grads[4 + 2 * j] = ops.rowsum(d)
+            if j > lowest:
+                add = gs[j - 1]
+                d = ops.period_conv_dgrad(d, ws[j], R, S[j], H[j], S[j + 1], stride, map=bufs[j],
+                                          add=None if add is None else add.contiguous(), slope=slope)
+            elif need[0]:
+                din0 = ops.period_conv_dgrad(d, ws[0], R, S[0], H[0], S[1], stride)
+                grads[0] = ops.period_fold_bwd(din0, N, T, p)
+        return tuple(grads)
+
+
+def period_stack(x, p, slope, *params):
+    return _PeriodStackFn.apply(x, p, slope, *params)

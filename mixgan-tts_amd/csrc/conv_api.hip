@@ -74,7 +74,7 @@ extern "C" int mg_conv_transpose_pack(const float *w, float *packed, int Ci, int
 }
 
 // conv_plan for an entry point's launches: this file's (the path's cases and the wide ones), melgan.hip's reflect-padded
-// and slice-writing ones, the denoiser's gate (EpiNeedsWM2, the path's cases only).
+// and slice-writing ones, the denoiser's gate (EpiNeedsWM2, the path's cases only), mpd.hip's period convolutions.
 extern "C" int mg_conv1d_fwd_plan(int B, int Ci, int Lout, int rows, int K, int stride, int dil, size_t scratch_floats,
                                   int epi, mg_conv_plan *out)
 {
@@ -85,6 +85,7 @@ extern "C" int mg_conv1d_fwd_plan(int B, int Ci, int Lout, int rows, int K, int 
     case MG_CONV_EPI_REFLECT: kind = ConvEpiKind{CONV_CASES_REFLECT, false}; break;
     case MG_CONV_EPI_PHASES_SLICE: kind = ConvEpiKind{CONV_CASES_SLICE, false}; break;
     case MG_CONV_EPI_NEEDS_WM2: kind = ConvEpiKind{CONV_CASES_PATH, true}; break;
+    case MG_CONV_EPI_PERIOD: kind = ConvEpiKind{CONV_CASES_PERIOD, false}; break;
     default: return MG_ERR_ARG;
     }
     mg_conv_plan p{};

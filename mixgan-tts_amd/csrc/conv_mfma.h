@@ -494,19 +494,23 @@ enum ConvCases {
     CONV_CASES_SLICE,      // the polyphase transposed conv writing a channel slice of a wider buffer (K = 3 only)
     CONV_CASES_DIL9,       // zero padding, K = 3 with dilation <= 9: the data gradient of the reflect-padded ResnetBlock
                            //   conv as the full correlation over the padded length (melgan_train.hip)
+    CONV_CASES_PERIOD,     // the period discriminator on its slotted flat axis (mpd.hip): K = 5 at stride 3 and 1, K = 3, and
+                           //   the two-tap GEMM of the polyphase stride-3 data gradient
 };
 #define MG_CONV_CASES_BASE(X) X(1, 1, 32, 1) X(3, 1, 32, 1) X(5, 1, 16, 1) X(9, 1, 16, 1) X(5, 2, 16, 1)
 #define MG_CONV_CASES_WIDE(X) X(3, 1, 32, 5) X(7, 1, 16, 5) X(11, 1, 16, 5) X(16, 1, 16, 1) X(4, 1, 16, 1)
 #define MG_CONV_CASES_REFLECT(X) X(3, 1, 32, 9) X(7, 1, 16, 1)
 #define MG_CONV_CASES_SLICE(X) X(3, 1, 32, 1)
 #define MG_CONV_CASES_DIL9(X) X(3, 1, 32, 9)
+#define MG_CONV_CASES_PERIOD(X) X(5, 3, 16, 1) X(5, 1, 16, 1) X(3, 1, 32, 1) X(2, 1, 32, 1)
 // Every list with its cases: LIST(id, the list's X(...) cases).  The one chain conv_plan and conv_launch both expand.
 #define MG_CONV_LISTS(LIST, X)                                                   \
     LIST(CONV_CASES_PATH, MG_CONV_CASES_BASE(X))                                 \
     LIST(CONV_CASES_PATH_WIDE, MG_CONV_CASES_BASE(X) MG_CONV_CASES_WIDE(X))      \
     LIST(CONV_CASES_REFLECT, MG_CONV_CASES_REFLECT(X))                           \
     LIST(CONV_CASES_SLICE, MG_CONV_CASES_SLICE(X))                               \
-    LIST(CONV_CASES_DIL9, MG_CONV_CASES_DIL9(X))
+    LIST(CONV_CASES_DIL9, MG_CONV_CASES_DIL9(X))                                 \
+    LIST(CONV_CASES_PERIOD, MG_CONV_CASES_PERIOD(X))
 
 // What the plan needs to know of a launch: its case list, and whether its epilogue needs WM = 2.
 struct ConvEpiKind {

@@ -1,4 +1,6 @@
-"""HiFi-GAN's multi-scale discriminator (Kong et al. 2020) on the HIP kernels of csrc/msd.hip.
+"""HiFi-GAN's discriminators (Kong et al. 2020): the multi-scale one on the HIP kernels of csrc/msd.hip, the multi-period
+one (DiscriminatorP / MultiPeriodDiscriminator, at the end of this file) on csrc/mpd.hip -- state-dict keys of
+weight_norm(Conv2d): `bias, weight_g [Co,1,1,1], weight_v [Co,Ci,K,1]`.
 
 DiscriminatorS / MultiScaleDiscriminator keep the published constructor arguments, attribute names (convs, conv_post,
 discriminators, meanpools), forward(y, y_hat) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs) and the state-dict keys of the torch
@@ -15,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import autograd as A
+from . import ops
 from ._lib import MixganHipError
 
 LRELU_SLOPE = 0.1
@@ -121,4 +124,90 @@ class MultiScaleDiscriminator(nn.Module):
             y_d_gs.append(g)
             fmap_rs.append(fr)
             fmap_gs.append(fg)
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the multi-period discriminator (csrc/mpd.hip)
+# ------------------------------------------------------------------------------------------------------------------
+MPD_PERIODS = (2, 3, 5, 7, 11)
+MPD_CHANNELS = (1, 32, 128, 512, 1024, 1024)      # DiscriminatorP.convs: K = 5, stride 3 (the last one stride 1)
+
+
+class UnsupportedPeriodConfig(MixganHipError, NotImplementedError):
+    """A DiscriminatorP constructor argument the HIP path has no kernels for: both MixganHipError (no fallback) and
+    NotImplementedError (the published multi-period discriminator never uses it)."""
+
+
+class NormConv2d(nn.Module):
+    """The parameters of one Conv2d(ci, co, (k, 1)) under weight_norm -- bias, weight_g [Co,1,1,1], weight_v [Co,Ci,k,1] --
+    initialised as torch initialises them, and the effective [Co, Ci, k] weight as a torch expression."""
+
+    def __init__(self, ci, co, k, stride, padding):
+        super().__init__()
+        self.geometry = (ci, co, k, stride, padding)
+        ref = nn.Conv2d(ci, co, (k, 1), (stride, 1), padding=(padding, 0))
+        w = ref.weight.detach()
+        self.bias = nn.Parameter(ref.bias.detach().clone())
+        self.weight_g = nn.Parameter(w.flatten(1).norm(dim=1).view(-1, 1, 1, 1))
+        self.weight_v = nn.Parameter(w.clone())
+
+    def effective_weight(self):
+        return A.weight_norm(self.weight_v.squeeze(3), self.weight_g.squeeze(3))
+
+
+class DiscriminatorP(nn.Module):
+    """One period of the multi-period discriminator.  The input is folded onto a slotted flat axis (one slot per
+    (n, w) row of the published [N, C, H, period] map) on which every layer is a plain 1-D convolution; the returned maps
+    are strided views of those buffers with the published shapes and values."""
+
+    def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
+        super().__init__()
+        if kernel_size != 5 or stride != 3 or use_spectral_norm:
+            raise UnsupportedPeriodConfig("DiscriminatorP: the HIP path has kernel_size 5, stride 3 under weight norm (the "
+                                         "published multi-period discriminator), got kernel_size %r, stride %r, "
+                                         "use_spectral_norm %r" % (kernel_size, stride, use_spectral_norm))
+        if int(period) != period or period < 1:
+            raise ValueError("DiscriminatorP: period must be a positive integer, got %r" % (period,))
+        self.period = int(period)
+        ch = MPD_CHANNELS
+        self.convs = nn.ModuleList([NormConv2d(ch[j], ch[j + 1], 5, 3 if j < 4 else 1, 2) for j in range(5)])
+        self.conv_post = NormConv2d(ch[5], 1, 3, 1, 1)
+
+    def forward(self, x):
+        """x [N, 1, T] -> (logits [N, H6 period], [five activated maps, conv_post's raw map], each [N, C, H, period])."""
+        if not x.is_cuda:
+            raise MixganHipError("DiscriminatorP: tensors must be on the GPU (no CPU fallback)")
+        if x.dim() != 3 or x.shape[1] != 1 or x.dtype != torch.float32:
+            raise MixganHipError("DiscriminatorP: expected a float32 waveform [N, 1, T], got %s %s"
+                                 % (x.dtype, tuple(x.shape)))
+        N, _, T = x.shape
+        p = self.period
+        H, S = ops.period_geometry(T, p)
+        params = []
+        for conv in [*self.convs, self.conv_post]:
+            params += [conv.effective_weight(), conv.bias]
+        bufs = A.period_stack(x, p, LRELU_SLOPE, *params)
+        fmap = [b.view(b.shape[1], N, p, S[j + 1]).permute(1, 0, 3, 2)[:, :, :H[j + 1]] for j, b in enumerate(bufs)]
+        return torch.flatten(fmap[-1], 1, -1), fmap
+
+
+class MultiPeriodDiscriminator(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorP(p) for p in MPD_PERIODS])
+
+    def forward(self, y, y_hat):
+        """Every period runs once on the batch [y; y_hat]: weight norm gives one weight for both halves."""
+        if not y.is_cuda or not y_hat.is_cuda:
+            raise MixganHipError("MultiPeriodDiscriminator: tensors must be on the GPU (no CPU fallback)")
+        B = y.shape[0]
+        both = torch.cat([y, y_hat], 0)
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        for d in self.discriminators:
+            out, fmap = d(both)
+            y_d_rs.append(out[:B])
+            y_d_gs.append(out[B:])
+            fmap_rs.append([f[:B] for f in fmap])
+            fmap_gs.append([f[B:] for f in fmap])
         return y_d_rs, y_d_gs, fmap_rs, fmap_gs

@@ -740,3 +740,76 @@ def reflect_pad1d_bwd(dy, p):
     dx = torch.empty(N, C, max(Tp - 2 * p, 0), device=dy.device, dtype=torch.float32)
     check(_lib.lib().mg_reflect_pad1d_bwd(fptr(dy), fptr(dx), N * C, Tp - 2 * p, p, stream_ptr()))
     return dx
+
+
+# ---- HiFi-GAN multi-period discriminator (csrc/mpd.hip): one layer at a time on the slotted flat axis
+def period_geometry(T, p):
+    """(H[0..6], S[0..6]) of DiscriminatorP(p) on T samples (mg_period_geometry, the one source of these numbers)."""
+    H, S = (ctypes.c_int * 7)(), (ctypes.c_int * 7)()
+    rc = _lib.lib().mg_period_geometry(int(T), int(p), H, S)
+    if rc != 0:
+        raise _lib.MixganHipError("DiscriminatorP(%d): %d samples do not fold (the reflect pad needs T > p - 1 - (T - 1) %% p)"
+                                  % (p, T))
+    return list(H), list(S)
+
+
+def period_fold_fwd(y, p):
+    """y [N, 1, T] -> the slotted layer-0 input [1, 1, N p S0]."""
+    N, _, T = y.shape
+    _, S = period_geometry(T, p)
+    out = torch.empty(1, 1, N * p * S[0], device=y.device, dtype=torch.float32)
+    check(_lib.lib().mg_period_fold_fwd(fptr(y), fptr(out), N, T, p, stream_ptr()))
+    return out
+
+
+def period_fold_bwd(din0, N, T, p):
+    dy = torch.empty(N, 1, T, device=din0.device, dtype=torch.float32)
+    check(_lib.lib().mg_period_fold_bwd(fptr(din0), fptr(dy), N, T, p, stream_ptr()))
+    return dy
+
+
+def _period_scratch(x, split):
+    if split and os.environ.get("MG_CONV_SPLIT", "1") != "0" and not torch.cuda.is_current_stream_capturing():
+        return split_scratch(x.device)
+    return None
+
+
+def period_conv_fwd(x, w, bias, R, S_in, S_out, H_out, stride, slope=None, split=True):
+    """One layer: x [1, Ci, R S_in] slotted, w [Co, Ci, K] -> [1, Co, R S_out] slotted (slack exactly 0), leaky ReLU with
+    `slope` (None: no activation)."""
+    Co, Ci, K = w.shape
+    Lin = x.shape[2]
+    out = torch.empty(1, Co, R * S_out, device=x.device, dtype=torch.float32)
+    scratch = _period_scratch(x, split)
+    check(_lib.lib().mg_period_conv_fwd(fptr(x), fptr(pack_conv_weight(w, PACK_PLAIN)), fptr(bias, True), fptr(out), R, Ci,
+                                        Lin, S_in, Co, R * S_out, S_out, H_out, K, stride,
+                                        _lib.MG_ACT_NONE if slope is None else _lib.MG_ACT_LRELU,
+                                        0.0 if slope is None else float(slope), fptr(scratch, True),
+                                        0 if scratch is None else scratch.numel(), stream_ptr()))
+    return out
+
+
+def period_dgrad3_pack(w):
+    """[Co, Ci, 5] -> the two-tap polyphase pack of the stride-3 data gradient."""
+    L = _lib.lib()
+    w = w.detach().contiguous()
+    Co, Ci, K = w.shape
+    n = L.mg_period_dgrad3_packed_floats(Co, Ci) if K == 5 else 0
+    if n == 0:
+        raise _lib.MixganHipError("unsupported period conv weight shape %s" % (tuple(w.shape),))
+    out = torch.empty(n, device=w.device, dtype=torch.float32)
+    check(L.mg_period_dgrad3_pack(fptr(w), fptr(out), Co, Ci, stream_ptr()))
+    return out
+
+
+def period_conv_dgrad(d, w, R, S_in, H_in, S_out, stride, map=None, add=None, slope=1.0, split=True):
+    """(data gradient of period_conv_fwd + add) * (map > 0 ? 1 : slope), slack exactly 0: d [1, Co, R S_out] ->
+    [1, Ci, R S_in]."""
+    Co, Ci, K = w.shape
+    packed = period_dgrad3_pack(w) if stride == 3 else pack_conv_weight(w, PACK_DGRAD)
+    dx = torch.empty(1, Ci, R * S_in, device=d.device, dtype=torch.float32)
+    scratch = _period_scratch(d, split)
+    check(_lib.lib().mg_period_conv_dgrad(fptr(d), fptr(packed), fptr(map, True), fptr(add, True), fptr(dx), R, Ci,
+                                          R * S_in, S_in, H_in, Co, d.shape[2], S_out, K, stride, float(slope),
+                                          fptr(scratch, True), 0 if scratch is None else scratch.numel(), stream_ptr()))
+    return dx

@@ -16,8 +16,8 @@ one buffer and the 1/3 is folded into the next convolution (leaky ReLU is positi
 The network is walked in one place, Generator._walk, with one of two site sets: _Infer (`forward`: no_grad, cached packs,
 post-activations fused into epilogues) or _Train (`forward_train`: autograd Functions that keep each pre-activation and
 differentiate in csrc/vocoder_train.hip; weight norm stays a torch expression).  vocoder_train's trainers put HiFi-GAN's
-mel loss and the full GAN step on forward_train (the multi-scale discriminator is native, hifigan_discriminators.py; the
-multi-period one is still a torch module).
+mel loss and the full GAN step on forward_train (both discriminators are native, hifigan_discriminators.py: the
+multi-scale one on csrc/msd.hip, the multi-period one on csrc/mpd.hip).
 """
 import math
 

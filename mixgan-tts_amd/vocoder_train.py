@@ -4,8 +4,8 @@ loads.  The two trainers share the optimizer rule, the mel-L1 term and the check
 
 GeneratorTrainer trains on the mel term alone.  VocoderGANTrainer is HiFi-GAN's full step: the discriminator phase and
 the generator phase with the adversarial and feature-matching terms (losses.hifigan_*: the fused HIP loss kernels), over
-any discriminator modules with the published calling convention.  The multi-scale discriminator is native
-(hifigan_discriminators.MultiScaleDiscriminator); the multi-period one is not yet: it is an ordinary torch module.
+any discriminator modules with the published calling convention.  Both of HiFi-GAN's are native
+(hifigan_discriminators.MultiScaleDiscriminator and MultiPeriodDiscriminator); a torch module with the same forward works too.
 
 Both trainers need only .parameters(), .forward_train(mel[, taps]) and .state_dict() of their generator, so a
 melgan.MelVocoder trains in them as a vocoder.Generator does; export_melgan_generator writes what get_vocoder loads for
