@@ -693,6 +693,17 @@ int mg_attention_fwd(const float *qkv, const uint8_t *key_pad, float *out, int B
  * accumulation, softmax statistics and I/O): BASELINE configs[4]'s "fp16 MFMA attention path" for L = 4000. */
 int mg_attention_fwd_f16(const float *qkv, const uint8_t *key_pad, float *out, int B, int L, int n_head,
                      int d_head, float scale, void *stream);
+/* The form mg_attention_fwd (f16 == 0) or mg_attention_fwd_f16 (f16 != 0) launches for these sizes; both switch on it.
+ * fp32: MG_ATTN_KSPLIT128 while the 128-query workgroups would number fewer than 512, else MG_ATTN_WIDE256 while the
+ * 256-query workgroups number at least 512, else MG_ATTN_PLAIN128.  MG_ATTENTION_KSPLIT=0|1|2 pins the first choice
+ * (0 never, 1 MG_ATTN_KSPLIT64, 2 MG_ATTN_KSPLIT128) and MG_ATTENTION_WIDE=0|1 the second; both are read on every call
+ * and any other value is ignored.  fp16 operands: only MG_ATTN_PLAIN128 and MG_ATTN_WIDE256 exist and only
+ * MG_ATTENTION_WIDE is read.  MG_ERR_SHAPE for a size that is not positive. */
+#define MG_ATTN_PLAIN128 0  /* 128 queries per workgroup, 4 waves */
+#define MG_ATTN_KSPLIT64 1  /* 64 queries, 4 waves: wave pairs split the keys of every tile */
+#define MG_ATTN_KSPLIT128 2 /* 128 queries, 8 waves: four query groups x two key halves */
+#define MG_ATTN_WIDE256 3   /* 256 queries, 8 waves */
+int mg_attention_form(int B, int L, int n_head, int f16);
 /* Post-LayerNorm on the channel-major layout (SubLayers.py:55,91 + Layers.py:25,28):
  * out[b,c,l] = pad[b,l] ? 0 : LN_c(a[b,:,l] + res[b,:,l]) * gamma[c] + beta[c];  C must be 256. */
 int mg_layernorm_cm_fwd(const float *a, const float *res, const float *gamma, const float *beta,
@@ -725,16 +736,20 @@ int mg_rel_coef(const int64_t *dur, const int64_t *dur_len, const uint8_t *mask,
  * Windowed relative-position self-attention (model/blocks.py:1016-1123, heads_share=True):
  * qkv [B, 3*H*D, L] channel-major (q, k, v stacked), valid uint8 [B,L] (1 = valid), emb_k / emb_v
  * [2*window+1, D] -> out [B, H*D, L] (before conv_o).  Scores masked with -1e4 where valid[i]*valid[j] == 0,
- * so padded queries come out finite (the reference's uniform rows).  D must be 128, window <= 8, L <= 2900. */
+ * so padded queries come out finite (the reference's uniform rows).  D must be 128, window <= 8, L <= 2895. */
 int mg_rel_attention_fwd(const float *qkv, const uint8_t *valid, const float *emb_k, const float *emb_v, float *out,
                          int B, int L, int n_head, int d_head, int window, void *stream);
 /* Word-to-phoneme attention (model/blocks.py:695-768): q [B, H*D, Lq], kv [B, 2*H*D, Lk] (k then v) channel-major;
  * key_valid [B,Lk], query_valid [B,Lq], mapping [B,Lq,Lk] uint8; prior [B,Lk,Lq] or NULL (helper_type "ctc").
  * Writes out [B, H*D, Lq] and the head-major [H, B, Lq, Lk] tensors attn (= attn_raw * mapping), attn_raw
- * (= softmax * query mask) and logprob (the scores, -inf at padded keys).  D must be 128, Lk <= 2900. */
+ * (= softmax * query mask) and logprob (the scores, -inf at padded keys).  D must be 128, Lk <= 2895. */
 int mg_w2p_attention_fwd(const float *q, const float *kv, const uint8_t *key_valid, const uint8_t *query_valid,
                          const uint8_t *mapping, const float *prior, float *out, float *attn, float *attn_raw,
                          float *logprob, int B, int Lq, int Lk, int n_head, int d_head, void *stream);
+/* Query rows per workgroup of the three attentions above (mg_rel_attention_fwd, mg_rel_attention_train_fwd,
+ * mg_w2p_attention_fwd; their launcher switches on it) for Lk keys: 16 while 16 score rows fit the 64 KiB of dynamic
+ * LDS (Lk <= 615), else 4 (Lk <= 2895), else 0: those entry points return MG_ERR_SHAPE.  0 for Lk <= 0. */
+int mg_le_attention_rows(int Lk);
 /* nn.Embedding into channel-major: out[b,c,l] = valid[b,l] ? table[ids[b,l], c] : 0 (table [n_rows, C]). */
 int mg_embed_cm(const int64_t *ids, const float *table, const uint8_t *valid, float *out, int B, int L, int C,
                 int n_rows, void *stream);

@@ -39,6 +39,7 @@ MG_ALIGN_MAX_D, MG_ALIGN_MAX_G, MG_ALIGN_MAX_S, MG_ALIGN_MAX_T = 128, 1024, 2048
 MG_CEPSTRA_MAX_M, MG_DTW_MAX_T, MG_DTW_MAX_D = 128, 4096, 64
 MG_GCONV_FWD, MG_GCONV_DGRAD = 0, 1                                               # mg_gconv_pack modes
 MG_LOSSMODE_MSE, MG_LOSSMODE_L1, MG_LOSSMODE_HINGE, MG_LOSSMODE_MEAN = range(4)    # MgLossTerm.mode
+MG_ATTN_PLAIN128, MG_ATTN_KSPLIT64, MG_ATTN_KSPLIT128, MG_ATTN_WIDE256 = range(4)  # mg_attention_form
 
 
 class LossTerm(ctypes.Structure):
@@ -169,6 +170,7 @@ def _signatures():
         "mg_mel_count_rows": (i, [vp, vp, i, i, vp, vp]),
         "mg_attention_fwd": (i, [vp, vp, vp, i, i, i, i, f, vp]),
         "mg_attention_fwd_f16": (i, [vp, vp, vp, i, i, i, i, f, vp]),
+        "mg_attention_form": (i, [i, i, i, i]),
         "mg_layernorm_cm_fwd": (i, [vp, vp, vp, vp, vp, vp, i, i, i, f, vp]),
         "mg_length_regulate_fwd": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_length_regulate_bwd": (i, [vp, vp, vp, i, i, i, i, vp]),
@@ -178,6 +180,7 @@ def _signatures():
         "mg_rel_coef": (i, [vp, vp, vp, vp, i, i, i, vp]),
         "mg_rel_attention_fwd": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
         "mg_w2p_attention_fwd": (i, [vp] * 10 + [i, i, i, i, i, vp]),
+        "mg_le_attention_rows": (i, [i]),
         "mg_embed_cm": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
         "mg_variance_head": (i, [vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, i, i, i, vp]),
         "mg_duration_head": (i, [vp, vp, vp, vp, f, vp, vp, i, i, i, i, vp]),

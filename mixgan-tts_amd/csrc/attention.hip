@@ -438,12 +438,30 @@ __global__ __launch_bounds__(NWQ * 64, 2) void attention_fwd_f16_kernel(const fl
     }
 }
 
-// 256-query workgroups (8 waves) when they still number two per CU; MG_ATTENTION_WIDE=0/1 pins the choice (tests)
-static bool attention_wide(int L, int n_head, int B)
+// The one place the kernel's form is chosen (mg_attention_fwd and mg_attention_fwd_f16 switch on it).
+// fp32: fewer than 512 workgroups of 128 queries (two per CU) -> MG_ATTN_KSPLIT128: 128-query workgroups of 8 waves, four
+// query groups x two key halves -- two waves per SIMD from ONE workgroup per CU, at the staging cost of the plain form;
+// else 256-query workgroups (8 waves) when they still number 512 -> MG_ATTN_WIDE256; else MG_ATTN_PLAIN128.
+// MG_ATTENTION_KSPLIT pins the first choice (tests pin each form): 0 = never, 1 = MG_ATTN_KSPLIT64 (64-query workgroups,
+// 4 waves), 2 = MG_ATTN_KSPLIT128.  MG_ATTENTION_WIDE=0/1 pins the second.  Both are read on every call; any other value
+// is ignored.  The fp16 kernel has no key-split form and does not read MG_ATTENTION_KSPLIT.
+static int attention_pin(const char *name, int top)
 {
-    const char *e = std::getenv("MG_ATTENTION_WIDE");
-    if (e) return e[0] == '1';
-    return (long)mg_cdiv(L, 256) * n_head * B >= 512;
+    const char *e = std::getenv(name);
+    return e && e[0] >= '0' && e[0] <= '0' + top && e[1] == 0 ? e[0] - '0' : -1;
+}
+
+extern "C" int mg_attention_form(int B, int L, int n_head, int f16)
+{
+    if (B <= 0 || L <= 0 || n_head <= 0) return MG_ERR_SHAPE;
+    if (!f16) {
+        const int pin = attention_pin("MG_ATTENTION_KSPLIT", 2);
+        const int ksplit = pin >= 0 ? pin : ((long)mg_cdiv(L, 128) * n_head * B < 512 ? 2 : 0);
+        if (ksplit) return ksplit == 1 ? MG_ATTN_KSPLIT64 : MG_ATTN_KSPLIT128;
+    }
+    const int pin = attention_pin("MG_ATTENTION_WIDE", 1);
+    const bool wide = pin >= 0 ? pin == 1 : (long)mg_cdiv(L, 256) * n_head * B >= 512;
+    return wide ? MG_ATTN_WIDE256 : MG_ATTN_PLAIN128;
 }
 
 extern "C" int mg_attention_fwd_f16(const float *qkv, const uint8_t *key_pad, float *out, int B, int L, int n_head,
@@ -453,7 +471,7 @@ extern "C" int mg_attention_fwd_f16(const float *qkv, const uint8_t *key_pad, fl
     if (B <= 0 || L <= 0 || n_head <= 0 || d_head != AT_D) return MG_ERR_SHAPE;
     const bool vec = (L % 4 == 0) && (((uintptr_t)qkv & 15) == 0);
     hipStream_t st = (hipStream_t)stream;
-    if (attention_wide(L, n_head, B)) {   // 256-query workgroups
+    if (mg_attention_form(B, L, n_head, 1) == MG_ATTN_WIDE256) {
         dim3 grid(mg_cdiv(L, 256), n_head, B);
         if (vec) hipLaunchKernelGGL((attention_fwd_f16_kernel<true, 8>), grid, dim3(512), 0, st, qkv, key_pad, out, L, n_head, scale);
         else hipLaunchKernelGGL((attention_fwd_f16_kernel<false, 8>), grid, dim3(512), 0, st, qkv, key_pad, out, L, n_head, scale);
@@ -472,21 +490,17 @@ extern "C" int mg_attention_fwd(const float *qkv, const uint8_t *key_pad, float 
     if (!qkv || !out) return MG_ERR_ARG;
     if (B <= 0 || L <= 0 || n_head <= 0 || d_head != AT_D) return MG_ERR_SHAPE;
     const bool vec = (L % 4 == 0) && (((uintptr_t)qkv & 15) == 0);
-    // fewer than two 128-query workgroups per CU: 64-query workgroups that split the keys between wave pairs
-    const char *ke = std::getenv("MG_ATTENTION_KSPLIT");   // tests pin each form
-    // MG_ATTENTION_KSPLIT: 0 = never, 1 = 64-query workgroups (4 waves), 2 = 128-query workgroups (8 waves: four query
-    // groups x two key halves -- two waves per SIMD from ONE workgroup per CU, at the staging cost of the plain form)
-    const int ksplit = ke ? ke[0] - '0' : ((long)mg_cdiv(L, 128) * n_head * B < 512 ? 2 : 0);
-    dim3 grid(mg_cdiv(L, ksplit == 1 ? 64 : 128), n_head, B);
+    const int form = mg_attention_form(B, L, n_head, 0);
+    dim3 grid(mg_cdiv(L, form == MG_ATTN_KSPLIT64 ? 64 : 128), n_head, B);
     hipStream_t st = (hipStream_t)stream;
-    if (!ksplit && attention_wide(L, n_head, B)) {
+    if (form == MG_ATTN_WIDE256) {
         dim3 wgrid(mg_cdiv(L, 256), n_head, B);
         if (vec) hipLaunchKernelGGL((attention_fwd_kernel<true, false, 8>), wgrid, dim3(512), 0, st, qkv, key_pad, out, L, n_head, scale);
         else hipLaunchKernelGGL((attention_fwd_kernel<false, false, 8>), wgrid, dim3(512), 0, st, qkv, key_pad, out, L, n_head, scale);
-    } else if (ksplit == 2) {
+    } else if (form == MG_ATTN_KSPLIT128) {
         if (vec) hipLaunchKernelGGL((attention_fwd_kernel<true, true, 8>), grid, dim3(512), 0, st, qkv, key_pad, out, L, n_head, scale);
         else hipLaunchKernelGGL((attention_fwd_kernel<false, true, 8>), grid, dim3(512), 0, st, qkv, key_pad, out, L, n_head, scale);
-    } else if (ksplit == 1) {
+    } else if (form == MG_ATTN_KSPLIT64) {
         if (vec) hipLaunchKernelGGL((attention_fwd_kernel<true, true>), grid, dim3(256), 0, st, qkv, key_pad, out, L, n_head, scale);
         else hipLaunchKernelGGL((attention_fwd_kernel<false, true>), grid, dim3(256), 0, st, qkv, key_pad, out, L, n_head, scale);
     } else {

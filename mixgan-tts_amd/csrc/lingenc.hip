@@ -199,6 +199,16 @@ __global__ __launch_bounds__(256) void le_attention_kernel(
     }
 }
 
+// The one place the kernel's form is chosen (le_attention_launch switches on it): 16 query rows per workgroup while
+// their score rows fit LE_LDS_MAX (Lk <= 615), else 4 (Lk <= 2895), else 0: no form, MG_ERR_SHAPE.
+extern "C" int mg_le_attention_rows(int Lk)
+{
+    if (Lk <= 0) return 0;
+    if (le_lds_bytes(16, Lk) <= LE_LDS_MAX) return 16;
+    if (le_lds_bytes(4, Lk) <= LE_LDS_MAX) return 4;
+    return 0;
+}
+
 template <bool REL, bool TRAIN = false>
 static int le_attention_launch(const float *q, long q_bs, const float *k, const float *v, long kv_bs, int Lq, int Lk,
                                int B, int H, const uint8_t *qvalid, const uint8_t *kvalid, const float *emb_k,
@@ -206,11 +216,12 @@ static int le_attention_launch(const float *q, long q_bs, const float *k, const 
                                long out_bs, float *attn, float *attn_raw, float *logprob, hipStream_t st,
                                const uint8_t *keep = nullptr, float keep_scale = 1.f, float *psave = nullptr)
 {
-    if (le_lds_bytes(16, Lk) <= LE_LDS_MAX) {
+    const int rows = mg_le_attention_rows(Lk);
+    if (rows == 16) {
         hipLaunchKernelGGL((le_attention_kernel<REL, 16, TRAIN>), dim3(mg_cdiv(Lq, 16), H, B), dim3(256),
                            le_lds_bytes(16, Lk), st, q, q_bs, k, v, kv_bs, Lq, Lk, B, qvalid, kvalid, emb_k, emb_v, w,
                            mapping, prior, out, out_bs, attn, attn_raw, logprob, keep, keep_scale, psave);
-    } else if (le_lds_bytes(4, Lk) <= LE_LDS_MAX) {
+    } else if (rows == 4) {
         hipLaunchKernelGGL((le_attention_kernel<REL, 4, TRAIN>), dim3(mg_cdiv(Lq, 4), H, B), dim3(256),
                            le_lds_bytes(4, Lk), st, q, q_bs, k, v, kv_bs, Lq, Lk, B, qvalid, kvalid, emb_k, emb_v, w,
                            mapping, prior, out, out_bs, attn, attn_raw, logprob, keep, keep_scale, psave);

@@ -22,6 +22,39 @@ def sinusoid(n, d):
     return torch.from_numpy(t).float()
 
 
+def rel_attention_probs(qkv, valid, emb_k, n_head, w):
+    """The softmax of rel_attention, [B, H, L, L]: what mg_rel_attention_train_fwd saves.  Follows qkv's dtype."""
+    B, C3, L = qkv.shape
+    HD = C3 // 3
+    d = HD // n_head
+    q, k = [t.reshape(B, n_head, d, L).transpose(2, 3) for t in qkv.split(HD, 1)[:2]]
+    scores = q @ k.transpose(-1, -2) / math.sqrt(d)
+    i = torch.arange(L, device=qkv.device)
+    rel = i[None, :] - i[:, None] + w
+    rk = F.pad((q @ emb_k.t()) / math.sqrt(d), (0, 1))              # one more column of zeros: outside the band
+    scores += rk.gather(3, torch.where((rel >= 0) & (rel <= 2 * w), rel, 2 * w + 1).expand(B, n_head, L, L))
+    m = valid.bool()
+    scores.masked_fill_(~(m[:, None, :, None] & m[:, None, None, :]), -1e4)
+    return F.softmax(scores, -1)
+
+
+def rel_attention_apply(p, qkv, emb_v, n_head, w, keep=None, scale=1.0):
+    """P.V + sum over the band of P[i,j] E_v[j-i+w] with P = dropout(p) (BL:1059: keep [B, H, L, L] 1 = kept, times
+    scale) -> [B, HD, L]."""
+    B, C3, L = qkv.shape
+    HD = C3 // 3
+    v = qkv[:, 2 * HD:].reshape(B, n_head, HD // n_head, L).transpose(2, 3)
+    if keep is not None:
+        p = p * keep.to(p.dtype) * scale
+    out = p @ v
+    i = torch.arange(L, device=qkv.device)
+    for m in range(2 * w + 1):                                       # diagonal j = i + m - w of P, times E_v[m]
+        lo, hi = max(0, w - m), min(L, L + w - m)
+        if lo < hi:
+            out[:, :, lo:hi] += p[:, :, i[lo:hi], i[lo:hi] + m - w][..., None] * emb_v[m]
+    return out.transpose(2, 3).reshape(B, HD, L)
+
+
 def rel_attention(qkv, valid, emb_k, emb_v, n_head, w):
     """BL:1016-1061 on qkv [B, 3HD, L]: scores q.k/sqrt(d) + q.E_k[j-i+w]/sqrt(d) inside the band, -1e4 where
     valid[i]*valid[j] == 0, softmax over all keys, P.V + sum over the band of P[i,j] E_v[j-i+w]."""
@@ -102,6 +135,48 @@ def variance_predictor(sd, p, x, mask):
     h = _conv(h.transpose(1, 2), sd, c + "conv1d_2.conv", 3)
     h = F.layer_norm(h.transpose(1, 2), (h.shape[1],), sd[c + "layer_norm_2.weight"], sd[c + "layer_norm_2.bias"])
     return F.linear(h, sd[p + "linear_layer.weight"], sd[p + "linear_layer.bias"]).squeeze(-1) * mask
+
+
+# ---- the per-token glue kernels of csrc/lingenc.hip, one restatement each; every one follows its input's dtype
+def embed_cm(ids, table, valid, skip_row=-1):
+    """mg_embed_cm: [B, C, L] = table[ids] where valid and 0 <= id < n_rows, else zero rows (and, for the gradient of
+    mg_embed_cm_bwd, nothing through row skip_row: nn.Embedding's padding_idx)."""
+    n = table.shape[0]
+    ok = valid.bool() & (ids >= 0) & (ids < n) & (ids != skip_row)
+    rows = table[ids.clamp(0, n - 1)]
+    return torch.where(ok[:, :, None], rows, torch.zeros((), dtype=table.dtype)).transpose(1, 2)
+
+
+def variance_head(h, weight, bias, valid, control, target, bins):
+    """mg_variance_head (LE:163-183, 473-478) on h [B, C, L] -> (pred [B, L], bucket [B, L]): pred = (w . h + b) * valid
+    (* control without a target); bucket = torch.bucketize(target or pred, bins), right=False: the number of bins strictly
+    below the value."""
+    pred = (torch.einsum("c,bcl->bl", weight.reshape(-1), h) + bias) * valid.to(h.dtype)
+    if target is None:
+        pred = pred * control
+    val = pred if target is None else target.to(h.dtype)
+    return pred, (bins.to(h.dtype)[None, None, :] < val[:, :, None]).sum(-1)
+
+
+def duration_head(logp, target, wb, src_w_len, d_control, W):
+    """mg_duration_head (LE:294-316) -> (log_w [B, W], dur int64 [B, W]): log of the word sum of exp(logp) (-inf for
+    words with no phoneme or past src_w_len); dur the word sum of the integer target, or
+    long(clamp(round(exp(log_w) - 1) * d_control, min=0))."""
+    logw = word_pool(logp.exp()[:, :, None], wb, src_w_len, W, False).log().squeeze(-1)
+    if target is not None:
+        return logw, word_pool(target.double()[:, :, None], wb, src_w_len, W, False).squeeze(-1).round().long()
+    return logw, torch.clamp(torch.round(torch.exp(logw) - 1) * d_control, min=0).long()
+
+
+def posenc_add(x, rowmajor, coef, table):
+    """mg_posenc_add (LE:201-220) -> [B, C, L] = x + coef[:, :, None] * table[:L]; x [B, L, C] when rowmajor."""
+    L = coef.shape[1]
+    y = x if rowmajor else x.transpose(1, 2)
+    return (y + coef[:, :, None] * table[:L]).transpose(1, 2)
+
+
+def dropout_apply(x, keep, scale):
+    return torch.where(keep.bool(), x * scale, torch.zeros((), dtype=x.dtype))
 
 
 def word_index(wb, Tp):

@@ -161,6 +161,74 @@ def test_bgemm_tile_choice_and_pin(monkeypatch):
             assert L.mg_bgemm_tile(*args) == tile, (junk, args)
 
 
+def test_le_attention_rows_thresholds():
+    """mg_le_attention_rows: 16 query rows per workgroup while le_lds_bytes(16, Lk) fits the 64 KiB of dynamic LDS, else
+    4, else 0.  The formula of csrc/lingenc.hip is restated here; both upper edges reach the limit exactly."""
+    L = mg.lib()
+    D, VCH, WMAX, LDS_MAX = 128, 32, 8, 64 * 1024
+
+    def lds_bytes(rows, Lk):        # q rows, score rows, one V chunk, the relative-key dots
+        return 4 * (rows * D + rows * Lk + D * (VCH + 1) + rows * (2 * WMAX + 1))
+    assert lds_bytes(16, 615) == LDS_MAX and lds_bytes(4, 2895) == LDS_MAX
+    for Lk, rows in ((615, 16), (616, 4), (2895, 4), (2896, 0), (0, 0), (-1, 0), (-2 ** 31, 0), (1, 16), (2 ** 31 - 1, 0)):
+        assert L.mg_le_attention_rows(Lk) == rows, Lk
+    for Lk in range(1, 3000):
+        want = 16 if lds_bytes(16, Lk) <= LDS_MAX else 4 if lds_bytes(4, Lk) <= LDS_MAX else 0
+        assert L.mg_le_attention_rows(Lk) == want, Lk
+
+
+def test_attention_form_choice_and_pins(monkeypatch):
+    """mg_attention_form: the key-split form of 128 queries while the 128-query workgroups would number fewer than 512,
+    the 256-query form while its workgroups number at least 512, else the plain one; MG_ATTENTION_KSPLIT / _WIDE pin
+    either choice, are read on every call, and any other value is ignored.  fp16 operands: plain or wide only."""
+    L = mg.lib()
+    PLAIN, KS64, KS128, WIDE = _lib.MG_ATTN_PLAIN128, _lib.MG_ATTN_KSPLIT64, _lib.MG_ATTN_KSPLIT128, _lib.MG_ATTN_WIDE256
+    assert (PLAIN, KS64, KS128, WIDE) == (0, 1, 2, 3)
+    for v in ("MG_ATTENTION_KSPLIT", "MG_ATTENTION_WIDE"):
+        monkeypatch.delenv(v, raising=False)
+    # (B, L, n_head) -> (fp32 form, fp16 form)
+    cases = [((16, 1000, 2), KS128, PLAIN),      # 8 * 32 = 256 workgroups of 128 queries
+             ((16, 4000, 2), WIDE, WIDE),        # 16 * 32 = 512 workgroups of 256 queries: the threshold itself
+             ((16, 3840, 2), PLAIN, PLAIN),      # 480 wide workgroups, 960 plain ones
+             ((16, 3841, 2), WIDE, WIDE),        # 16 wide tiles again
+             ((16, 2048, 2), PLAIN, PLAIN),      # exactly 512 plain workgroups
+             ((16, 2047, 2), PLAIN, PLAIN),      # the same count
+             ((16, 1921, 2), PLAIN, PLAIN),
+             ((16, 1920, 2), KS128, PLAIN),      # 15 * 32 = 480
+             ((2, 1, 3), KS128, PLAIN), ((2, 700, 3), KS128, PLAIN)]
+    for args, f32, f16 in cases:
+        assert L.mg_attention_form(*args, 0) == f32, args
+        assert L.mg_attention_form(*args, 1) == f16, args
+    # every pin, at every size
+    for ks, wide, f32 in (("0", "0", PLAIN), ("0", "1", WIDE), ("1", "0", KS64), ("1", "1", KS64), ("2", "0", KS128),
+                          ("2", "1", KS128)):
+        monkeypatch.setenv("MG_ATTENTION_KSPLIT", ks)
+        monkeypatch.setenv("MG_ATTENTION_WIDE", wide)
+        for args, _, _ in cases:
+            assert L.mg_attention_form(*args, 0) == f32, (ks, wide, args)
+            assert L.mg_attention_form(*args, 1) == (WIDE if wide == "1" else PLAIN), (ks, wide, args)
+    # one pin alone: the other choice stays with the rule
+    monkeypatch.delenv("MG_ATTENTION_WIDE")
+    monkeypatch.setenv("MG_ATTENTION_KSPLIT", "0")
+    for args, f32, f16 in cases:
+        assert L.mg_attention_form(*args, 0) == f16, args       # without the key split fp32 follows the fp16 rule
+        assert L.mg_attention_form(*args, 1) == f16, args
+    monkeypatch.delenv("MG_ATTENTION_KSPLIT")
+    monkeypatch.setenv("MG_ATTENTION_WIDE", "1")
+    for args, f32, _ in cases:
+        assert L.mg_attention_form(*args, 0) == (f32 if f32 == KS128 else WIDE), args
+        assert L.mg_attention_form(*args, 1) == WIDE, args
+    # anything else is ignored
+    for junk in ("", "3", "9", "-1", "01", "2 ", "1x", "yes"):
+        monkeypatch.setenv("MG_ATTENTION_KSPLIT", junk)
+        monkeypatch.setenv("MG_ATTENTION_WIDE", junk if junk != "01" else "10")
+        for args, f32, f16 in cases:
+            assert L.mg_attention_form(*args, 0) == f32, (junk, args)
+            assert L.mg_attention_form(*args, 1) == f16, (junk, args)
+    for bad in ((0, 4, 2), (2, 0, 2), (2, 4, 0), (-1, 4, 2)):
+        assert L.mg_attention_form(*bad, 0) == _lib.MG_ERR_SHAPE and L.mg_attention_form(*bad, 1) == _lib.MG_ERR_SHAPE
+
+
 def test_schedule_matches_reference_bits():
     g = golden("schedule")
     for mode, T in [("vpsde", 1), ("vpsde", 4), ("vpsde", 100), ("vpsde", 1000), ("linear", 4), ("cosine", 4)]:
