@@ -246,11 +246,22 @@ typedef struct {
 #define MG_FWD_SAVE 1     /* keep per-layer activations for mg_denoiser_bwd (fp32 path only) */
 #define MG_FWD_SPLIT 2    /* residual-layer GEMMs as 3-term bf16-split MFMA products (fp32-grade, ~1e-5) */
 #define MG_FWD_P16 4      /* `packed` was built with MG_DEN_P16: small launches may use the 16-frame tile width */
+/* Accepted models: 1 <= n_layers <= 256, channels a multiple of 64, cond_channels a multiple of 32, mel_bins >= 1
+ * (MG_ERR_SHAPE otherwise).  MG_DEN_SPLIT and MG_DEN_P16 exist for channels == cond_channels == 256 only: for any other
+ * model mg_denoiser_packed_floats answers 0 and mg_denoiser_pack MG_ERR_SHAPE, before it queues or launches anything. */
 size_t mg_denoiser_packed_floats(const mg_denoiser_dims *d, int flags);
 /* freq: the C/2 step-embedding frequencies exp(-i ln(1e4)/(C/2-1)) (model/blocks.py:909-910),
- * computed by the host exactly as the reference does and cached in the packed blob. */
+ * computed by the host exactly as the reference does and cached in the packed blob.
+ * The pack is a list of jobs (9 + 7 or 8 per layer, 3 + 3 per layer more with MG_DEN_BACKWARD, 3 + 5 per layer more with
+ * MG_DEN_P16) executed from a 768-entry table in the blob's tail: one upload and one launch per 768 jobs, so every
+ * accepted n_layers packs.  MG_DEN_JOBS_RESIDENT is honoured for a list of at most 768 jobs and ignored for a longer one. */
 int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *weights, const float *freq,
                      float *packed, int flags, void *stream);
+/* The host half of mg_denoiser_pack alone -- the same checks over the same arguments and the same job list, no device
+ * call, no pointer dereferenced but the table itself: the code mg_denoiser_pack would return before its first upload,
+ * and, when MG_OK, how many jobs it queues and in how many launches it runs them (either may be NULL). */
+int mg_denoiser_pack_plan(const mg_denoiser_dims *d, const float *const *weights, const float *freq,
+                          const float *packed, int flags, int *jobs, int *launches);
 /* Workspace (floats) for a forward of batch B, L frames.  save_for_backward additionally keeps the
  * per-layer activations that mg_denoiser_bwd consumes. */
 size_t mg_denoiser_workspace_floats(const mg_denoiser_dims *d, int B, int L, int save_for_backward);

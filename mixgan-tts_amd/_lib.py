@@ -139,6 +139,7 @@ def _signatures():
         "mg_conv1d_wgrad_grouped_bias": (i, [vp, lg, lg, vp, lg, lg, vp, lg, vp, lg, vp, i, i, i, i, i, i, i, i, i, f, i, vp]),
         "mg_denoiser_packed_floats": (sz, [dp, i]),
         "mg_denoiser_pack": (i, [dp, vp, vp, vp, i, vp]),
+        "mg_denoiser_pack_plan": (i, [dp, vp, vp, vp, i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         "mg_denoiser_bwd_workspace_floats": (sz, [dp, i, i]),
         "mg_denoiser_bwd": (i, [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, i, i, vp]),
         "mg_denoiser_bwd_staged": (i, [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, i, i, vp, vp]),

@@ -144,7 +144,7 @@ struct EpiResSkip {
 extern "C" size_t mg_denoiser_packed_floats(const mg_denoiser_dims *d, int flags)
 {
     if (den_check(d) != MG_OK) return 0;
-    if ((flags & MG_DEN_SPLIT) && (d->channels != RB_C || d->cond_channels != RB_C)) return 0;
+    if ((flags & (MG_DEN_SPLIT | MG_DEN_P16)) && (d->channels != RB_C || d->cond_channels != RB_C)) return 0;
     return den_layout(d, flags).total;
 }
 
@@ -197,37 +197,46 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const PackJob *__restri
     }
 }
 
-#define MG_DEN_MAX_JOBS 768
+#define MG_DEN_MAX_JOBS 768   // entries of the device-side table (den_layout reserves them): one launch takes that many
 static_assert(sizeof(PackJob) <= 96, "den_layout reserves 96 bytes per pack job");
 
-extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w, const float *freq, float *packed,
-                                int flags, void *stream)
+// The pack's host half (every check and the whole job list) and, unless `dry`, its device half: the list goes to the
+// device MG_DEN_MAX_JOBS jobs at a time, one table upload and one launch per chunk, all through the same reserved
+// slice (stream order keeps a chunk's table in place until its kernel has read it).  A model within den_check's
+// bounds has up to 9 + 14 * 256 jobs; the 20-layer model has 292 and stays one launch.
+static int den_pack(const mg_denoiser_dims *d, const float *const *w, const float *freq, float *packed, int flags,
+                    void *stream, bool dry, int *jobs_out, int *launches_out)
 {
     MG_TRY(den_check(d));
     if (!w || !packed || !freq) return MG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int C = d->channels, H = d->cond_channels, M = d->mel_bins;
     const int with_backward = flags & MG_DEN_BACKWARD;
+    // what only the 256-channel kernels read is refused for other models before anything is queued or launched
+    // (mg_denoiser_packed_floats answers 0 for MG_DEN_SPLIT there: the caller's buffer has no such sections)
+    if ((flags & (MG_DEN_P16 | MG_DEN_SPLIT)) && (C != RB_C || H != RB_C)) return MG_ERR_SHAPE;
     const DenLayout o = den_layout(d, flags);
     for (int i = 0; i < MG_DEN_HEAD_PTRS; ++i)
         if (!w[i]) return MG_ERR_ARG;
 
     auto layer = [&](int l) { return w + MG_DEN_HEAD_PTRS + (size_t)l * MG_DEN_LAYER_PTRS; };
+    // every layer's pointers before the first job: with more than one chunk a later layer's would be met after a launch
+    for (int l = 0; l < d->n_layers; ++l)
+        for (int j = MG_DEN_L_CONV_W; j <= (d->multi_speaker ? MG_DEN_L_SPK_W : MG_DEN_L_OUT_B); ++j)
+            if (!layer(l)[j]) return MG_ERR_ARG;
 
-    static thread_local PackJob jobs[MG_DEN_MAX_JOBS];
-    int n = 0;
-    unsigned blocks = 0;
+    static thread_local std::vector<PackJob> jobs;   // (never reused within a call: a chunk's upload may still read it)
+    jobs.clear();
     int rc = MG_OK;
     auto push = [&](const float *src, size_t dst, size_t total, const PackDesc &pd) {
-        if (!src || n >= MG_DEN_MAX_JOBS) {
+        if (!src) {
             rc = MG_ERR_ARG;
             return;
         }
         unsigned nb = (unsigned)((total + 255) / 256);
         if (nb > 512) nb = 512;   // grid-stride inside the job beyond that
         if (nb < 1) nb = 1;
-        jobs[n++] = PackJob{src, dst, total, pd, blocks, nb};
-        blocks += nb;
+        jobs.push_back(PackJob{src, dst, total, pd, 0u, nb});   // first_block: per chunk, below
     };
     auto copy = [&](size_t dst, const float *src, size_t count) {
         PackDesc pd{};
@@ -256,8 +265,6 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
     for (int l = 0; l < d->n_layers; ++l) {
         const float *const *lw = layer(l);
         const size_t lp = o.layers + (size_t)l * o.layer_stride;
-        for (int j = MG_DEN_L_CONV_W; j <= MG_DEN_L_OUT_B; ++j)   // (push rejects a missing speaker weight)
-            if (!lw[j]) return MG_ERR_ARG;
         pack(lw[MG_DEN_L_CONV_W], lp + o.l_w3, 2 * C, C, 3, MG_PACK_GATE);
         copy(lp + o.l_b3, lw[MG_DEN_L_CONV_B], 2 * C);
         copy(lp + o.l_wd, lw[MG_DEN_L_DIFF_W], (size_t)C * C);
@@ -282,7 +289,6 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
         }
     }
     if (flags & MG_DEN_P16) {
-        if (C != RB_C || H != RB_C) return MG_ERR_SHAPE;
         pack(w[MG_DEN_IN_W], o.in_w16, C, M, 1, MG_PACK_PLAIN16);
         pack(w[MG_DEN_SKIP_W], o.skip_w16, C, C, 1, MG_PACK_PLAIN16);
         pack(w[MG_DEN_OUT_W], o.out_w16, M, C, 1, MG_PACK_PLAIN16);
@@ -300,19 +306,31 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
         }
     }
     if (rc != MG_OK) return rc;
-    {
-        // the table travels in the reserved tail of the packed buffer (host memory is pageable: the runtime stages
-        // the 30 KB copy, after which `jobs` may be reused)
-        PackJob *dev_jobs = reinterpret_cast<PackJob *>(packed + o.jobs);
-        if (!(flags & MG_DEN_JOBS_RESIDENT)) {   // (a caller repacking the same tensors into the same buffer skips the copy)
-            hipError_t e = hipMemcpyAsync(dev_jobs, jobs, (size_t)n * sizeof(PackJob), hipMemcpyHostToDevice, st);
+    const size_t n = jobs.size();
+    if (jobs_out) *jobs_out = (int)n;
+    if (launches_out) *launches_out = (int)((n + MG_DEN_MAX_JOBS - 1) / MG_DEN_MAX_JOBS);
+    // the table travels in the reserved tail of the packed buffer (host memory is pageable: the runtime stages the
+    // 30 KB copy).  MG_DEN_JOBS_RESIDENT (a caller repacking the same tensors into the same buffer skips the copy)
+    // holds for a list of one chunk only: after several the slice keeps the last one's table.
+    PackJob *dev_jobs = reinterpret_cast<PackJob *>(packed + o.jobs);
+    const bool resident = (flags & MG_DEN_JOBS_RESIDENT) && n <= MG_DEN_MAX_JOBS;
+    for (size_t c0 = 0; c0 < n; c0 += MG_DEN_MAX_JOBS) {
+        const size_t cn = n - c0 < MG_DEN_MAX_JOBS ? n - c0 : MG_DEN_MAX_JOBS;
+        unsigned blocks = 0;
+        for (size_t i = 0; i < cn; ++i) {
+            jobs[c0 + i].first_block = blocks;
+            blocks += jobs[c0 + i].nblocks;
+        }
+        if (dry) continue;
+        if (!resident) {
+            hipError_t e = hipMemcpyAsync(dev_jobs, jobs.data() + c0, cn * sizeof(PackJob), hipMemcpyHostToDevice, st);
             if (e != hipSuccess) return (int)e;
         }
-        hipLaunchKernelGGL(pack_table_kernel, dim3(blocks), dim3(256), 0, st, dev_jobs, n, packed);
+        hipLaunchKernelGGL(pack_table_kernel, dim3(blocks), dim3(256), 0, st, dev_jobs, (int)cn, packed);
         MG_LAUNCH_CHECK();
     }
+    if (dry) return MG_OK;
     if (flags & MG_DEN_SPLIT) {
-        if (C != RB_C || H != RB_C) return MG_ERR_SHAPE;
         for (int l = 0; l < d->n_layers; ++l) {
             const float *const *lw = layer(l);
             float *sp = packed + o.slayers + (size_t)l * o.slayer_stride;
@@ -330,6 +348,20 @@ extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w
         }
     }
     return MG_OK;
+}
+
+extern "C" int mg_denoiser_pack(const mg_denoiser_dims *d, const float *const *w, const float *freq, float *packed,
+                                int flags, void *stream)
+{
+    return den_pack(d, w, freq, packed, flags, stream, false, nullptr, nullptr);
+}
+
+extern "C" int mg_denoiser_pack_plan(const mg_denoiser_dims *d, const float *const *w, const float *freq,
+                                     const float *packed, int flags, int *jobs, int *launches)
+{
+    if (jobs) *jobs = 0;
+    if (launches) *launches = 0;
+    return den_pack(d, w, freq, const_cast<float *>(packed), flags, nullptr, true, jobs, launches);
 }
 
 extern "C" size_t mg_denoiser_workspace_floats(const mg_denoiser_dims *d, int B, int L, int save_for_backward)

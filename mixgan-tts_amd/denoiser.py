@@ -166,6 +166,10 @@ class Denoiser(nn.Module):
         table = self._weight_table()
         if self.precision not in ("fp32", "bf16x3"):
             raise ValueError("Denoiser.precision must be 'fp32' or 'bf16x3'")
+        if self.precision == "bf16x3" and not (self._dims.channels == 256 and self._dims.cond_channels == 256):
+            raise _lib.MixganHipError(
+                "Denoiser.precision = 'bf16x3' needs channels = cond channels = 256 (this model: residual_channels %d, "
+                "encoder_hidden %d); use precision = 'fp32'" % (self._dims.channels, self._dims.cond_channels))
         # MG_DEN_* flags of the blob; the backward and split packs, once asked for, stay
         BWD, SPLIT = _lib.MG_DEN_BACKWARD, _lib.MG_DEN_SPLIT
         flags = (self._packed_key[0] & (BWD | SPLIT)) if self._packed_key is not None else 0

@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests (oracle side)."""
 import os
+import re
 import sys
 
 import numpy as np
@@ -95,6 +96,125 @@ def condition_relu_kinks(W64, x, t, cond, spk, go, band, gen, chunk=4):
         g = go[b, 0, :, l].double()
         go[b, 0, :, l] = (g - A @ torch.linalg.lstsq(A, g[:, None]).solution[:, 0]).float()
     return redrawn, len(frames)
+
+
+# Model sizes off the hand-tuned point (C = H = 256, M <= 96), DESIGN.md section 7.6: name -> (residual_layers NL,
+# residual_channels C, encoder_hidden H, n_mel_channels M, multi_speaker).  test_gpu_denoiser_dims.py runs them,
+# test_denoiser_plan_cpu.py pins the path each takes.
+DEN_SIZES = {
+    "A": (3, 128, 192, 80, 0),    # C below 256; H a multiple of 32, not of 64
+    "B": (3, 64, 32, 20, 1),      # every minimum at once: 64-row packs, M below one 32-row block, K = H = 32 speaker projection
+    "C": (2, 384, 256, 100, 0),   # C above 256, 2C = 768: the x / skip split falls inside a 128-row tile; NL < 3
+    "D": (4, 256, 256, 100, 0),   # fused layers, generic head, fused tail
+    "E": (3, 256, 256, 136, 1),   # fused layers, generic head and tail
+    "F": (3, 256, 384, 80, 0),    # only H differs
+    "G": (3, 256, 256, 80, 0),    # the control: single launch by default, generic under MG_DENOISER_GENERIC
+}
+DEN_SMALL_SHAPES = [(1, 1), (2, 63), (3, 129), (2, 260)]   # one frame; a partial 64-frame tile; one past two; float4, 128-frame tiles
+DEN_LARGE_SHAPE = ("C", 16, 700)                           # the conv kernel's large forms (test_conv_forms_reached)
+
+
+def den_size_configs(name, sizes=None):
+    """(preprocess_config, model_config) of hot_path_configs with the sizes of DEN_SIZES[name] (or `sizes`)."""
+    NL, C, H, M, ms = sizes or DEN_SIZES[name]
+    _, pre, mc, _ = hot_path_configs(multi_speaker=bool(ms), stats_dir=None)
+    pre["preprocessing"]["mel"]["n_mel_channels"] = M
+    mc["transformer"]["encoder_hidden"] = H
+    mc["denoiser"]["residual_channels"], mc["denoiser"]["residual_layers"], mc["denoiser"]["keep_bins"] = C, NL, M
+    return pre, mc
+
+
+def live_output_projection(den, seed=3):
+    """Denoiser.__init__ zeroes output_projection's weight: with it the output would be the bias broadcast over the
+    frames whatever the layers compute.  Seeded weight and bias instead."""
+    gen = torch.Generator().manual_seed(seed)
+    conv = den.output_projection.conv
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(conv.weight.shape, generator=gen) * 0.05)
+        conv.bias.copy_(torch.randn(conv.bias.shape, generator=gen) * 0.1)
+
+
+def den_size_model(mg, name, sizes=None):
+    """(product Denoiser of DEN_SIZES[name] (or `sizes`) on the CPU, its weights as float64 leaves, as float32 tensors).  No fixture
+    recipe exists for these sizes: the module's own initialisation under a fixed seed, the same in every process."""
+    torch.manual_seed(4100 + ord(name))
+    den = mg.Denoiser(*den_size_configs(name, sizes))
+    live_output_projection(den, 4200 + ord(name))
+    W32 = {k: v.detach().clone() for k, v in den.state_dict().items()}
+    W64 = {k: v.double().requires_grad_() for k, v in W32.items()}
+    return den, W64, W32
+
+
+# The denoiser tests' bars (max-abs error / max-abs reference, per tensor) against float64: forward, data gradients,
+# parameter gradients -- and the one fallback for a tensor that misses its bar (den_judge).
+DEN_FT, DEN_GT, DEN_PT = 2e-5, 5e-5, 1e-4
+
+
+def den_kind(key):
+    return re.sub(r"residual_layers\.\d+\.", "residual_layers.*.", key)
+
+
+def den_bar(key):
+    return DEN_FT if key == "out" else DEN_PT if key.startswith("param/") else DEN_GT
+
+
+def den_err(got, ref):
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return float((got.double() - ref.double()).abs().max() / (ref.double().abs().max() + 1e-30))
+
+
+def den_f32_cpu_errors(W32, x, t, cond, spk, go, ref):
+    """The yardstick for a missed bar: the float32 CPU oracle's autograd error against the float64 one (`ref`) on the
+    same inputs, worst tensor per kind."""
+    W = {k: v.clone().requires_grad_() for k, v in W32.items()}
+    got = oracle_grads(W, x, t, cond, spk, go, torch.float32)
+    worst = {}
+    for k, v in got.items():
+        worst[den_kind(k)] = max(worst.get(den_kind(k), 0.0), den_err(v, ref[k]))
+    return worst
+
+
+def den_run(case):
+    """One product forward in grad mode + backward of a case (den, x, t, cond, spk, go, ms, B, L); every result on the GPU,
+    and how far the backward workspace's `launches` advanced."""
+    den = case.den
+    den.zero_grad(set_to_none=True)
+    before = den.backward_status(case.B, case.L)
+    x, cond = case.x.cuda().requires_grad_(), case.cond.cuda().requires_grad_()
+    spk = case.spk.cuda().requires_grad_() if case.ms else None
+    out = den(x, case.t.cuda(), cond, spk)
+    (out * case.go.cuda()).sum().backward()
+    after = den.backward_status(case.B, case.L)
+    den.check()
+    got = {"out": out.detach(), "d_x": x.grad, "d_cond": cond.grad}
+    if case.ms:
+        got["d_spk"] = spk.grad
+    for k, p in den.named_parameters():
+        assert p.grad is not None, k
+        got["param/" + k] = p.grad
+    den.zero_grad(set_to_none=True)
+    assert after["error"] == 0 and before["error"] == 0, (before, after)
+    return got, after["launches"] - before["launches"]
+
+
+def den_judge(case, label, got, fails, keys=None, ref_of=None, tag="BWDERR"):
+    """Every tensor against float64 (case.ref_gpu(key), or ref_of(key)) at its bar; a tensor that misses it passes only
+    within 8 x the float32 CPU oracle's error at the same case (case.f32_cpu_error(kind)), and only where that exceeds
+    the bar.  Prints and returns the worst error per tensor kind."""
+    worst = {}
+    for k in (keys or got):
+        e = den_err(got[k], ref_of(k) if ref_of else case.ref_gpu(k))
+        kind, bar = den_kind(k), den_bar(k)
+        worst[kind] = max(worst.get(kind, 0.0), e)
+        if not e <= bar:
+            f32 = case.f32_cpu_error(kind)
+            if 8 * f32 > bar and e <= 8 * f32:
+                print("%s-WIDENED %s %s: %.3e > %.1e, within 8 x the float32 CPU oracle's %.3e" % (tag, label, k, e, bar, f32))
+            else:
+                fails.append("%s %s: %.3e > %.1e (float32 CPU oracle: %.3e)" % (label, k, e, bar, f32))
+    for kind in sorted(worst):
+        print("%s %-28s %-52s %.3e" % (tag, label, kind, worst[kind]))
+    return worst
 
 
 def jcu_oracle_grads(W, x_ts, x_t_prevs, s, t, cot, dtype, masks=None):

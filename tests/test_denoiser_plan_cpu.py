@@ -7,6 +7,7 @@ import pytest
 
 import mixgan_tts_amd as mg
 from mixgan_tts_amd import _lib
+from helpers import DEN_SIZES, DEN_SMALL_SHAPES, DEN_LARGE_SHAPE
 
 CUS = 256
 SAVE, SPLIT, P16 = 1, 2, 4
@@ -90,6 +91,22 @@ def test_shape_conditions():
     assert _form(_plan(16, 1000, INFER, dims=_dims(mel_bins=97))) is None
     assert _form(_plan(16, 1000, INFER, dims=_dims(channels=128))) is None
     assert _form(_plan(16, 1000, INFER, dims=_dims(cond_channels=192))) is None
+
+
+@pytest.mark.parametrize("name", sorted(DEN_SIZES))
+def test_other_model_sizes_launch_per_layer(name):
+    """The sizes test_gpu_denoiser_dims.py runs (helpers.DEN_SIZES): A to F launch per layer in inference and in save
+    mode at every shape of that test, so its default and MG_DENOISER_PERSIST=0 runs are the same code there; G, the
+    control, takes the single launch."""
+    NL, C, H, M, ms = DEN_SIZES[name]
+    dims = _lib.DenoiserDims(NL, C, H, M, ms)
+    modes = [0, SAVE] + ([INFER] if C == 256 and H == 256 else [])      # the 16-row packs exist at 256 / 256 only
+    for B, L in DEN_SMALL_SHAPES + [DEN_LARGE_SHAPE[1:]]:
+        for mode in modes:
+            p = _plan(B, L, mode, dims=dims)
+            assert p.path == (1 if name == "G" else 0), (name, B, L, mode)
+            if p.path == 0:
+                assert _form(p) is None
 
 
 def test_chain_capacity_follows_cus():

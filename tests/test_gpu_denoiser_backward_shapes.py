@@ -20,17 +20,19 @@ gradient; the product computes on the inputs as given."""
 import ctypes
 import json
 import os
-import re
 
 import pytest
 import torch
 
 from helpers import GOLDEN, hot_path_configs, seeded, oracle_grads, condition_relu_kinks
+# shared with test_gpu_denoiser_dims.py: the bars, the error measure, the one run and the judgement with its fallback
+from helpers import DEN_FT as FT
+from helpers import den_bar as _bar, den_err as _err, den_run as _run, den_judge as _judge
+from helpers import den_f32_cpu_errors
 from oracle import weights as WR
 from mixgan_tts_amd import _lib
 
 pytestmark = pytest.mark.gpu
-FT, GT, PT = 2e-5, 5e-5, 1e-4
 SEED = {0: 78, 1: 79}
 # Reduced with fp32 atomics, so not bit-reproducible run to run: small_linear_t_kernel with Z = n_layers adds every
 # layer's product into the step-vector gradient (bws.ds), which the two mlp weight gradients are computed from, and in
@@ -80,14 +82,6 @@ def _model(mg, ms, n_layers=20):
     return _MODELS[key]
 
 
-def _kind(key):
-    return re.sub(r"residual_layers\.\d+\.", "residual_layers.*.", key)
-
-
-def _bar(key):
-    return FT if key == "out" else PT if key.startswith("param/") else GT
-
-
 class Case:
     """Fixed inputs of one (B, L, speakers, layers) and their float64 reference, computed once."""
 
@@ -124,12 +118,7 @@ class Case:
         """The yardstick for a missed bar: the float32 CPU oracle's autograd error against the float64 one at this
         shape and seed, worst tensor of the kind."""
         if self._f32 is None:
-            W = {k: v.clone().requires_grad_() for k, v in self.W32.items()}
-            got = oracle_grads(W, self.x, self.t, self.cond, self.spk, self.go, torch.float32)
-            self._f32 = {}
-            for k, v in got.items():
-                e = _err(v, self.ref()[k])
-                self._f32[_kind(k)] = max(self._f32.get(_kind(k), 0.0), e)
+            self._f32 = den_f32_cpu_errors(self.W32, self.x, self.t, self.cond, self.spk, self.go, self.ref())
         return self._f32[kind]
 
     def batch_of_one(self, mg, b):
@@ -149,11 +138,6 @@ def _case(mg, B, L, ms, n_layers=20, t_one=999, salt=0):
     return _CASES[key]
 
 
-def _err(got, ref):
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    return float((got.double() - ref.double()).abs().max() / (ref.double().abs().max() + 1e-30))
-
-
 def _cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
@@ -163,46 +147,6 @@ def _single_launch_expected(case):
     the CUs, and no MG_DENOISER_PERSIST=0."""
     return (os.environ.get("MG_DENOISER_PERSIST", "1")[:1] != "0" and case.n_layers >= 3
             and -(-case.L // 32) <= _cus() // 4)
-
-
-def _run(case):
-    """One product forward in grad mode + backward; every result on the GPU, and how far `launches` advanced."""
-    den = case.den
-    den.zero_grad(set_to_none=True)
-    before = den.backward_status(case.B, case.L)
-    x, cond = case.x.cuda().requires_grad_(), case.cond.cuda().requires_grad_()
-    spk = case.spk.cuda().requires_grad_() if case.ms else None
-    out = den(x, case.t.cuda(), cond, spk)
-    (out * case.go.cuda()).sum().backward()
-    after = den.backward_status(case.B, case.L)
-    den.check()
-    got = {"out": out.detach(), "d_x": x.grad, "d_cond": cond.grad}
-    if case.ms:
-        got["d_spk"] = spk.grad
-    for k, p in den.named_parameters():
-        assert p.grad is not None, k
-        got["param/" + k] = p.grad
-    den.zero_grad(set_to_none=True)
-    assert after["error"] == 0 and before["error"] == 0, (before, after)
-    return got, after["launches"] - before["launches"]
-
-
-def _judge(case, label, got, fails, keys=None, ref_of=None):
-    """Every tensor against float64 at its bar; returns the worst error per tensor kind."""
-    worst = {}
-    for k in (keys or got):
-        e = _err(got[k], ref_of(k) if ref_of else case.ref_gpu(k))
-        kind, bar = _kind(k), _bar(k)
-        worst[kind] = max(worst.get(kind, 0.0), e)
-        if not e <= bar:
-            f32 = case.f32_cpu_error(kind)
-            if 8 * f32 > bar and e <= 8 * f32:
-                print("BWDERR-WIDENED %s %s: %.3e > %.1e, within 8 x the float32 CPU oracle's %.3e" % (label, k, e, bar, f32))
-            else:
-                fails.append("%s %s: %.3e > %.1e (float32 CPU oracle: %.3e)" % (label, k, e, bar, f32))
-    for kind in sorted(worst):
-        print("BWDERR %-28s %-52s %.3e" % (label, kind, worst[kind]))
-    return worst
 
 
 # ------------------------------------------------------------------------------------------ 2. shapes x paths
