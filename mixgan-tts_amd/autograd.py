@@ -561,23 +561,42 @@ def voc_up(x, w, b, u, slope, alpha):
 
 
 # --------------------------------------------------------------------------------------------------
-# MelGAN generator (melgan.MelGANGenerator.forward_train; csrc/melgan_train.hip).  Effective weights, as above.
+# MelGAN generator (melgan.MelGANGenerator._walk; csrc/melgan_train.hip).  Effective weights, as above.
 # --------------------------------------------------------------------------------------------------
+def melgan_block_fwd(buf, pack1, b1, mix, C, dil, slope, out=None, out_bs=0):
+    """General-form MelGAN ResnetBlock(C, dil) on buf [B, 2C, L], x in channels [0, C): t = lrelu(conv3(reflection_pad(
+    lrelu(x)), dil) + b1) -> channels [C, 2C), then y = [Ws | W2] [x ; t] + bs + b2, one K = 1 GEMM; mix() gives that pack
+    and bias, after the conv as both callers always did.  out None: a new y (training); else into `out`, batch stride
+    out_bs (inference).  Two entry points on purpose: only mg_conv1x1_fwd_strided writes a strided output, and its case
+    list is not mg_conv1d_fwd_split's, so moving either side could change its bits."""
+    L = buf.shape[2]
+    ops.conv1d_reflect_packed(buf, pack1, b1, C, 3, dil, slope, "lrelu_s", slope, x_bs=2 * C * L, C=C, out=buf,
+                              out_bs=2 * C * L, out_off=C * L)
+    pack_mix, b_mix = mix()
+    if out is None:
+        return ops.conv1d_packed(buf, pack_mix, b_mix, C, 1)
+    _lib.check(_lib.lib().mg_conv1x1_fwd_strided(_lib.fptr(buf), 2 * C * L, _lib.fptr(pack_mix), _lib.fptr(b_mix),
+                                                 _lib.fptr(out), out_bs, buf.shape[0], 2 * C, L, C, _lib.stream_ptr()))
+    return out
+
+
 class _MelResBlockFn(torch.autograd.Function):
-    """MelGAN ResnetBlock(C, dil): t = lrelu(conv3(reflection_pad(lrelu(x)), w1, dil) + b1), y = ws x + w2 t + bs + b2,
-    the last line one K = 1 GEMM over the [B, 2C, L] buffer [x ; t].  Saves that buffer -- x is the first leaky ReLU's
-    input, t the second's OUTPUT, whose sign is its input's -- and the weights; returns (y, buffer)."""
+    """melgan_block_fwd on a fresh [B, 2C, L] buffer [x ; t] and fresh packs.  Saves that buffer -- x is the first leaky
+    ReLU's input, t the second's OUTPUT, whose sign is its input's -- and the weights; returns (y, buffer)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, ws, bs, dil, slope):
         B, C, L = x.shape
         buf = torch.empty(B, 2 * C, L, device=x.device, dtype=torch.float32)
         buf[:, :C].copy_(x)
-        ops.conv1d_reflect_packed(buf, ops.pack_conv_weight(w1, ops.PACK_PLAIN), b1, C, 3, dil, slope, "lrelu_s", slope,
-                                  x_bs=2 * C * L, C=C, out=buf, out_bs=2 * C * L, out_off=C * L)
-        wmix = torch.cat([ws, w2], 1)
-        y = ops.conv1d_packed(buf, ops.pack_conv_weight(wmix, ops.PACK_PLAIN), bs + b2, C, 1)
-        ctx.save_for_backward(buf, w1, wmix)
+        mixed = []
+
+        def mix():
+            mixed.append(torch.cat([ws, w2], 1))
+            return ops.pack_conv_weight(mixed[0], ops.PACK_PLAIN), bs + b2
+
+        y = melgan_block_fwd(buf, ops.pack_conv_weight(w1, ops.PACK_PLAIN), b1, mix, C, dil, slope)
+        ctx.save_for_backward(buf, w1, mixed[0])
         ctx.cfg = (dil, slope)
         ctx.mark_non_differentiable(buf)
         return y, buf
@@ -604,14 +623,44 @@ def melgan_resblock(x, w1, b1, w2, b2, ws, bs, dil, slope):
 
 
 # --------------------------------------------------------------------------------------------------
+# Discriminator stacks: a chain of convolutions as ONE node f(x, <two non-tensor arguments>, w0, b0, w1, b1, ...) that
+# returns every layer's map, so that a map's outside gradient (feature matching) and the leaky-ReLU mask of the layer
+# below (from the stored activated map: slope > 0 keeps the sign) ride in the data-gradient kernel's epilogue.
+# --------------------------------------------------------------------------------------------------
+def _stack_backward(need, gs, start, wgrad, dgrad, bottom):
+    """-> (dx, None, None, dw0, db0, ...), each only where `need` (needs_input_grad) asks.  gs[j]: the outside gradient of
+    layer j's map or None.  Walks from the highest map that has one down to `lowest`, the lowest layer with anything to
+    compute at or below it.  d = gradient of layer j's PRE-activation: start(j, gs[j]) -> d; wgrad(j, d, want_w,
+    want_b) -> (dw, db); dgrad(j, d, gs[j - 1]) -> d of layer j - 1, masked by layer j's input; bottom(d) -> dx."""
+    n = len(gs)
+    need_w = [need[3 + 2 * j] for j in range(n)]
+    need_b = [need[4 + 2 * j] for j in range(n)]
+    lowest = 0 if need[0] else min([j for j in range(n) if need_w[j] or need_b[j]], default=n)
+    grads = [None] * (3 + 2 * n)
+    d = None
+    for j in range(n - 1, lowest - 1, -1):
+        if d is None:
+            if gs[j] is None:
+                continue
+            d = start(j, gs[j].contiguous())
+        if need_w[j] or need_b[j]:
+            dw, db = wgrad(j, d, need_w[j], need_b[j])
+            grads[3 + 2 * j], grads[4 + 2 * j] = (dw if need_w[j] else None), (db if need_b[j] else None)
+        if j > lowest:
+            add = gs[j - 1]
+            d = dgrad(j, d, None if add is None else add.contiguous())
+        elif need[0]:
+            grads[0] = bottom(d)
+    return tuple(grads)
+
+
+# --------------------------------------------------------------------------------------------------
 # HiFi-GAN multi-scale discriminator (csrc/msd.hip; hifigan_discriminators.py)
 # --------------------------------------------------------------------------------------------------
 class _ScaleStackFn(torch.autograd.Function):
     """DiscriminatorS' one-channel first layer and the grouped layers above it as ONE node, every layer followed by
     leaky_relu(slope): x [N, 1, T] -> the activated maps.  params = (w0, b0, w1, b1, ...), effective weights;
-    layers[j] = (stride, groups, padding).  One node so that a map's gradient from outside (feature matching) and the
-    leaky-ReLU mask of the layer below ride in the data-gradient kernel's epilogue; masks come from the stored
-    activated maps (slope > 0 keeps the sign).  Weight / bias / data gradients are computed only where asked for."""
+    layers[j] = (stride, groups, padding)."""
 
     @staticmethod
     def forward(ctx, x, slope, layers, *params):
@@ -635,36 +684,23 @@ class _ScaleStackFn(torch.autograd.Function):
         n = len(layers)
         saved = ctx.saved_tensors
         x, maps, ws = saved[0], saved[1:1 + n], saved[1 + n:]
-        need = ctx.needs_input_grad
-        need_w = [need[3 + 2 * j] for j in range(n)]
-        need_b = [need[4 + 2 * j] for j in range(n)]
-        lowest = 0 if need[0] else min([j for j in range(n) if need_w[j] or need_b[j]], default=n)
-        grads = [None] * (3 + 2 * n)
-        d = None                                   # gradient of layer j's PRE-activation
-        for j in range(n - 1, lowest - 1, -1):
-            if d is None:
-                if gs[j] is None:
-                    continue
-                d = ops.lrelu_bwd(gs[j].contiguous(), maps[j], slope)
+
+        def wgrad(j, d, want_w, want_b):
             s, g, pad = layers[j]
             K = ws[j].shape[2]
-            if j == 0:
-                if need_w[0] or need_b[0]:
-                    dw, db = ops.conv1d_c1_wgrad(d, x, K, pad)
-                    grads[3], grads[4] = (dw if need_w[0] else None), (db if need_b[0] else None)
-                if need[0]:
-                    grads[0] = ops.conv1d_c1_dgrad(d, ws[0], x.shape[2], pad)
-                break
+            if j == 0:                             # the one-channel kernel gives both in one launch
+                return ops.conv1d_c1_wgrad(d, x, K, pad)
+            return (ops.gconv1d_wgrad(d, maps[j - 1], K, s, pad, g) if want_w else None,
+                    ops.rowsum(d) if want_b else None)
+
+        def dgrad(j, d, add):
+            s, g, pad = layers[j]
             below = maps[j - 1]
-            if need_w[j]:
-                grads[3 + 2 * j] = ops.gconv1d_wgrad(d, below, K, s, pad, g)
-            if need_b[j]:
-                grads[4 + 2 * j] = ops.rowsum(d)
-            if j > lowest:
-                add = gs[j - 1]
-                d = ops.gconv1d_dgrad(d, ops.gconv_pack(ws[j], s, g, ops.GCONV_DGRAD), below.shape[1], below.shape[2], K, s,
-                                      pad, g, map=below, add=None if add is None else add.contiguous(), slope=slope)
-        return tuple(grads)
+            return ops.gconv1d_dgrad(d, ops.gconv_pack(ws[j], s, g, ops.GCONV_DGRAD), below.shape[1], below.shape[2],
+                                     ws[j].shape[2], s, pad, g, map=below, add=add, slope=slope)
+
+        return _stack_backward(ctx.needs_input_grad, gs, lambda j, g: ops.lrelu_bwd(g, maps[j], slope), wgrad, dgrad,
+                               lambda d: ops.conv1d_c1_dgrad(d, ws[0], x.shape[2], layers[0][2]))
 
 
 def scale_stack(x, slope, layers, *params):
@@ -716,9 +752,7 @@ def reflect_pad1d(x, p):
 class _PeriodStackFn(torch.autograd.Function):
     """DiscriminatorP(p) as ONE node: the fold of x [N, 1, T] onto the slotted axis, the five leaky-ReLU layers and
     conv_post; returns the six slotted maps [1, C, N p S[j]] (slack exactly 0).  params = (w0, b0, ..., w5, b5),
-    effective [Co, Ci, K] weights.  Stores only the activated maps (slope > 0 keeps the sign); a map's gradient from
-    outside (feature matching) and the mask of the layer below ride in the data-gradient epilogue of the layer above;
-    weight / bias / data gradients are computed only where asked for."""
+    effective [Co, Ci, K] weights."""
 
     @staticmethod
     def forward(ctx, x, p, slope, *params):
@@ -746,33 +780,24 @@ class _PeriodStackFn(torch.autograd.Function):
         n = len(gs)
         saved = ctx.saved_tensors
         bufs, ws = saved[:n], saved[n:]        # bufs[j]: the input of layer j (the fold, then the activated maps)
-        need = ctx.needs_input_grad
-        need_w = [need[3 + 2 * j] for j in range(n)]
-        need_b = [need[4 + 2 * j] for j in range(n)]
-        lowest = 0 if need[0] else min([j for j in range(n) if need_w[j] or need_b[j]], default=n)
-        grads = [None] * (3 + 2 * n)
         R = N * p
-        d = None                                   # gradient of layer j's PRE-activation, slotted
-        for j in range(n - 1, lowest - 1, -1):
-            if d is None:
-                if gs[j] is None:
-                    continue
-                d = gs[j].contiguous()
-                if j < n - 1:
-                    d = ops.lrelu_bwd(d, bufs[j + 1], slope)
-            K, stride = ws[j].shape[2], S[j] // S[j + 1]
-            if need_w[j]:
-                grads[3 + 2 * j] = ops.conv1d_wgrad(d, bufs[j], K, stride, (K - 1) // 2)
-            if need_b[j]:
-                grads[4 + 2 * j] = ops.rowsum(d)
-            if j > lowest:
-                add = gs[j - 1]
-                d = ops.period_conv_dgrad(d, ws[j], R, S[j], H[j], S[j + 1], stride, map=bufs[j],
-                                          add=None if add is None else add.contiguous(), slope=slope)
-            elif need[0]:
-                din0 = ops.period_conv_dgrad(d, ws[0], R, S[0], H[0], S[1], stride)
-                grads[0] = ops.period_fold_bwd(din0, N, T, p)
-        return tuple(grads)
+
+        def start(j, g):                           # conv_post's map is raw; the others are activated
+            return g if j == n - 1 else ops.lrelu_bwd(g, bufs[j + 1], slope)
+
+        def wgrad(j, d, want_w, want_b):
+            K = ws[j].shape[2]
+            return (ops.conv1d_wgrad(d, bufs[j], K, S[j] // S[j + 1], (K - 1) // 2) if want_w else None,
+                    ops.rowsum(d) if want_b else None)
+
+        def dgrad(j, d, add):
+            return ops.period_conv_dgrad(d, ws[j], R, S[j], H[j], S[j + 1], S[j] // S[j + 1], map=bufs[j], add=add,
+                                         slope=slope)
+
+        def bottom(d):                             # no mask below layer 0: the fold is linear
+            return ops.period_fold_bwd(ops.period_conv_dgrad(d, ws[0], R, S[0], H[0], S[1], S[0] // S[1]), N, T, p)
+
+        return _stack_backward(ctx.needs_input_grad, gs, start, wgrad, dgrad, bottom)
 
 
 def period_stack(x, p, slope, *params):

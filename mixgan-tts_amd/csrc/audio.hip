@@ -7,10 +7,8 @@
 // rows of DC and Nyquist zero), so an FFT computes the same sums with less rounding.
 //
 // Both kernels are one wave per workgroup.  A wave transforms two frames at once as z = a + i b: one 1024-point
-// complex FFT (radix-4 Stockham, five passes through an 8 KB LDS buffer, twiddles from a host-built fp32 table), then
-//     A[k] = (Z[k] + conj Z[N-k]) / 2,   B[k] = (Z[k] - conj Z[N-k]) / 2i          (forward split)
-//     Z[k] = A[k] + i B[k] over the Hermitian extensions of A and B                 (inverse packing)
-// and the inverse is conj(FFT(conj Z)) / N.
+// complex FFT (radix-4 Stockham, five passes through an 8 KB LDS buffer, twiddles from a host-built fp32 table), with
+// the forward split and the inverse packing of stft_pair.h; the inverse is conj(FFT(conj Z)) / N.
 //
 // Forward (grid: frame pairs x batch): frame t covers samples [t hop - N/2, t hop + N/2) of the item, reflected at
 // both of the item's own ends (its length comes from `lengths`, so ragged items of one batch get exactly what a call
@@ -24,7 +22,7 @@
 // 1 / (n_fft / hop) in its pseudo-inverse and its * (n_fft / hop) after the division are powers of two that cancel
 // exactly, so neither is applied.
 #include "common.h"
-#include "fft1024.h"
+#include "stft_pair.h"
 
 #include <float.h>
 
@@ -89,26 +87,7 @@ __device__ __forceinline__ void stft_fwd_body(const FwdArgs &a)
         return;
     }
 
-    const float *x = a.x + (size_t)b * a.x_bs;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int n = lane + 64 * i;
-        const float w = a.window[n];
-        float2 z;
-        int j = t0 * a.hop + n - N / 2;
-        j = j < 0 ? -j : (j >= Lb ? 2 * (Lb - 1) - j : j);
-        j = j < 0 ? 0 : (j >= Lb ? Lb - 1 : j);
-        z.x = x[j] * w;
-        if (vb) {
-            j = (t0 + 1) * a.hop + n - N / 2;
-            j = j < 0 ? -j : (j >= Lb ? 2 * (Lb - 1) - j : j);
-            j = j < 0 ? 0 : (j >= Lb ? Lb - 1 : j);
-            z.y = x[j] * w;
-        } else {
-            z.y = 0.f;
-        }
-        d[n] = z;
-    }
+    mg_pair_stage(d, a.x + (size_t)b * a.x_bs, Lb, a.hop, t0, a.window, vb, lane);
     __syncthreads();
     mg_fft1024(d, a.tw, lane);
 
@@ -117,10 +96,8 @@ __device__ __forceinline__ void stft_fwd_body(const FwdArgs &a)
     for (int jj = 0; jj < 9; ++jj) {
         const int k = lane + 64 * jj;
         if (k >= NB) break;
-        const float2 zk = d[k], zm = d[(N - k) & (N - 1)];
-        // A = (Z[k] + conj Z[N-k]) / 2, B = (Z[k] - conj Z[N-k]) / 2i
-        const float ar = 0.5f * (zk.x + zm.x), ai = 0.5f * (zk.y - zm.y);
-        const float br = 0.5f * (zk.y + zm.y), bi = -0.5f * (zk.x - zm.x);
+        float ar, ai, br, bi;
+        mg_pair_split(d, k, ar, ai, br, bi);
         const float ma = sqrtf(ar * ar + ai * ai), mb = sqrtf(br * br + bi * bi);
         if (EPI == EPI_MEL) {
             mags[k] = ma;
@@ -150,13 +127,8 @@ __device__ __forceinline__ void stft_fwd_body(const FwdArgs &a)
     __syncthreads();
     float *mel = a.mel + (size_t)b * a.n_mels * a.T;
     for (int m = lane; m < a.n_mels; m += 64) {
-        const int st = a.band[m], len = a.band[a.n_mels + m];
-        const float *w = a.band_w + a.band[2 * a.n_mels + m];
-        float s0 = 0.f, s1 = 0.f;
-        for (int i = 0; i < len; ++i) {
-            s0 = fmaf(w[i], mags[st + i], s0);
-            s1 = fmaf(w[i], mags[NB + st + i], s1);
-        }
+        float s0, s1;
+        mg_pair_band_sum(a.band, a.band_w, a.n_mels, m, mags, s0, s1);
         // spectral_normalize: log(clamp(x, 1e-5) * 1)
         if (wa) mel[(size_t)m * a.T + t0] = logf(fmaxf(s0, 1e-5f));
         if (wb) mel[(size_t)m * a.T + t0 + 1] = vb ? logf(fmaxf(s1, 1e-5f)) : 0.f;
@@ -189,6 +161,8 @@ __global__ __launch_bounds__(64) void istft_ola_kernel(InvArgs a)
     const int lane = threadIdx.x, b = blockIdx.y, hop = a.hop;
     const int p0 = blockIdx.x * a.tile + N / 2;  // first output sample, in padded coordinates
     const int nacc = a.tile / 64;
+    // the frames that cover the tile: from the first position's lowest to the last position's highest (written out: as
+    // a call of mg_pair_frame_range it compiles to other code, and so does the packing below)
     const int num = p0 - (N - 1);
     const int t_lo = num <= 0 ? 0 : (num + hop - 1) / hop;
     int t_hi = (p0 + a.tile - 1) / hop;
@@ -239,10 +213,8 @@ __global__ __launch_bounds__(64) void istft_ola_kernel(InvArgs a)
         const int p = p0 + lane + 64 * j;
         if (j >= nacc || p - N / 2 >= a.Lout) continue;
         // window_sumsquare: frames in ascending order, float32 accumulator, each add in float64
-        const int n0 = p - (N - 1);
-        const int w_lo = n0 <= 0 ? 0 : (n0 + hop - 1) / hop;
-        int w_hi = p / hop;
-        w_hi = w_hi > a.T - 1 ? a.T - 1 : w_hi;
+        int w_lo, w_hi;
+        mg_pair_frame_range(p, hop, a.T, w_lo, w_hi);
         float ws = 0.f;
         for (int t = w_lo; t <= w_hi; ++t) ws = (float)((double)ws + a.wsq[p - t * hop]);
         float v = acc[j];
@@ -250,8 +222,6 @@ __global__ __launch_bounds__(64) void istft_ola_kernel(InvArgs a)
         out[p - N / 2] = v;
     }
 }
-
-bool hop_ok(int hop) { return hop >= 1 && hop <= N && (hop & (hop - 1)) == 0; }
 
 }  // namespace
 
@@ -270,7 +240,7 @@ extern "C" int mg_stft_fwd(const float *x, long x_bs, const int *lengths, int B,
                            void *stream)
 {
     if (!x || !window || !twiddle || !phase) return MG_ERR_ARG;
-    if (B <= 0 || !hop_ok(hop) || L <= N / 2 || T <= 0 || T > 1 + L / hop || x_bs < L) return MG_ERR_SHAPE;
+    if (B <= 0 || !mg_stft_hop_ok(hop) || L <= N / 2 || T <= 0 || T > 1 + L / hop || x_bs < L) return MG_ERR_SHAPE;
     FwdArgs a = {};
     a.x = x;
     a.x_bs = x_bs;
@@ -293,7 +263,7 @@ extern "C" int mg_stft_mel(const float *x, long x_bs, const int *lengths, int B,
                            float *energy, int T, void *stream)
 {
     if (!x || !window || !twiddle || !band || !band_w || !mel || !energy) return MG_ERR_ARG;
-    if (B <= 0 || !hop_ok(hop) || L <= N / 2 || T <= 0 || T > 1 + L / hop || x_bs < L || n_mels <= 0 ||
+    if (B <= 0 || !mg_stft_hop_ok(hop) || L <= N / 2 || T <= 0 || T > 1 + L / hop || x_bs < L || n_mels <= 0 ||
         n_mels > MG_STFT_MAX_MELS)
         return MG_ERR_SHAPE;
     FwdArgs a = {};
@@ -318,7 +288,7 @@ extern "C" int mg_istft(const float *mag, const float *phase, long s_bs, long s_
                         void *stream)
 {
     if (!mag || !phase || !window || !wsq || !twiddle || !out) return MG_ERR_ARG;
-    if (B <= 0 || T < 2 || !hop_ok(hop) || tile <= 0 || tile % 64 || tile > MAX_TILE) return MG_ERR_SHAPE;
+    if (B <= 0 || T < 2 || !mg_stft_hop_ok(hop) || tile <= 0 || tile % 64 || tile > MAX_TILE) return MG_ERR_SHAPE;
     InvArgs a;
     a.mag = mag;
     a.phase = phase;

@@ -4,7 +4,7 @@
 //
 // Front end (grid: frame pairs x batch, one wave): frame f = offset + t of item b covers trimmed samples
 // [f step, f step + frame_len) of audio[b, start : end), zero past the end; pre-emphasis y[i] = x[i] - 0.97 x[i-1]
-// (y[0] = x[0]) is applied on the fly.  Two frames go through one 1024-point complex FFT (fft1024.h), the power
+// (y[0] = x[0]) is applied on the fly.  Two frames go through one 1024-point complex FFT (stft_pair.h), the power
 // spectrum |X|^2 / 1024 through the banded triangular filters (lane m owns filter m), exact zeros become DBL_EPSILON
 // and each frame is normalised over its filters by its population std (floored at 1e-12).  Rows at or past the
 // item's frame count are zeros, as sample_from_mfcc pads.
@@ -20,7 +20,7 @@
 // output does not depend on the batch around it.  Epilogue: + bias, clip to [0, 20], then optionally + residual and
 // clip again.  Layers with Ci % 32 != 0 (the Ci = 1 first conv) take a direct VALU kernel.
 #include "common.h"
-#include "fft1024.h"
+#include "stft_pair.h"
 
 #include <float.h>
 
@@ -79,9 +79,8 @@ __global__ __launch_bounds__(64) void ds_fbank_kernel(FbankArgs a)
     __syncthreads();
     mg_fft1024(d, a.tw, lane);
     for (int k = lane; k < NB; k += 64) {
-        const float2 zk = d[k], zm = d[(N - k) & (N - 1)];
-        const float ar = 0.5f * (zk.x + zm.x), ai = 0.5f * (zk.y - zm.y);
-        const float br = 0.5f * (zk.y + zm.y), bi = -0.5f * (zk.x - zm.x);
+        float ar, ai, br, bi;
+        mg_pair_split(d, k, ar, ai, br, bi);
         pw[k] = (ar * ar + ai * ai) * (1.f / N);
         pw[NB + k] = (br * br + bi * bi) * (1.f / N);
     }
@@ -89,12 +88,7 @@ __global__ __launch_bounds__(64) void ds_fbank_kernel(FbankArgs a)
     float s0 = 0.f, s1 = 0.f;
     const bool own = lane < a.nfilt;
     if (own) {
-        const int bs = a.band[lane], len = a.band[a.nfilt + lane];
-        const float *w = a.band_w + a.band[2 * a.nfilt + lane];
-        for (int i = 0; i < len; ++i) {
-            s0 = fmaf(w[i], pw[bs + i], s0);
-            s1 = fmaf(w[i], pw[NB + bs + i], s1);
-        }
+        mg_pair_band_sum(a.band, a.band_w, a.nfilt, lane, pw, s0, s1);
         s0 = s0 == 0.f ? (float)DBL_EPSILON : s0;
         s1 = s1 == 0.f ? (float)DBL_EPSILON : s1;
     }

@@ -1,5 +1,6 @@
-// One-wave 1024-point complex FFT in LDS, shared by the audio front end (audio.hip) and the DeepSpeaker filterbank
-// (deepspeaker.hip).
+// One-wave 1024-point complex FFT in LDS, shared by the audio front end (audio.hip), the log-mel backward
+// (vocoder_train.hip) and the DeepSpeaker filterbank (deepspeaker.hip), which reach it through stft_pair.h, and by the
+// pitch extractor (pitch.hip).
 #pragma once
 #include "common.h"
 

@@ -13,7 +13,7 @@
 // The two weight gradients (mg_conv1d_wgrad_ex, mg_conv_transpose1d_wgrad) are in conv_api.hip, on wgrad_tile_kernel of
 // wgrad_mfma.h.
 #include "common.h"
-#include "fft1024.h"
+#include "stft_pair.h"
 
 namespace {
 
@@ -81,7 +81,8 @@ struct MelBwdArgs {
     float *frames;       // [B, T, N] windowed frame gradients
 };
 
-// One wave, two frames: the forward's spectrum (same staging and FFT), then the chain rule down to the frame samples.
+// One wave, two frames: the forward's spectrum and band sums (stft_pair.h's staging, split and sum, as stft_fwd_body
+// calls them), then the chain rule down to the frame samples.
 __global__ __launch_bounds__(64) void stft_mel_bwd_frames_kernel(MelBwdArgs a)
 {
     __shared__ float2 d[N];
@@ -93,33 +94,13 @@ __global__ __launch_bounds__(64) void stft_mel_bwd_frames_kernel(MelBwdArgs a)
     const bool fb = t0 + 1 < 1 + Lb / a.hop;   // the forward transforms frame t0 + 1 whenever the signal has it
     const bool vb = t0 + 1 < a.T;              // ... but only T frames carry a gradient
 
-    const float *x = a.x + (size_t)b * a.x_bs;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int n = lane + 64 * i;
-        const float w = a.window[n];
-        float2 z;
-        int j = t0 * a.hop + n - N / 2;
-        j = j < 0 ? -j : (j >= Lb ? 2 * (Lb - 1) - j : j);
-        j = j < 0 ? 0 : (j >= Lb ? Lb - 1 : j);
-        z.x = x[j] * w;
-        if (fb) {
-            j = (t0 + 1) * a.hop + n - N / 2;
-            j = j < 0 ? -j : (j >= Lb ? 2 * (Lb - 1) - j : j);
-            j = j < 0 ? 0 : (j >= Lb ? Lb - 1 : j);
-            z.y = x[j] * w;
-        } else {
-            z.y = 0.f;
-        }
-        d[n] = z;
-    }
+    mg_pair_stage(d, a.x + (size_t)b * a.x_bs, Lb, a.hop, t0, a.window, fb, lane);
     __syncthreads();
     mg_fft1024(d, a.tw, lane);
 
     for (int k = lane; k < NB; k += 64) {
-        const float2 zk = d[k], zm = d[(N - k) & (N - 1)];
-        const float ar = 0.5f * (zk.x + zm.x), ai = 0.5f * (zk.y - zm.y);
-        const float br = 0.5f * (zk.y + zm.y), bi = -0.5f * (zk.x - zm.x);
+        float ar, ai, br, bi;
+        mg_pair_split(d, k, ar, ai, br, bi);
         spa[k] = make_float2(ar, ai);
         spb[k] = make_float2(br, bi);
         mags[k] = sqrtf(ar * ar + ai * ai);
@@ -130,13 +111,8 @@ __global__ __launch_bounds__(64) void stft_mel_bwd_frames_kernel(MelBwdArgs a)
     // dm = dmel * [m >= 1e-5] / m, m = basis |X| summed as in the forward
     const float *dmel = a.dmel + (size_t)b * a.n_mels * a.T;
     for (int m = lane; m < a.n_mels; m += 64) {
-        const int st = a.band[m], len = a.band[a.n_mels + m];
-        const float *w = a.band_w + a.band[2 * a.n_mels + m];
-        float s0 = 0.f, s1 = 0.f;
-        for (int i = 0; i < len; ++i) {
-            s0 = fmaf(w[i], mags[st + i], s0);
-            s1 = fmaf(w[i], mags[NB + st + i], s1);
-        }
+        float s0, s1;
+        mg_pair_band_sum(a.band, a.band_w, a.n_mels, m, mags, s0, s1);
         dm[m] = s0 >= 1e-5f ? dmel[(size_t)m * a.T + t0] / s0 : 0.f;
         dm[MG_STFT_MAX_MELS + m] = (vb && s1 >= 1e-5f) ? dmel[(size_t)m * a.T + t0 + 1] / s1 : 0.f;
     }
@@ -191,16 +167,12 @@ __global__ __launch_bounds__(256) void stft_mel_bwd_gather_kernel(const float *_
     for (int s = 0; s < 3; ++s) {
         if (!ok3[s]) continue;
         const int q = q3[s];
-        const int num = q - (N - 1);
-        const int t_lo = num <= 0 ? 0 : (num + hop - 1) / hop;
-        int t_hi = q / hop;
-        t_hi = t_hi > T - 1 ? T - 1 : t_hi;
+        int t_lo, t_hi;
+        mg_pair_frame_range(q, hop, T, t_lo, t_hi);
         for (int t = t_lo; t <= t_hi; ++t) acc += fr[(size_t)t * N + (q - t * hop)];
     }
     dx[(size_t)b * dx_bs + j] = acc;
 }
-
-bool hop_ok(int hop) { return hop >= 1 && hop <= N && (hop & (hop - 1)) == 0; }
 
 }  // namespace
 
@@ -264,7 +236,7 @@ extern "C" int mg_stft_mel_bwd(const float *x, long x_bs, const int *lengths, in
 {
     if (!x || !window || !twiddle || !band || !band_w || !dmel || !dx || !workspace) return MG_ERR_ARG;
     if (lengths) return MG_ERR_SHAPE;   // ragged items are not differentiated
-    if (B <= 0 || !hop_ok(hop) || L <= N / 2 || T <= 0 || T > 1 + L / hop || x_bs < L || dx_bs < L || n_mels <= 0 ||
+    if (B <= 0 || !mg_stft_hop_ok(hop) || L <= N / 2 || T <= 0 || T > 1 + L / hop || x_bs < L || dx_bs < L || n_mels <= 0 ||
         n_mels > MG_STFT_MAX_MELS)
         return MG_ERR_SHAPE;
     if (workspace_bytes < mg_stft_mel_bwd_workspace_bytes(B, T)) return MG_ERR_WORKSPACE;

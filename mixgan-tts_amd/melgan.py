@@ -12,7 +12,7 @@ with the packs of shortcut and block.4 concatenated gives shortcut(x) + block(x)
 three blocks of the 64- and 32-channel stages run as one launch each, holding a tile and its 13-sample halo in LDS.
 
 Training (csrc/melgan_train.hip, autograd.voc_conv with pad = REFLECT / melgan_resblock / voc_up): `forward_train` is
-the same function as an autograd tensor, every stage in the general form, the backward in the HIP library: the reflect-padded
+the same `_walk` with the `_Train` sites, every stage in the general form, the backward in the HIP library: the reflect-padded
 weight gradient mirrors the frame index while it stages the saved pre-activation, the data gradient is the zero-padded
 correlation over the padded length folded back through the reflection, and a ResnetBlock's K = 1 gradients run once
 over [x ; t].  vocoder_train's trainers take a MelVocoder as they take a HiFi-GAN generator.
@@ -90,15 +90,11 @@ class ResnetBlock(nn.Module):
             hit = cache[permuted] = (key, packed, bias)
         return hit[1], hit[2]
 
-    def forward_general(self, buf, out, out_bs, B, L):
+    def forward_general(self, buf, out, out_bs):
         """buf [B, 2C, L] with x in channels [0, C): t -> channels [C, 2C); the block output -> out (batch stride out_bs)."""
-        C = self.dim
         c1 = self.block[2]
-        ops.conv1d_reflect_packed(buf, c1.packed(ops.PACK_PLAIN), c1.bias.detach(), C, 3, self.dilation, SLOPE, "lrelu_s",
-                                  SLOPE, x_bs=2 * C * L, C=C, out=buf, out_bs=2 * C * L, out_off=C * L)
-        packed, bias = self.mix_pack(False)
-        check(_lib.lib().mg_conv1x1_fwd_strided(fptr(buf), 2 * C * L, fptr(packed), fptr(bias), fptr(out), out_bs, B,
-                                                2 * C, L, C, stream_ptr()))
+        ag.melgan_block_fwd(buf, c1.packed(ops.PACK_PLAIN), c1.bias.detach(), lambda: self.mix_pack(False), self.dim,
+                            self.dilation, SLOPE, out, out_bs)
 
 
 def residual_stack_fused(x, blocks):
@@ -116,6 +112,54 @@ def residual_stack_fused(x, blocks):
     out = torch.empty_like(x)
     check(_lib.lib().mg_melgan_stack_fwd(fptr(x), fptr(out), arr(w1), arr(b1), arr(wm), arr(bm), B, C, L, stream_ptr()))
     return out
+
+
+class _Infer:
+    """MelGANGenerator._walk's sites at inference."""
+
+    @staticmethod
+    def conv(c, x, Co, K, in_slope=1.0, alpha=1.0, act=None):
+        return ops.conv1d_reflect_packed(x, c.packed(ops.PACK_PLAIN), c.bias.detach(), Co, K, in_slope=in_slope, act=act,
+                                         alpha=alpha)
+
+    @staticmethod
+    def stage(up, blocks, x, C, r, fused):
+        nres = len(blocks)
+        if nres == 0 or (fused and nres == 3 and C in (32, 64)):
+            y = ops.conv_transpose1d_packed(x, up.packed(ops.PACK_TPOSE), up.bias.detach(), C, r, in_slope=SLOPE)
+            return (residual_stack_fused(y, blocks) if nres else y), ()
+        # general form: [B, 2C, L] buffers, x in [0, C), t in [C, 2C); the upsampler writes the first x, block j the next
+        B, Cin, Lin = x.shape
+        L = Lin * r
+        bufs = [torch.empty(B, 2 * C, L, device=x.device, dtype=torch.float32) for _ in range(min(nres, 2))]
+        check(_lib.lib().mg_conv_transpose1d_fwd_slice(fptr(x), fptr(up.packed(ops.PACK_TPOSE)), fptr(up.bias.detach()),
+                                                       fptr(bufs[0]), 2 * C * L, B, Cin, Lin, C, r, float(SLOPE), 1.0,
+                                                       stream_ptr()))
+        for j, blk in enumerate(blocks):
+            last = j + 1 == nres
+            out = torch.empty(B, C, L, device=x.device, dtype=torch.float32) if last else bufs[(j + 1) % 2]
+            blk.forward_general(bufs[j % 2], out, 0 if last else 2 * C * L)
+        return out, ()
+
+
+class _Train:
+    """MelGANGenerator._walk's sites in training; a stage also returns (block input, t) per block for the taps."""
+
+    @staticmethod
+    def conv(c, x, Co, K, in_slope=1.0, alpha=1.0, act=None):
+        return ag.voc_conv(x, c.effective_weight(), c.bias, 1, ag.REFLECT, in_slope, alpha, act)
+
+    @staticmethod
+    def stage(up, blocks, x, C, r, fused):      # fused: inference only
+        x = ag.voc_up(x, up.effective_weight(), up.bias, r, SLOPE, 1.0)
+        signs = []
+        for blk in blocks:
+            c1, c2, cs = blk.block[2], blk.block[4], blk.shortcut
+            y, xt = ag.melgan_resblock(x, c1.effective_weight(), c1.bias, c2.effective_weight(), c2.bias,
+                                       cs.effective_weight(), cs.bias, blk.dilation, SLOPE)
+            signs.append((x, xt[:, blk.dim:]))
+            x = y
+        return x, signs
 
 
 class MelGANGenerator(nn.Module):
@@ -154,41 +198,30 @@ class MelGANGenerator(nn.Module):
             raise _lib.MixganHipError("MelGANGenerator: dilations above 9 are not taken by the HIP conv")
         return B, Ci, L
 
+    def _walk(self, mel, site, scale, taps=None):
+        """First reflect conv (alpha = scale); per ratio one stage, an upsampler and its blocks at half the channels; last
+        reflect conv, tanh.  `site` (_Infer or _Train) runs each convolution and stage; `taps`: see forward_train."""
+        m, nres = self.model, self.n_residual_layers
+        tap = (lambda path, t: None) if taps is None else taps.__setitem__
+        C = 2 ** len(RATIOS) * self.ngf
+        x = site.conv(m[1], mel, C, 7, alpha=scale)
+        for i, r in enumerate(RATIOS):
+            base = 2 + i * (2 + nres)
+            C //= 2
+            tap("model.%d" % base, x)
+            x, signs = site.stage(m[base + 1], [m[base + 2 + j] for j in range(nres)], x, C, r, self.fused_stack)
+            for j, (xin, t) in enumerate(signs):
+                tap("model.%d.block.0" % (base + 2 + j), xin)
+                tap("model.%d.block.3" % (base + 2 + j), t)
+        last = len(m) - 2
+        tap("model.%d" % (last - 2), x)
+        return site.conv(m[last], x, 1, 7, in_slope=SLOPE, act="tanh")
+
     @torch.no_grad()
     def forward_scaled(self, mel, scale):
         """forward(mel * scale), the scale riding on the first conv's alpha (no pass over the mel)."""
-        B, Ci, L = self._check_input(mel)
-        mel = mel.float().contiguous()
-        m = self.model
-        C = 16 * self.ngf
-        x = ops.conv1d_reflect_packed(mel, m[1].packed(ops.PACK_PLAIN), m[1].bias.detach(), C, 7, alpha=scale)
-        nres = self.n_residual_layers
-        for i, r in enumerate(RATIOS):
-            base = 2 + i * (2 + nres)
-            up, blocks = m[base + 1], [m[base + 2 + j] for j in range(nres)]
-            Cin, C = C, C // 2
-            Lin, L = L, L * r
-            if self.fused_stack and nres == 3 and C in (32, 64):
-                y = ops.conv_transpose1d_packed(x, up.packed(ops.PACK_TPOSE), up.bias.detach(), C, r, in_slope=SLOPE)
-                x = residual_stack_fused(y, blocks)
-                continue
-            if nres == 0:
-                x = ops.conv_transpose1d_packed(x, up.packed(ops.PACK_TPOSE), up.bias.detach(), C, r, in_slope=SLOPE)
-                continue
-            # general form: [B, 2C, L] buffers, x in channels [0, C), t in [C, 2C); block j writes the next one's x
-            bufs = [torch.empty(B, 2 * C, L, device=mel.device, dtype=torch.float32) for _ in range(min(nres, 2))]
-            check(_lib.lib().mg_conv_transpose1d_fwd_slice(fptr(x), fptr(up.packed(ops.PACK_TPOSE)),
-                                                           fptr(up.bias.detach()), fptr(bufs[0]), 2 * C * L, B, Cin,
-                                                           Lin, C, r, float(SLOPE), 1.0, stream_ptr()))
-            for j, blk in enumerate(blocks):
-                if j + 1 < nres:
-                    blk.forward_general(bufs[j % 2], bufs[(j + 1) % 2], 2 * C * L, B, L)
-                else:
-                    x = torch.empty(B, C, L, device=mel.device, dtype=torch.float32)
-                    blk.forward_general(bufs[j % 2], x, 0, B, L)
-        last = m[len(m) - 2]
-        return ops.conv1d_reflect_packed(x, last.packed(ops.PACK_PLAIN), last.bias.detach(), 1, 7, in_slope=SLOPE,
-                                         act="tanh")
+        self._check_input(mel)
+        return self._walk(mel.float().contiguous(), _Infer, scale)
 
     def forward_train(self, mel, taps=None, scale=1.0):
         """forward_scaled(mel, scale) as an autograd tensor: gradients reach every weight_g / weight_v (through the
@@ -202,28 +235,7 @@ class MelGANGenerator(nn.Module):
         if self.ngf % 32:
             raise _lib.MixganHipError("MelGANGenerator.forward_train: ngf = %d; the general form takes channel counts "
                                       "that are multiples of 32" % self.ngf)
-        nres = self.n_residual_layers
-        m = self.model
-        x = ag.voc_conv(mel.float(), m[1].effective_weight(), m[1].bias, 1, ag.REFLECT, 1.0, float(scale))
-        for i, r in enumerate(RATIOS):
-            base = 2 + i * (2 + nres)
-            up = m[base + 1]
-            if taps is not None:
-                taps["model.%d" % base] = x
-            x = ag.voc_up(x, up.effective_weight(), up.bias, r, SLOPE, 1.0)
-            for j in range(nres):
-                blk = m[base + 2 + j]
-                c1, c2, cs = blk.block[2], blk.block[4], blk.shortcut
-                y, xt = ag.melgan_resblock(x, c1.effective_weight(), c1.bias, c2.effective_weight(), c2.bias,
-                                           cs.effective_weight(), cs.bias, blk.dilation, SLOPE)
-                if taps is not None:
-                    taps["model.%d.block.0" % (base + 2 + j)] = x
-                    taps["model.%d.block.3" % (base + 2 + j)] = xt[:, blk.dim:]
-                x = y
-        last = len(m) - 2
-        if taps is not None:
-            taps["model.%d" % (last - 2)] = x
-        return ag.voc_conv(x, m[last].effective_weight(), m[last].bias, 1, ag.REFLECT, SLOPE, 1.0, "tanh")
+        return self._walk(mel.float(), _Train, float(scale), taps)
 
 
 class MelVocoder(nn.Module):

@@ -115,7 +115,7 @@ def test_general_blocks_match_restatement(mg, C):
         buf[0][:, :C].copy_(x.cuda())
         out = torch.empty(B, C, L, device="cuda")
         for j, o in enumerate(ours):
-            o.forward_general(buf[j % 2], buf[(j + 1) % 2] if j < 2 else out, 2 * C * L if j < 2 else 0, B, L)
+            o.forward_general(buf[j % 2], buf[(j + 1) % 2] if j < 2 else out, 2 * C * L if j < 2 else 0)
         e = _err(out, _stack_ref(ref, x))
         assert e < TOL, (B, L, e)
 

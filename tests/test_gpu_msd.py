@@ -291,6 +291,39 @@ def test_module_eval_leaves_u_and_v(mg):
         check(got, a32, a64, BAR_MAP, "eval: " + what)
 
 
+def test_discriminator_s_partly_frozen_backward_stops_above_layer_0(mg):
+    """A weight-norm DiscriminatorS at T = 300 with convs.0 and convs.1 frozen, an input that does not require grad and
+    a loss on one middle map plus the logits: the walk down the stack starts at a map with an outside gradient and stops
+    at layer 2.  The layers above run the same kernels on the same data as with nothing frozen, and those kernels have
+    fixed summation orders, so their parameter gradients are the same bits."""
+    prefix = "discriminators.1."
+    W = {k[len(prefix):]: v for k, v in MR.msd_init(25).items() if k.startswith(prefix)}
+    gen = torch.Generator().manual_seed(26)
+    x = torch.randn(2, 1, 300, generator=gen).cuda()
+    cots = None
+    nets = {}
+    for name in ("all", "frozen"):
+        net = mg.DiscriminatorS()
+        net.load_state_dict({k: v.clone() for k, v in W.items()}, strict=True)
+        net = net.cuda().train()
+        if name == "frozen":
+            for q in [*net.convs[0].parameters(), *net.convs[1].parameters()]:
+                q.requires_grad_(False)
+        logits, fmap = net(x)
+        if cots is None:
+            cots = [torch.randn(t.shape, generator=gen).cuda() for t in (fmap[3], logits)]
+        ((fmap[3] * cots[0]).sum() + (logits * cots[1]).sum()).backward()
+        nets[name] = net
+    assert x.grad is None
+    full = dict(nets["all"].named_parameters())
+    for k, q in nets["frozen"].named_parameters():
+        if k.startswith(("convs.0.", "convs.1.")):
+            assert q.grad is None, "frozen %s got a gradient" % k
+        else:
+            assert q.grad is not None and torch.equal(q.grad, full[k].grad), k
+    assert all(q.grad is not None for q in full.values())
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # 4: in the trainer
 # ------------------------------------------------------------------------------------------------------------------
