@@ -22,6 +22,31 @@
                    // (both strides = 4 mod 64 words: the 16-lane groups of a b128 read land on 16 distinct 4-bank slots)
 #define AT_NEG (-1.0e30f)
 
+// ---------------------------------------------------------------------------------------------
+// Shared by the fp32 and the fp16 kernel.  Their tile loads, mask ballots and softmax updates are the same text too, but
+// stay written out in each: as calls they change all twelve instruction streams ("Attention kernels: shared code").
+// ---------------------------------------------------------------------------------------------
+// One staging thread's share of a 64-key tile in a workgroup of NWQ waves
+template <int NWQ> constexpr int AT_KCH = AT_D * 64 / (NWQ * 64);   // K channels: 32 (4 waves) or 16 (8)
+template <int NWQ> constexpr int AT_NVR = 2048 / (NWQ * 64);        // V float4s: 8 or 4
+
+// out[b][head * 128 + d][q] = O^T[d][q] / l for the lane's query q; register j of O[i] is d = 32i + 8(j>>2) + 4h + (j&3)
+__device__ __forceinline__ void at_store_out(float *__restrict__ out, int b, int HD, int head, int L, int q, int hh,
+                                             const f32x16 (&O)[4], float l_run)
+{
+    if (q < L) {
+        const float inv = 1.f / l_run;
+        float *o = out + ((size_t)b * HD + head * AT_D) * L + q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int d = i * 32 + 8 * (j >> 2) + 4 * hh + (j & 3);
+                o[(size_t)d * L] = O[i][j] * inv;
+            }
+    }
+}
+
 // Round 2: one LDS read per FOUR MFMAs (was one ds_read_b32 per MFMA), the next key tile's global loads in flight behind
 // the current tile's MFMAs (was: loaded after the barrier, fully exposed), the key mask as one ballot word per 32 keys
 // (was 16 LDS reads per block), the accumulator rescale skipped while the running maximum does not move.
@@ -43,8 +68,7 @@ __global__ __launch_bounds__(NWQ * 64, 2) void attention_fwd_kernel(const float 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hh = lane >> 5, r = lane & 31;
     const int b = blockIdx.z, head = blockIdx.y;
-    constexpr int KCH = AT_D * 64 / (NWQ * 64);   // K channels per staging thread: 32 (4 waves) or 16 (8)
-    constexpr int NVR = 2048 / (NWQ * 64);        // V float4s per staging thread: 8 or 4
+    constexpr int KCH = AT_KCH<NWQ>, NVR = AT_NVR<NWQ>;
     const int q0 = KSPLIT ? blockIdx.x * (NWQ * 16) + (wave >> 1) * 32 : blockIdx.x * (NWQ * 32) + wave * 32;
     const int HD = n_head * AT_D;
     const float *Q = qkv + ((size_t)b * 3 * HD + head * AT_D) * L;
@@ -223,18 +247,7 @@ __global__ __launch_bounds__(NWQ * 64, 2) void attention_fwd_kernel(const float 
 #pragma unroll
             for (int j = 0; j < 16; ++j) O[i][j] = O[i][j] * c0 + park[2 + 16 * i + j] * c1;
     }
-    const int q = q0 + r;
-    if (q < L) {
-        const float inv = 1.f / l_run;
-        float *o = out + ((size_t)b * HD + head * AT_D) * L + q;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int d = i * 32 + 8 * (j >> 2) + 4 * hh + (j & 3);
-                o[(size_t)d * L] = O[i][j] * inv;
-            }
-    }
+    at_store_out(out, b, HD, head, L, q0 + r, hh, O, l_run);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -269,7 +282,7 @@ __global__ __launch_bounds__(NWQ * 64, 2) void attention_fwd_f16_kernel(const fl
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hh = lane >> 5, r = lane & 31;
     const int b = blockIdx.z, head = blockIdx.y;
-    constexpr int KCH = AT_D * 64 / (NWQ * 64), NVR = 2048 / (NWQ * 64);   // staging shares, as in the fp32 kernel
+    constexpr int KCH = AT_KCH<NWQ>, NVR = AT_NVR<NWQ>;
     const int q0 = blockIdx.x * (NWQ * 32) + wave * 32;
     const int HD = n_head * AT_D;
     const float *Q = qkv + ((size_t)b * 3 * HD + head * AT_D) * L;
@@ -424,18 +437,7 @@ __global__ __launch_bounds__(NWQ * 64, 2) void attention_fwd_f16_kernel(const fl
             }
         }
     }
-    const int q = q0 + r;
-    if (q < L) {
-        const float inv = 1.f / l_run;
-        float *o = out + ((size_t)b * HD + head * AT_D) * L + q;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int d = i * 32 + 8 * (j >> 2) + 4 * hh + (j & 3);
-                o[(size_t)d * L] = O[i][j] * inv;
-            }
-    }
+    at_store_out(out, b, HD, head, L, q0 + r, hh, O, l_run);
 }
 
 // The one place the kernel's form is chosen (mg_attention_fwd and mg_attention_fwd_f16 switch on it).

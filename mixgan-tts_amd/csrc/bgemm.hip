@@ -209,15 +209,13 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float *__restrict__ S
         const float v = (pad && pad[k]) ? -INFINITY : s[k] * scale;
         m = fmaxf(m, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = mg_wave_max(m);
     float sum = 0.f;
     for (int k = lane; k < L; k += 64) {
         const float v = (pad && pad[k]) ? -INFINITY : s[k] * scale;
         sum += __expf(v - m);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    sum = mg_wave_sum(sum);
     const float inv = 1.f / sum;
     for (int k = lane; k < L; k += 64) {
         const float v = (pad && pad[k]) ? -INFINITY : s[k] * scale;
@@ -236,8 +234,7 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float *__re
     float *d = dP + row * L;
     float dot = 0.f;
     for (int k = lane; k < L; k += 64) dot = fmaf(p[k], d[k], dot);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+    dot = mg_wave_sum(dot);
     for (int k = lane; k < L; k += 64) d[k] = scale * p[k] * (d[k] - dot);
 }
 

@@ -45,6 +45,21 @@ __device__ __forceinline__ float mg_sigmoid(float x) { return __builtin_amdgcn_r
 // tanh via one exp: 1 - 2/(exp(2x)+1); exact limits at +-inf, abs err ~1e-7.
 __device__ __forceinline__ float mg_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 
+// Full 64-lane xor butterfly: every lane ends with the sum (the maximum) over the wave.  T: float, or double in pitch.hip.
+template <typename T>
+__device__ __forceinline__ T mg_wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float mg_wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
 template <int ACT>
 __device__ __forceinline__ float mg_act(float v)
 {

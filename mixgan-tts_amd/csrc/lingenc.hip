@@ -18,17 +18,6 @@
 #define LE_VCH 32     // keys per V chunk staged in LDS
 #define LE_LDS_MAX (64 * 1024)
 
-__device__ __forceinline__ float le_wave_max(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float le_wave_sum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 static size_t le_lds_bytes(int rows, int Lk)
 {
     return sizeof(float) * ((size_t)rows * LE_D + (size_t)rows * Lk + (size_t)LE_D * (LE_VCH + 1) +
@@ -114,10 +103,10 @@ __global__ __launch_bounds__(256) void le_attention_kernel(
         float mx = -INFINITY;
         if (!REL && prior) {    // log_softmax(scores) + log(prior^T + 1e-8)
             for (int j = lane; j < Lk; j += 64) mx = fmaxf(mx, Sr[j]);
-            mx = le_wave_max(mx);
+            mx = mg_wave_max(mx);
             float sum = 0.f;
             for (int j = lane; j < Lk; j += 64) sum += expf(Sr[j] - mx);
-            const float lsum = logf(le_wave_sum(sum));
+            const float lsum = logf(mg_wave_sum(sum));
             const float *pb = prior + (size_t)b * Lk * Lq + i;
             for (int j = lane; j < Lk; j += 64) Sr[j] = ((Sr[j] - mx) - lsum) + logf(pb[(size_t)j * Lq] + 1e-8f);
             mx = -INFINITY;
@@ -128,14 +117,14 @@ __global__ __launch_bounds__(256) void le_attention_kernel(
             if (!REL) logprob[ob + j] = s;
             mx = fmaxf(mx, s);
         }
-        mx = le_wave_max(mx);
+        mx = mg_wave_max(mx);
         float sum = 0.f;
         for (int j = lane; j < Lk; j += 64) {
             const float e = expf(Sr[j] - mx);
             Sr[j] = e;
             sum += e;
         }
-        sum = le_wave_sum(sum);
+        sum = mg_wave_sum(sum);
         if (REL && TRAIN) {
             const size_t pb = (((size_t)b * gridDim.y + h) * Lq + i) * Lk;
             for (int j = lane; j < Lk; j += 64) {

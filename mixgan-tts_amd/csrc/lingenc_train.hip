@@ -16,12 +16,6 @@
 #define LT_NREL (2 * LT_WMAX + 1)
 #define LT_SLOTS 32  // partial-sum slots of the d emb_rel_k / d emb_rel_v reduction
 
-__device__ __forceinline__ float lt_wave_sum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------ relative self-attention
 // One wave per score row (b, h, i), four rows per workgroup.  dPd (the bgemm's dO.V^T) arrives in dS and leaves as
 // the score gradient dS (unscaled by 1/sqrt(d)):
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(256) void lt_rel_rows_kernel(const float *__restric
         do1 = dob[(size_t)(lane + 64) * L];
     }
     for (int m = 0; m < nrel; ++m) {
-        const float s = lt_wave_sum(do0 * emb_v[m * LT_D + lane] + do1 * emb_v[m * LT_D + lane + 64]);
+        const float s = mg_wave_sum(do0 * emb_v[m * LT_D + lane] + do1 * emb_v[m * LT_D + lane + 64]);
         if (lane == 0) bt[wave][m] = s;
     }
     __syncthreads();
@@ -80,7 +74,7 @@ __global__ __launch_bounds__(256) void lt_rel_rows_kernel(const float *__restric
             if (band) bp[wave][m] = pd;
             dot = fmaf(p, dp, dot);
         }
-        dot = lt_wave_sum(dot);
+        dot = mg_wave_sum(dot);
         for (int j = lane; j < L; j += 64) {
             const int m = j - i + w;
             const bool ok = qv && valid[(size_t)b * L + j] != 0;
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256) void lt_w2p_rows_kernel(float *__restrict__ G,
         G[off + j] = dp;
         dot = fmaf(raw[off + j], dp, dot);
     }
-    dot = lt_wave_sum(dot);
+    dot = mg_wave_sum(dot);
     float tot = 0.f;
     for (int j = lane; j < Lk; j += 64) {
         float s = raw[off + j] * (G[off + j] - dot) + (d_logp ? d_logp[off + j] : 0.f);
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(256) void lt_w2p_rows_kernel(float *__restrict__ G,
         tot += s;
     }
     if (!prior) return;
-    tot = lt_wave_sum(tot);
+    tot = mg_wave_sum(tot);
     const float *pb = prior + (size_t)b * Lk * Lq + i;
     for (int j = lane; j < Lk; j += 64) {
         float s = 0.f;

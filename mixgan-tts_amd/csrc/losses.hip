@@ -157,8 +157,7 @@ __global__ __launch_bounds__(256) void mel_count_rows_kernel(const float *__rest
         const float *t = targ + (size_t)row * M;
         float tabs = 0.f;
         for (int m = lane; m < M; m += 64) tabs += fabsf(padded ? 0.f : t[m]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tabs += __shfl_xor(tabs, o, 64);
+        tabs = mg_wave_sum(tabs);
         acc += tabs != 0.f ? 1 : 0;
     }
     if (lane == 0) red[wave] = acc;

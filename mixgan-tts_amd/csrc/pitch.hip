@@ -17,13 +17,6 @@ constexpr int PN = MG_PITCH_N, PW = MG_PITCH_W, PK = MG_PITCH_K;
 constexpr int LPL = 9;      // lags per lane: lane l owns the lags 9 l .. 9 l + 8, 576 >= PN - PW + 1 in all
 constexpr float EMPTY_COST = 1e30f;
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Exclusive prefix sum over the lanes of one wave.
 __device__ __forceinline__ double wave_exclusive_scan(double v, int lane)
 {
@@ -79,8 +72,8 @@ __global__ __launch_bounds__(64) void yin_candidates_kernel(const float *__restr
         sq += (double)v * (double)v;
         if (n < PW) sqa += (double)v * (double)v;
     }
-    sq = wave_sum(sq);
-    const double e0 = wave_sum(sqa);
+    sq = mg_wave_sum(sq);
+    const double e0 = mg_wave_sum(sqa);
     if (lane == 0) rms[o] = (float)sqrt(sq * (1.0 / PN));
     __syncthreads();
     mg_fft1024(d, tw, lane);

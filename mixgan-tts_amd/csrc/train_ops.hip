@@ -194,8 +194,7 @@ extern "C" int mg_layernorm_cm_bwd(const float *pre, const float *dy, const floa
 // ---------------------------------------------------------------------------------------------
 static __device__ __forceinline__ float block_sum(float v, float *red)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = mg_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

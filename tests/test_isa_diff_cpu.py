@@ -76,6 +76,33 @@ def test_operand_order_only(tmp_path, capsys):
     assert _verdicts(tool, a, a.replace("s_and_b64 s[8:9], s[12:13], s[2:3]", "s_and_b64 s[10:11], s[2:3], s[12:13]"))["_Z3fooPf"] == "differs"
 
 
+def test_mad64_factors_commute(tmp_path, capsys):
+    tool = _tool()
+    mad = "v_mad_u64_u32 v[2:3], s[2:3], v5, s8, v[68:69]"
+    a = _asm([("_Z3fooPf", 0, _body(0, extra=(mad,)), FIG)])
+
+    def other(insn):
+        return _verdicts(tool, a, _asm([("_Z3fooPf", 0, _body(0, extra=(insn,)), FIG)]))["_Z3fooPf"]
+    # the two factors exchanged: destination pair, carry-out and addend as they were
+    b = _asm([("_Z3fooPf", 0, _body(0, extra=("v_mad_u64_u32 v[2:3], s[2:3], s8, v5, v[68:69]",)), FIG)])
+    assert _verdicts(tool, a, b) == {"_Z3fooPf": "operand-order only"}
+    assert _status(tool, tmp_path, a, b) == 0
+    assert "operand-order only  _Z3fooPf  [1 of 9 instructions]" in capsys.readouterr().out
+    signed = "v_mad_i64_i32 v[2:3], s[2:3], v5, v7, v[68:69]"
+    a_signed = _asm([("_Z3fooPf", 0, _body(0, extra=(signed,)), FIG)])
+    b_signed = _asm([("_Z3fooPf", 0, _body(0, extra=("v_mad_i64_i32 v[2:3], s[2:3], v7, v5, v[68:69]",)), FIG)])
+    assert _verdicts(tool, a_signed, b_signed) == {"_Z3fooPf": "operand-order only"}
+    # a swap that involves the addend is another product
+    c = _asm([("_Z3fooPf", 0, _body(0, extra=("v_mad_u64_u32 v[2:3], s[2:3], v5, v[68:69], s8",)), FIG)])
+    assert _verdicts(tool, a, c) == {"_Z3fooPf": "differs"}
+    assert _status(tool, tmp_path, a, c) == 1
+    # ... and so are exchanged factors with another addend, carry-out or destination pair, or the other signedness
+    assert other("v_mad_u64_u32 v[2:3], s[2:3], s8, v5, v[70:71]") == "differs"
+    assert other("v_mad_u64_u32 v[2:3], s[4:5], s8, v5, v[68:69]") == "differs"
+    assert other("v_mad_u64_u32 v[4:5], s[2:3], s8, v5, v[68:69]") == "differs"
+    assert other("v_mad_i64_i32 v[2:3], s[2:3], s8, v5, v[68:69]") == "differs"
+
+
 def test_differs(tmp_path, capsys):
     tool = _tool()
     a = _asm([("_Z3fooPf", 0, _body(0), FIG), ("_Z3barPf", 1, _body(1), FIG)])

@@ -8,7 +8,8 @@
 For every kernel symbol (optionally only those matching the regular expression `pattern`) one verdict:
     identical           the same instruction stream
     operand-order only  the same instruction sequence; the files differ only in the order of the two source operands
-                        of instructions on the list of commutative ALU ops below
+                        of instructions on the list of commutative ALU ops below, or of the two factors of a 64-bit
+                        multiply-add (v_mad_i64_i32, v_mad_u64_u32)
     differs             anything else (a kernel present in one file only included), with both instruction counts and
                         the sgpr / vgpr / spill figures of the code object metadata
 Comment and directive lines do not count, and local labels are compared by the position they mark, not by name.
@@ -24,6 +25,9 @@ COMMUTATIVE = frozenset(
     + ["v_%s%s" % (op, enc) for enc in ("_e32", "_e64", "")
        for op in ("and_b32", "or_b32", "xor_b32", "add_u32", "add_f32", "mul_f32", "min_f32", "max_f32", "mul_lo_u32",
                   "mul_hi_u32", "min_u32", "max_u32", "min_i32", "max_i32", "add_f64", "mul_f64")])
+
+# src0 * src1 + addend: the two factors commute, the addend does not take part
+MAD64 = frozenset("v_mad_%s%s" % (t, enc) for t in ("i64_i32", "u64_u32") for enc in ("_e64", ""))
 
 META_KEYS = ("sgpr_count", "vgpr_count", "sgpr_spill_count", "vgpr_spill_count")
 _LABEL = re.compile(r"^([.\w$]+):$")
@@ -79,7 +83,11 @@ def _operands(insn):
 def _swapped(x, y):
     """Instructions x, y: the same commutative op on the same destination with its two sources exchanged?"""
     (mx, ox), (my, oy) = _operands(x), _operands(y)
-    return mx == my and mx in COMMUTATIVE and len(ox) == 3 and len(oy) == 3 and ox[0] == oy[0] and ox[1:] == oy[:0:-1]
+    if mx != my or len(ox) != len(oy):
+        return False
+    if mx in MAD64:     # dst pair, carry-out, src0, src1, addend: only the two factors may change places
+        return len(ox) == 5 and ox[:2] == oy[:2] and ox[4] == oy[4] and ox[2:4] == oy[3:1:-1]
+    return mx in COMMUTATIVE and len(ox) == 3 and ox[0] == oy[0] and ox[1:] == oy[:0:-1]
 
 
 def verdict(a, b):
