@@ -307,21 +307,9 @@ class GaussianDiffusion(nn.Module):
             trace.append(ops.transpose_bml(self._bml(x), True))
         return trace
 
-    # HotPathTrainer sets this around its D-phase forward: the next (grad-enabled) forward is launched together with it
-    # (Denoiser.run_pair).  Off by default: it draws that second forward's randomness early.  pair_inputs: the
-    # (cond, spk_emb, coarse_mel) that grad-enabled forward will be called with (the reference's two model calls of a
-    # step see different conditioners when the encoder has dropout, train.py:133,153); None = the same as this call's.
-    pair_forward = False
-    pair_inputs = None
-    _pair_stash = None
-
-    @staticmethod
-    def _pair_key(mel, cond, spk, mel_mask, coarse_mel):
-        return (mel.data_ptr(), mel._version, cond.data_ptr(), cond._version, mel_mask.data_ptr(), tuple(mel.shape),
-                None if coarse_mel is None else coarse_mel.data_ptr(), None if spk is None else spk.data_ptr())
-
-    def forward(self, mel, cond, spk_emb, mel_mask, coarse_mel=None, clip_denoised=True):
-        """model/diffusion.py:187-226.  mel [B,L,M]|None, cond [B,L,H], mel_mask bool [B,L] True = pad."""
+    def forward(self, mel, cond, spk_emb, mel_mask, coarse_mel=None, clip_denoised=True, *, pair=None):
+        """model/diffusion.py:187-226.  mel [B,L,M]|None, cond [B,L,H], mel_mask bool [B,L] True = pad.
+        pair: the ForwardPair of a GAN step, given to its no-grad call and then to its grad-enabled one."""
         B = cond.shape[0]
         dev = cond.device
         if dev.type != "cuda":
@@ -357,42 +345,33 @@ class GaussianDiffusion(nn.Module):
             x_t_ = ops.diffuse(melc, t_, self._bml(self._randn((B, 1, M, L), dev)), keep, buf)
             x_prev_ = ops.diffuse(melc, (t_ - 1).contiguous(), self._bml(self._randn((B, 1, M, L), dev)), keep, buf)
             return t_, x_t_, x_prev_, self._bml(self._randn((B, 1, M, L), dev))
-        pair_key = self._pair_key(mel, cond, spk, mel_mask, coarse_mel)
-        stash, self._pair_stash = self._pair_stash, None
         if grad:
             from .autograd import denoise_and_posterior
-            pre = None
-            if (stash is not None and stash["key"] == pair_key
-                    and self.denoise_fn.packed_weights(with_backward=True) is stash["packed"]
-                    and self.denoise_fn._packed_key == stash["packed_key"]):
-                # this forward was already launched next to the previous no-grad one (pair_forward): adopt its draws,
-                # its output and its saved activations
-                t, x_t_b, x_prev_b, post_noise = stash["draws"]
-                pre = (stash["x0"], stash["ws"]) if stash["ws"] is not None else None
+            ahead = pair.adopt(self.denoise_fn) if pair is not None else None
+            if ahead is not None:
+                # this forward was already launched next to the step's no-grad one: its draws, its output and its saved
+                # activations
+                (t, x_t_b, x_prev_b, post_noise), pre = ahead
             else:
-                if stash is not None and stash["ws"] is not None:
-                    stash["ws"]._mg_busy = False      # never used: hand the workspace back
-                t, x_t_b, x_prev_b, post_noise = draw()
+                (t, x_t_b, x_prev_b, post_noise), pre = draw(), None
             x0c, xpp = denoise_and_posterior(self, x_t_b, t, cond_t, spk, post_noise, keep, clip_denoised,
                                              coarse_mel if self.model == "shallow" else None, pre=pre)
             from .autograd import transpose_to_blm
             return (transpose_to_blm(x0c), ops.transpose_bml(x_t_b, True), ops.transpose_bml(x_prev_b, True),
                     transpose_to_blm(xpp), t)
-        if stash is not None and stash["ws"] is not None:
-            stash["ws"]._mg_busy = False
         t, x_t_b, x_prev_b, post_noise = draw()
         x0 = None
-        if self.pair_forward and self.denoise_fn.precision == "fp32":
+        if pair is not None and not pair.begun and self.denoise_fn.precision == "fp32":
             # The GAN step runs this forward twice on the same weights -- here without gradient (train.py:133), then
             # with (train.py:153), with fresh t / noise.  Draw the second set now (nothing else consumes randomness in
-            # between) and run both in one launch; the grad-enabled call that follows picks its half up above.
+            # between) and run both in one launch; the grad-enabled call that follows adopts its half above.
             draws2 = draw()
-            cond_g, spk_g, coarse_g = self.pair_inputs if self.pair_inputs is not None else (cond, spk_emb, coarse_mel)
+            cond_g, spk_g = pair.inputs
             spk_g = spk_g.contiguous() if spk_g is not None else None
             cond_t2 = spk2 = None
             if cond_g is not cond:
                 if cond_g.shape != cond.shape:
-                    raise _lib.MixganHipError("pair_inputs: the two phases' conditioners differ in shape")
+                    raise _lib.MixganHipError("ForwardPair: the two phases' conditioners differ in shape")
                 cond_t2 = ops.transpose_bml(cond_g.detach().contiguous(), False)
             if spk_g is not None and spk is not None and spk_g.data_ptr() != spk.data_ptr():
                 spk2 = spk_g.detach()
@@ -401,10 +380,7 @@ class GaussianDiffusion(nn.Module):
                 x0 = both[0]
             # (not a single-launch shape: the second forward still uses these draws, so that the random stream is
             # consumed in the same order either way)
-            pair_key = self._pair_key(mel, cond_g, spk_g, mel_mask, coarse_g)
-            self._pair_stash = {"key": pair_key, "draws": draws2, "x0": None if both is None else both[1],
-                                "ws": None if both is None else both[2],
-                                "packed": self.denoise_fn._packed, "packed_key": self.denoise_fn._packed_key}
+            pair.record(self.denoise_fn, draws2, both)
         if x0 is None:
             x0 = self.denoise_fn.run(x_t_b, t, cond_t, spk)
         if self.model != "shallow":
@@ -416,6 +392,43 @@ class GaussianDiffusion(nn.Module):
             _, x0c = ops.posterior_sample(x0, x_t_b, t, post_noise, keep, buf, clip=clip_denoised, want_x0c=True)
         tb = lambda a: ops.transpose_bml(a, True)
         return tb(x0c), tb(x_t_b), tb(x_prev_b), tb(xpp), t
+
+
+class ForwardPair:
+    """What the two generator forwards of one GAN step share (HotPathTrainer.step makes one per step and hands it to both
+    `G(..., pair=)` calls): both are launched together by the first, no-grad call (Denoiser.run_pair: same weights, only
+    D is stepped in between), which draws the second call's randomness right behind its own.  inputs: the (cond, spk_emb)
+    the grad-enabled call will be made with (the reference's two model calls of a step see different
+    conditioners when the encoder has dropout, train.py:133,153)."""
+
+    def __init__(self, inputs):
+        self.inputs = inputs
+        self.begun = self.consumed = False
+        self.draws = self.x0 = self.ws = self.packed = self.packed_key = None
+
+    def record(self, den, draws, both):
+        """The second call's draws and, when run_pair took the shape, its output and workspace on these weights."""
+        self.begun = True
+        self.draws, self.packed, self.packed_key = draws, den._packed, den._packed_key
+        self.x0, self.ws = (None, None) if both is None else both[1:]
+
+    def adopt(self, den):
+        """(draws, (x0, ws) | None) for the grad-enabled call if the packed weights are still the ones recorded; None
+        otherwise (nothing recorded, or repacked since: the workspace goes back and the call draws afresh)."""
+        got = self.draws, (None if self.ws is None else (self.x0, self.ws))
+        if self.draws is None or den.packed_weights(with_backward=True) is not self.packed \
+                or den._packed_key != self.packed_key:
+            self.release()
+            return None
+        self.inputs = self.draws = self.x0 = self.ws = self.packed = None
+        self.consumed = True
+        return got
+
+    def release(self):
+        """Drop what no call adopted: its workspace was never used and is free again."""
+        if self.ws is not None:
+            self.ws._mg_busy = False
+        self.inputs = self.draws = self.x0 = self.ws = self.packed = None
 
 
 class _DiffuseTraceFn(torch.autograd.Function):

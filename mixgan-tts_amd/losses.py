@@ -1,6 +1,9 @@
 """Losses that enter the hot path's backward (model/loss.py:12-30, 221-242, 255-259): LSGAN
 on the last feature map of the JCU discriminator, feature matching over the first four maps and
 the masked mel L1.  Reductions and their gradients run in the HIP library."""
+import collections
+import ctypes
+
 import torch
 
 from . import _lib
@@ -64,73 +67,113 @@ def _multi_scratch(dev):
     return _SCRATCH[key]
 
 
-class _WeightedMeansFn(torch.autograd.Function):
+# One entry of a loss table (MgLossTerm): mode (_lib.MG_LOSSMODE_*), c, weight, group; x: which tensor, rows [lo, hi) of
+# it (hi None: the whole tensor); y: which tensor holds the L1 target (x itself, or another one: it gets no gradient), from
+# row y_lo on; den: a host denominator in place of the term's element count.
+_Term = collections.namedtuple("_Term", "mode c weight group x lo hi y y_lo den", defaults=(0, None, None, 0, None))
+
+
+def _loss_table(spec, ts, grads=None):
+    """(MgLossTerm array of `spec` over the contiguous tensors `ts`, its denominators as a double array or None).
+    grads: per tensor the gradient buffer its terms write into, or None (the forward)."""
+    nt = len(spec)
+    terms = (_lib.LossTerm * nt)()
+    for k, s in enumerate(spec):
+        x, y = ts[s.x], None if s.y is None else ts[s.y]
+        if s.hi is None:            # the whole tensor, as one row
+            lo, rows, per = 0, 1, x.numel()
+            if y is not None and (y.shape != x.shape or s.y_lo != 0):
+                raise ValueError("term %d: shapes %s vs %s" % (k, tuple(x.shape), tuple(y.shape)))
+        else:
+            lo, rows, per = s.lo, s.hi - s.lo, x.numel() // max(1, x.shape[0])
+            if not (0 <= lo < s.hi <= x.shape[0]) or (y is not None and not (
+                    0 <= s.y_lo and s.y_lo + rows <= y.shape[0] and (y is x or y.shape[1:] == x.shape[1:]))):
+                raise ValueError("term %d: batch range outside the tensor" % k)
+        d = grads[s.x] if grads is not None else None
+        terms[k] = _lib.LossTerm(fptr(x).value + 4 * lo * per, None if y is None else fptr(y).value + 4 * s.y_lo * per,
+                                 None if d is None else fptr(d).value + 4 * lo * per, rows * per, float(s.c),
+                                 float(s.weight), int(s.mode), int(s.group))
+    den = [float(s.den) for s in spec if s.den is not None]
+    if den and len(den) != nt:
+        raise ValueError("a denominator for every term or for none")
+    return terms, (ctypes.c_double * nt)(*den) if den else None
+
+
+_ENTRY = {("fwd", False): "mg_multi_loss_fwd", ("fwd", True): "mg_multi_loss_fwd_den",
+          ("bwd", False): "mg_multi_loss_bwd", ("bwd", True): "mg_multi_loss_bwd_den"}
+
+
+def _launch_means(which, table, *args):
+    """The plain entry point, or the _den one when the table carries denominators: the one place that chooses."""
+    terms, den = table
+    fn = getattr(_lib.lib(), _ENTRY[which, den is not None])
+    check(fn(terms, len(terms), *(() if den is None else (den,)), *args, stream_ptr()))
+
+
+class _MeansFn(torch.autograd.Function):
     """total = sum_k weight_k * mean_k in ONE launch (mg_multi_loss_fwd), gradients of all terms in one more.
-    spec: tuple of (mode, c, weight, group) per term, mode 0 = mean (x - c)^2, mode 1 = mean |x - y| with gradient
-    to x only, mode 2 = mean max(0, 1 + c x), mode 3 = mean x; tensors: the x of every term, then the y of the mode-1 terms in order.
-    Returns the [1 + groups + nterms] result vector (total, group subtotals, per-term means); differentiate [0]."""
+    spec: tuple of _Term over `tensors` -- MSE = mean (x - c)^2, L1 = mean |x - y| with gradient to x only, HINGE = mean
+    max(0, 1 + c x), MEAN = mean x, each over rows [lo, hi) of its x.  Returns the [1 + groups + nterms] result vector
+    (total, group subtotals, per-term means); differentiate [0].
+    The trainer runs D(fake) and D(real) as one pass over 2B items; slicing the maps apart for the losses made autograd
+    rebuild every map's gradient from two zero-padded halves (a fill, a copy and an add per half and map: ~55 launches per
+    step).  Here the maps go in whole and the terms name their rows: a tensor that one term writes over all of its rows
+    gets an empty gradient buffer, every other one a view into ONE zero-filled flat buffer (rows no term writes: zero).
+    No two terms may write the same rows."""
 
     @staticmethod
     def forward(ctx, spec, *tensors):
         nt = len(spec)
         if nt < 1 or nt > _lib.MG_LOSS_MAX_TERMS:
             raise ValueError("1..%d terms per call" % _lib.MG_LOSS_MAX_TERMS)
-        xs = [t.contiguous() for t in tensors[:nt]]
-        ys = iter([t.detach().contiguous() for t in tensors[nt:]])
-        targets = [next(ys) if s[0] == 1 else None for s in spec]
-        terms = (_lib.LossTerm * nt)()
-        for k, (s, x, y) in enumerate(zip(spec, xs, targets)):
-            if y is not None and y.shape != x.shape:
-                raise ValueError("term %d: shapes %s vs %s" % (k, tuple(x.shape), tuple(y.shape)))
-            terms[k] = _lib.LossTerm(fptr(x).value, fptr(y, True).value if y is not None else None, None, x.numel(),
-                                     float(s[1]), float(s[2]), int(s[0]), int(s[3]))
-        dev = xs[0].device
+        ts = [t.contiguous() for t in tensors]
+        table = _loss_table(spec, ts)            # refuses a tensor off the GPU before anything is allocated there
+        dev = ts[0].device
         out = torch.empty(1 + _lib.MG_LOSS_GROUPS + nt, device=dev, dtype=torch.float32)
-        check(_lib.lib().mg_multi_loss_fwd(terms, nt, fptr(_multi_scratch(dev)), fptr(out), stream_ptr()))
+        _launch_means("fwd", table, fptr(_multi_scratch(dev)), fptr(out))
         ctx.spec = spec
-        ctx.save_for_backward(*xs, *[y for y in targets if y is not None])
+        ctx.save_for_backward(*ts)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        spec, nt = ctx.spec, len(ctx.spec)
-        saved = ctx.saved_tensors
-        xs, ys = saved[:nt], iter(saved[nt:])
-        terms = (_lib.LossTerm * nt)()
-        grads = []
-        for k, (s, x) in enumerate(zip(spec, xs)):
-            y = next(ys) if s[0] == 1 else None
-            d = torch.empty_like(x) if ctx.needs_input_grad[1 + k] else None
-            grads.append(d)
-            terms[k] = _lib.LossTerm(fptr(x).value, fptr(y).value if y is not None else None,
-                                     fptr(d).value if d is not None else None, x.numel(), float(s[1]), float(s[2]),
-                                     int(s[0]), int(s[3]))
+        spec, ts = ctx.spec, ctx.saved_tensors
+        writers = [[] for _ in ts]
+        for s in spec:
+            if ctx.needs_input_grad[1 + s.x]:
+                writers[s.x].append(s)
+        whole = [len(w) == 1 and (w[0].hi is None or (w[0].lo == 0 and w[0].hi == t.shape[0]))
+                 for w, t in zip(writers, ts)]
+        sizes = [t.numel() if w and not wh else 0 for w, wh, t in zip(writers, whole, ts)]
+        flat = torch.zeros(sum(sizes), device=ts[0].device, dtype=torch.float32) if any(sizes) else None
+        grads, at = [], 0
+        for w, wh, n, t in zip(writers, whole, sizes, ts):
+            grads.append(None if not w else torch.empty_like(t) if wh else flat[at:at + n].view_as(t))
+            at += n
         # only the total (element 0) is a loss; the subtotals and means are read-outs of the same numbers
-        check(_lib.lib().mg_multi_loss_bwd(terms, nt, fptr(g[:1].contiguous()), stream_ptr()))
-        return (None, *grads, *([None] * (len(saved) - nt)))
+        _launch_means("bwd", _loss_table(spec, ts, grads), fptr(g[:1].contiguous()))
+        return (None, *grads)
+
+
+_KINDS = {"mse": _lib.MG_LOSSMODE_MSE, "l1": _lib.MG_LOSSMODE_L1, "hinge": _lib.MG_LOSSMODE_HINGE,
+          "mean": _lib.MG_LOSSMODE_MEAN}
 
 
 def weighted_means(terms):
     """terms: list of ("mse", x, c, weight[, group]) / ("l1", x, y, weight[, group]) / ("hinge", x, sign, weight[, group])
     = weight * mean(max(0, 1 + sign * x)) / ("mean", x, None, weight[, group]).  Returns the result vector of
-    _WeightedMeansFn: [0] total (differentiable w.r.t. every x), [1:1+4] group subtotals, then per-term means."""
-    spec, xs, ys = [], [], []
-    for t in terms:
+    _MeansFn: [0] total (differentiable w.r.t. every x), [1:1+4] group subtotals, then per-term means."""
+    spec, ys = [], []
+    for k, t in enumerate(terms):
         kind, x, other, w = t[:4]
-        grp = t[4] if len(t) > 4 else 0
-        if kind == "mse":
-            spec.append((0, float(other), float(w), grp))
-        elif kind == "l1":
-            spec.append((1, 0.0, float(w), grp))
-            ys.append(other)
-        elif kind == "hinge":
-            spec.append((_lib.MG_LOSSMODE_HINGE, float(other), float(w), grp))
-        elif kind == "mean":
-            spec.append((_lib.MG_LOSSMODE_MEAN, 0.0, float(w), grp))
-        else:
+        if kind not in _KINDS:
             raise ValueError(kind)
-        xs.append(x)
-    return _WeightedMeansFn.apply(tuple(spec), *xs, *ys)
+        l1 = kind == "l1"
+        spec.append(_Term(_KINDS[kind], 0.0 if l1 or other is None else float(other), float(w),
+                          t[4] if len(t) > 4 else 0, k, y=len(terms) + len(ys) if l1 else None))
+        if l1:
+            ys.append(other)
+    return _MeansFn.apply(tuple(spec), *[t[1] for t in terms], *ys)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -210,90 +253,16 @@ def melgan_feature_loss(D_real, D_fake):
     return _means_in_calls(terms)[0]
 
 
-class _RangeMeansFn(torch.autograd.Function):
-    """weighted_means over BATCH RANGES of whole feature maps: term k reads rows [a_lo, a_hi) of tensor `ti` (mode 0:
-    mean (x - c)^2; mode 1: mean |x[a] - x[b]| against rows [b_lo, b_lo + a_hi - a_lo) of the same tensor, gradient to
-    the a-range only).  The trainer runs D(fake) and D(real) as one pass over 2B items; slicing the maps apart for the
-    losses made autograd rebuild every map's gradient from two zero-padded halves (a fill, a copy and an add per half
-    and map: ~55 launches per step).  Here the maps go in whole, and the backward is one zero-fill of one flat buffer
-    plus one launch that writes every term's gradient into its range.
-    spec.den (a _Spec, optional): one host denominator per term in place of the term's element count."""
-
-    @staticmethod
-    def forward(ctx, spec, *tensors):
-        nt = len(spec)
-        den = getattr(spec, "den", None)
-        if nt < 1 or nt > _lib.MG_LOSS_MAX_TERMS:
-            raise ValueError("1..%d terms per call" % _lib.MG_LOSS_MAX_TERMS)
-        xs = [t.contiguous() for t in tensors]
-        terms = (_lib.LossTerm * nt)()
-        for k, (ti, mode, c, w, grp, a_lo, a_hi, b_lo) in enumerate(spec):
-            x = xs[ti]
-            per = x[0].numel()
-            n = (a_hi - a_lo) * per
-            if not (0 <= a_lo < a_hi <= x.shape[0]) or (mode == 1 and not (0 <= b_lo and b_lo + a_hi - a_lo <= x.shape[0])):
-                raise ValueError("term %d: batch range outside the tensor" % k)
-            base = fptr(x).value
-            terms[k] = _lib.LossTerm(base + 4 * a_lo * per, (base + 4 * b_lo * per) if mode == 1 else None, None, n,
-                                     float(c), float(w), int(mode), int(grp))
-        dev = xs[0].device
-        out = torch.empty(1 + _lib.MG_LOSS_GROUPS + nt, device=dev, dtype=torch.float32)
-        if den is None:
-            check(_lib.lib().mg_multi_loss_fwd(terms, nt, fptr(_multi_scratch(dev)), fptr(out), stream_ptr()))
-        else:
-            check(_lib.lib().mg_multi_loss_fwd_den(terms, nt, _den_array(den, nt), fptr(_multi_scratch(dev)), fptr(out),
-                                                   stream_ptr()))
-        ctx.spec = spec
-        ctx.save_for_backward(*xs)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        spec, nt = ctx.spec, len(ctx.spec)
-        xs = ctx.saved_tensors
-        need = [ctx.needs_input_grad[1 + i] for i in range(len(xs))]
-        sizes = [x.numel() if nd else 0 for x, nd in zip(xs, need)]
-        flat = torch.zeros(sum(sizes), device=xs[0].device, dtype=torch.float32)      # rows no term writes: zero
-        grads, at = [], 0
-        for x, nd, n in zip(xs, need, sizes):
-            grads.append(flat[at:at + n].view_as(x) if nd else None)
-            at += n
-        terms = (_lib.LossTerm * nt)()
-        for k, (ti, mode, c, w, grp, a_lo, a_hi, b_lo) in enumerate(spec):
-            x = xs[ti]
-            per = x[0].numel()
-            base = fptr(x).value
-            da = (fptr(grads[ti]).value + 4 * a_lo * per) if grads[ti] is not None else None
-            terms[k] = _lib.LossTerm(base + 4 * a_lo * per, (base + 4 * b_lo * per) if mode == 1 else None, da,
-                                     (a_hi - a_lo) * per, float(c), float(w), int(mode), int(grp))
-        den = getattr(spec, "den", None)
-        if den is None:
-            check(_lib.lib().mg_multi_loss_bwd(terms, nt, fptr(g[:1].contiguous()), stream_ptr()))
-        else:
-            check(_lib.lib().mg_multi_loss_bwd_den(terms, nt, _den_array(den, nt), fptr(g[:1].contiguous()),
-                                                   stream_ptr()))
-        return (None, *grads)
-
-
-class _Spec(tuple):
-    """The spec tuple of _RangeMeansFn with the optional per-term denominators riding along."""
-    den = None
-
-
-def _den_array(den, nt):
-    import ctypes
-    if len(den) != nt:
-        raise ValueError("one denominator per term: %d for %d terms" % (len(den), nt))
-    return (ctypes.c_double * nt)(*[float(d) for d in den])
-
-
 def _range_means(spec, tensors, den=None):
-    """spec entries (tensor index, mode, c, weight, group, a_lo, a_hi, b_lo); no two terms may write the same rows.
+    """_MeansFn over BATCH RANGES of whole feature maps.  spec entries (tensor index, mode, c, weight, group, a_lo, a_hi,
+    b_lo): the term reads rows [a_lo, a_hi) of its tensor, L1 against rows [b_lo, b_lo + a_hi - a_lo) of the same tensor.
     den: one host denominator per term (mg_multi_loss_fwd_den); None = each term's own element count (a mean)."""
-    spec = _Spec(spec)
-    if den is not None:
-        spec.den = tuple(float(d) for d in den)
-    return _RangeMeansFn.apply(spec, *tensors)
+    if den is not None and len(den) != len(spec):
+        raise ValueError("one denominator per term: %d for %d terms" % (len(den), len(spec)))
+    return _MeansFn.apply(tuple(
+        _Term(mode, c, w, grp, ti, a_lo, a_hi, ti if mode == _lib.MG_LOSSMODE_L1 else None, b_lo,
+              None if den is None else den[k])
+        for k, (ti, mode, c, w, grp, a_lo, a_hi, b_lo) in enumerate(spec)), *tensors)
 
 
 def _global_den(spec, tensors, B, n_total):
@@ -308,8 +277,9 @@ def d_loss_total_2b(logit_cond, logit_uncond, B, n_total=None):
     """d_loss_total on the last maps of ONE discriminator pass over [fake (rows 0..B-1); real (rows B..2B-1)].
     n_total: the item count of the whole batch when these B items are one rank's shard of it -- every mean then divides
     by the whole batch's element count (the maps of all ranks have the same length), and the result is the rank's share."""
-    spec = [(0, 0, 1.0, 0.5, 0, B, 2 * B, 0), (1, 0, 1.0, 0.5, 0, B, 2 * B, 0),
-            (0, 0, 0.0, 0.5, 1, 0, B, 0), (1, 0, 0.0, 0.5, 1, 0, B, 0)]
+    MSE = _lib.MG_LOSSMODE_MSE
+    spec = [(0, MSE, 1.0, 0.5, 0, B, 2 * B, 0), (1, MSE, 1.0, 0.5, 0, B, 2 * B, 0),
+            (0, MSE, 0.0, 0.5, 1, 0, B, 0), (1, MSE, 0.0, 0.5, 1, 0, B, 0)]
     tensors = [logit_cond, logit_uncond]
     out = _range_means(spec, tensors, _global_den(spec, tensors, B, n_total))
     return out[0], out[1], out[2]
@@ -322,10 +292,11 @@ def g_adv_fm_total_2b(cond_maps, uncond_maps, B, lambda_fm, n_layers=5, n_total=
     w = lambda_fm * (4.0 / (n_layers + 1)) * 0.5
     nm = len(cond_maps)
     tensors = list(cond_maps) + list(uncond_maps)
-    spec = [(nm - 1, 0, 1.0, 0.5, 0, 0, B, 0), (2 * nm - 1, 0, 1.0, 0.5, 0, 0, B, 0)]
+    MSE, L1 = _lib.MG_LOSSMODE_MSE, _lib.MG_LOSSMODE_L1
+    spec = [(nm - 1, MSE, 1.0, 0.5, 0, 0, B, 0), (2 * nm - 1, MSE, 1.0, 0.5, 0, 0, B, 0)]
     for j in range(nm - 1):
-        spec.append((j, 1, 0.0, w, 1, 0, B, B))
-        spec.append((nm + j, 1, 0.0, w, 1, 0, B, B))
+        spec.append((j, L1, 0.0, w, 1, 0, B, B))
+        spec.append((nm + j, L1, 0.0, w, 1, 0, B, B))
     out = _range_means(spec, tensors, _global_den(spec, tensors, B, n_total))
     return out[0], out[1], out[2]
 

@@ -20,6 +20,7 @@ import os
 import torch
 
 from . import losses
+from .diffusion import ForwardPair
 from .distributed import GradBucket, ShardCounts, exchange_batch_shape, is_distributed
 from .optimizer import FlatAdam
 
@@ -100,6 +101,7 @@ class HotPathTrainer:
     pair_forwards = True      # False: the two generator forwards of a step as two launches
     overlap_exchange = True   # multi-GPU: start the all-reduce of the k=3 gradients while the backward is still running
     grad_hook = None      # optional callable(name, bucket) after the gradient exchange, before clipping (tests, logging)
+    last_pair = None      # read-out: the last training step's diffusion.ForwardPair (None: its forwards were not paired)
 
     def _update(self, bucket, opt):
         # no-op on one process; waits for chunks already in flight
@@ -202,7 +204,6 @@ class HotPathTrainer:
         cond_maps, uncond_maps = self.D(both(x_ts, x_ts), both(x_fake, x_real), both(spk, spk), both(t, t))
         return cond_maps, uncond_maps, B
 
-    # ------------------------------------------------------------------ the two phases on given generator outputs
     # ------------------------------------------------------------------ exact_shards: what a step shares with the ranks
     @staticmethod
     def _pad_frames(x, L, value=0):
@@ -228,12 +229,16 @@ class HotPathTrainer:
             counts.n_items = shape.n_total
         return _Shard(shape.n_total, shape.max_len, counts)
 
-    def _exact_inputs(self, shape, counts, mel, cond, mel_pad_mask, *more):
-        """_exact_begin + the inputs padded to the whole batch's length + the count of mel rows under way."""
+    def _exact_inputs(self, shape, counts, mel, cond, mel_pad_mask, coarse_mel, *more):
+        """The head of step / evaluate_step: (None, the inputs) off exact mode, else _exact_begin + the inputs padded to
+        the whole batch's length, with the count of the mel rows under way."""
+        inputs = (mel, cond, mel_pad_mask, coarse_mel) + more
+        if not self._exact(shape, counts):
+            return None, inputs
         ex = self._exact_begin(shape, mel_pad_mask.shape[0], mel_pad_mask.shape[1], mel_pad_mask.device, counts)
-        L = ex.max_len
-        padded = [self._pad_frames(x, L) for x in (mel, cond)] + [self._pad_frames(mel_pad_mask, L, True)]
-        padded += [self._pad_frames(x, L) for x in more]
+        padded = [self._pad_frames(x, ex.max_len) for x in inputs]
+        padded[2] = self._pad_frames(mel_pad_mask, ex.max_len, True)      # the mask pads with True = pad
+        self._exact_count(ex, padded[3 if self.G.model == "shallow" else 0], padded[2])
         return ex, padded
 
     def _exact_count(self, ex, target, mel_pad_mask):
@@ -283,9 +288,81 @@ class HotPathTrainer:
             g_loss = g_loss + extra_loss
         return g_loss, parts
 
+    # ------------------------------------------------------------------ the one walk: train.py:131-184 / evaluate.py:76-120
+    def _walk(self, d_forward, g_forward, ex, train):
+        """D phase -> (D update) -> G phase -> (G update).  d_forward() -> (x_ts, x_prevs, x_prev_preds, spk, t) is the
+        D phase's generator forward; g_forward() -> _g_loss's arguments up to extra_loss is the G phase's, called only
+        after the discriminator was stepped.  ex: the step's shard context (exact_shards) or None.  train=False: the
+        losses only (the caller holds no_grad)."""
+        # train.py:133 builds (and discards) the generator's autograd graph here; every output is detached
+        # before use (train.py:135-137), so running it under no_grad gives identical results and skips
+        # the activation saves of the grad-enabled forward.
+        with torch.no_grad():
+            d_in = d_forward()
+        d_loss = self._d_loss(*d_in, ex)
+        if train:
+            self._model_update(d_loss, self.bucketD, self.optD)
+        g_loss, out = self._g_loss(*g_forward(), ex)
+        if train:
+            self._model_update(g_loss, self.bucketG, self.optG)
+            self.step_no += 1
+        out["d_loss"] = d_loss.detach()
+        return out
+
+    def _exact(self, shape, counts):
+        """exact_shards, after checking that only an exact trainer was given a shape."""
+        if not self.exact_shards and (shape is not None or counts is not None):
+            raise ValueError("shape= / counts= belong to HotPathTrainer(exact_shards=True)")
+        return self.exact_shards
+
+    def _walk_tensors(self, train, ex, mel, cond, spk, mel_pad_mask, coarse_mel, extra_loss, cond_d, spk_d, coarse_mel_d):
+        """step / evaluate_step: the walk with direct G(...) calls on inputs that _exact_inputs has seen."""
+        G = self.G
+        cd = cond if cond_d is None else cond_d
+        sd = spk if spk_d is None else spk_d
+        cmd = coarse_mel if coarse_mel_d is None else coarse_mel_d
+        # the D phase's forward is launched TOGETHER with the G phase's (same weights: only D is stepped in between;
+        # diffusion.ForwardPair): one grid of 64-frame tiles over both instead of two of 32-frame tiles
+        pair = None
+        if train and self.pair_forwards and os.environ.get("MG_PAIR_FORWARDS", "1") != "0":
+            pair = ForwardPair((cond, spk))
+        self.last_pair = pair      # holds no tensor once consumed or released
+
+        def d_forward():           # train.py:133-146
+            _, x_ts, x_prevs, x_prev_preds, t = G(mel, cd, sd, mel_pad_mask, cmd, pair=pair)
+            return x_ts, x_prevs, x_prev_preds, sd, t
+
+        def g_forward():           # train.py:153-184
+            x0, x_ts, x_prevs, x_prev_preds, t = G(mel, cond, spk, mel_pad_mask, coarse_mel, pair=pair)
+            return x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss
+        try:
+            return self._walk(d_forward, g_forward, ex, train)
+        finally:
+            if pair is not None:
+                pair.release()
+
+    def _walk_model(self, train, model, batch, upstream_loss, ex):
+        """step_from_model / evaluate_from_model: the walk with one `model(*(batch[2:]))` per phase."""
+        shallow = self.G.model == "shallow"
+
+        def d_forward():           # every D-phase use is detached (train.py:135-137)
+            output, *_ = model(*(batch[2:]))
+            return self._unpack(output)[1:6]
+
+        def g_forward():
+            output, p_targets, _ = model(*(batch[2:]))
+            batch[9] = p_targets                     # train.py:155
+            x0, x_ts, x_prevs, x_prev_preds, spk, t, mel_pad_mask, slot15 = self._unpack(output)
+            mel = batch[11][:, :mel_pad_mask.shape[1], :]
+            if ex is not None and shallow:
+                self._exact_count(ex, slot15, mel_pad_mask)
+            extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
+            return x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, slot15 if shallow else None, extra
+        return self._walk(d_forward, g_forward, ex, train)
+
     # ------------------------------------------------------------------ train.py:131-184 on a given conditioner
     def step(self, mel, cond, spk, mel_pad_mask, coarse_mel=None, extra_loss=None, cond_d=None, spk_d=None,
-             coarse_mel_d=None, shape=None, counts=None, _ex=None):
+             coarse_mel_d=None, shape=None, counts=None):
         """One D phase + one G phase on a batch.  mel [B,L,M]; cond [B,L,H]; mel_pad_mask True = pad.
         cond_d / spk_d / coarse_mel_d: the D phase's generator inputs when they differ from the G phase's -- the
         reference calls `model(*(batch[2:]))` once per phase (train.py:133,153), i.e. the train-mode linguistic encoder
@@ -304,47 +381,10 @@ class HotPathTrainer:
         exact_shards only -- shape: the whole batch's distributed.BatchShape (exchanged here when None: one host round
         trip); counts: a distributed.ShardCounts the caller has put the encoder's local counts into, not yet reduced
         (the trainer adds the mel rows and starts the one all-reduce); the inputs may be shorter than shape.max_len."""
-        G = self.G
-        ex = self._step_shard(_ex, shape, counts)
-        if ex is True:
-            ex, (mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d) = self._exact_inputs(
-                shape, counts, mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d)
-            self._exact_count(ex, coarse_mel if G.model == "shallow" else mel, mel_pad_mask)
-        cd = cond if cond_d is None else cond_d
-        sd = spk if spk_d is None else spk_d
-        cmd = coarse_mel if coarse_mel_d is None else coarse_mel_d
-        # ---------------- D phase (train.py:133-146)
-        # train.py:133 builds (and discards) the generator's autograd graph here; every output is detached
-        # before use (train.py:135-137), so running it under no_grad gives identical results and skips
-        # the activation saves of the grad-enabled forward.
-        # ... and it is launched TOGETHER with the G phase's forward below (same weights: only D is stepped in between;
-        # GaussianDiffusion.pair_forward): one grid of 64-frame tiles over both instead of two of 32-frame tiles
-        G.pair_forward = self.pair_forwards and os.environ.get("MG_PAIR_FORWARDS", "1") != "0"
-        G.pair_inputs = (cond, spk, coarse_mel)
-        try:
-            with torch.no_grad():
-                _, x_ts, x_prevs, x_prev_preds, t = G(mel, cd, sd, mel_pad_mask, cmd)
-        finally:
-            G.pair_forward = False
-            G.pair_inputs = None
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, sd, t, ex)
-        self._model_update(d_loss, self.bucketD, self.optD)
-        # ---------------- G phase (train.py:153-184)
-        x0, x_ts, x_prevs, x_prev_preds, t = G(mel, cond, spk, mel_pad_mask, coarse_mel)
-        g_loss, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss,
-                                   ex)
-        self._model_update(g_loss, self.bucketG, self.optG)
-        self.step_no += 1
-        out["d_loss"] = d_loss.detach()
-        return out
-
-    def _step_shard(self, ex, shape, counts):
-        """None off exact mode (which takes no shape), the caller's context, or True: build one."""
-        if not self.exact_shards:
-            if shape is not None or counts is not None or ex is not None:
-                raise ValueError("shape= / counts= belong to HotPathTrainer(exact_shards=True)")
-            return None
-        return ex if ex is not None else True
+        ex, (mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d) = self._exact_inputs(
+            shape, counts, mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d)
+        return self._walk_tensors(True, ex, mel, cond, spk, mel_pad_mask, coarse_mel, extra_loss, cond_d, spk_d,
+                                  coarse_mel_d)
 
     def _exact_batch(self, batch, shape, counts):
         """exact_shards around a whole model: the 17-slot batch padded to the whole batch's length (data.pad_batch_to),
@@ -395,33 +435,14 @@ class HotPathTrainer:
         and exchanged after that forward, not under the D phase."""
         if getattr(model, "diffusion", None) is not self.G:
             raise ValueError("step_from_model: model.diffusion is not this trainer's generator")
-        ex = self._step_shard(None, shape, counts)
-        if ex is True:
-            ex = self._exact_batch(batch, shape, counts)
+        ex = self._exact_batch(batch, shape, counts) if self._exact(shape, counts) else None
         if pair:
             return self._step_from_model_paired(model, batch, upstream_loss, ex)
-        with torch.no_grad():                    # every D-phase use is detached (train.py:135-137)
-            output, *_ = model(*(batch[2:]))
-        _, x_ts, x_prevs, x_prev_preds, spk, t, _, _ = self._unpack(output)
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, spk, t, ex)
-        self._model_update(d_loss, self.bucketD, self.optD)
-        output, p_targets, coarse_mels = model(*(batch[2:]))
-        batch[9] = p_targets                     # train.py:155
-        x0, x_ts, x_prevs, x_prev_preds, spk, t, mel_pad_mask, slot15 = self._unpack(output)
-        mel = batch[11][:, :mel_pad_mask.shape[1], :]
-        if ex is not None and self.G.model == "shallow":
-            self._exact_count(ex, slot15, mel_pad_mask)
-        extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
-        g_loss, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask,
-                                   slot15 if self.G.model == "shallow" else None, extra, ex)
-        self._model_update(g_loss, self.bucketG, self.optG)
-        self.step_no += 1
-        out["d_loss"] = d_loss.detach()
-        return out
+        return self._walk_model(True, model, batch, upstream_loss, ex)
 
-    def _step_from_model_paired(self, model, batch, upstream_loss, ex=None):
-        """Both encoder passes first (the second with grad), then step() with the two conditioners: one launch for both
-        generator forwards.  Runs model.forward with its diffusion swapped for a recorder, so the encoder-side code
+    def _step_from_model_paired(self, model, batch, upstream_loss, ex):
+        """Both encoder passes first (the second with grad), then step()'s walk with the two conditioners: one launch for
+        both generator forwards.  Runs model.forward with its diffusion swapped for a recorder, so the encoder-side code
         is the model's own."""
         rec = _DiffusionInputs()
         real = model.diffusion
@@ -440,8 +461,8 @@ class HotPathTrainer:
         if ex is not None and self.G.model == "shallow":
             self._exact_count(ex, slot15 if slot15 is not None else coarse, pad)
         extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
-        return self.step(mel, cond, spk, pad, slot15 if slot15 is not None else coarse, extra,
-                         cond_d=d_in[1], spk_d=d_in[2], coarse_mel_d=d_in[4], _ex=ex)
+        return self._walk_tensors(True, ex, mel, cond, spk, pad, slot15 if slot15 is not None else coarse, extra,
+                                  d_in[1], d_in[2], d_in[4])
 
     @torch.no_grad()
     def evaluate_step(self, mel, cond, spk, mel_pad_mask, coarse_mel=None, extra_loss=None, cond_d=None, spk_d=None,
@@ -449,43 +470,17 @@ class HotPathTrainer:
         """The validation step of evaluate.py:70-120 for the path: the same two generator forwards and four
         discriminator passes as step(), under no_grad, no update; returns the same loss dict (exact_shards: the
         rank's shares, with shape= / counts= as in step())."""
-        G = self.G
-        ex = self._step_shard(None, shape, counts)
-        if ex is True:
-            ex, (mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d) = self._exact_inputs(
-                shape, counts, mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d)
-            self._exact_count(ex, coarse_mel if G.model == "shallow" else mel, mel_pad_mask)
-        cd = cond if cond_d is None else cond_d
-        sd = spk if spk_d is None else spk_d
-        cmd = coarse_mel if coarse_mel_d is None else coarse_mel_d
-        _, x_ts, x_prevs, x_prev_preds, t = G(mel, cd, sd, mel_pad_mask, cmd)
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, sd, t, ex)
-        x0, x_ts, x_prevs, x_prev_preds, t = G(mel, cond, spk, mel_pad_mask, coarse_mel)
-        _, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask, coarse_mel, extra_loss, ex)
-        out["d_loss"] = d_loss
-        return out
+        ex, (mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d) = self._exact_inputs(
+            shape, counts, mel, cond, mel_pad_mask, coarse_mel, cond_d, coarse_mel_d)
+        return self._walk_tensors(False, ex, mel, cond, spk, mel_pad_mask, coarse_mel, extra_loss, cond_d, spk_d,
+                                  coarse_mel_d)
 
     @torch.no_grad()
     def evaluate_from_model(self, model, batch, upstream_loss=None, shape=None, counts=None):
         """evaluate.py:76-120 around `model`: two `model(*(batch[2:]))` calls, losses only (exact_shards: as
         step_from_model)."""
-        ex = self._step_shard(None, shape, counts)
-        if ex is True:
-            ex = self._exact_batch(batch, shape, counts)
-        output, *_ = model(*(batch[2:]))
-        _, x_ts, x_prevs, x_prev_preds, spk, t, _, _ = self._unpack(output)
-        d_loss = self._d_loss(x_ts, x_prevs, x_prev_preds, spk, t, ex)
-        output, p_targets, coarse_mels = model(*(batch[2:]))
-        batch[9] = p_targets
-        x0, x_ts, x_prevs, x_prev_preds, spk, t, mel_pad_mask, slot15 = self._unpack(output)
-        mel = batch[11][:, :mel_pad_mask.shape[1], :]
-        if ex is not None and self.G.model == "shallow":
-            self._exact_count(ex, slot15, mel_pad_mask)
-        extra = self._upstream(upstream_loss, batch, output, self.step_no, ex)
-        _, out = self._g_loss(x0, x_ts, x_prevs, x_prev_preds, spk, t, mel, mel_pad_mask,
-                              slot15 if self.G.model == "shallow" else None, extra, ex)
-        out["d_loss"] = d_loss
-        return out
+        ex = self._exact_batch(batch, shape, counts) if self._exact(shape, counts) else None
+        return self._walk_model(False, model, batch, upstream_loss, ex)
 
     def log_scalars(self, out):
         """The host's read-back of a step's losses (train.py:198-199 `.item()`s): one synchronisation, after which the

@@ -93,6 +93,73 @@ def _launch(mg, data, den, g, with_den):
     return out.cpu(), [d.cpu() for d in grads]
 
 
+# ------------------------------------------------------------------ the Python loss table against one built by hand
+# The multi-loss kernels sum in a fixed order, so the spec builders of losses.py must return the bits of a table written
+# out here: whole result vector and every gradient, torch.equal.
+G_OUT = 0.625        # the cotangent of the total
+
+
+def _through_python(out, inputs):
+    grads = torch.autograd.grad(out[0] * G_OUT, inputs)
+    torch.cuda.synchronize()
+    return out.detach().cpu(), [d.cpu() for d in grads]
+
+
+@pytest.mark.parametrize("n", [1, 257, 4099, 12306])          # 12306: several 2048-element blocks per term
+def test_weighted_means_is_the_hand_built_table(mg, n):
+    from mixgan_tts_amd import _lib
+    gen = torch.Generator().manual_seed(n)
+    xs = [torch.randn(n, generator=gen).cuda().requires_grad_() for _ in range(4)]
+    y = torch.randn(n, generator=gen).cuda()                  # the "l1" term's target: a tensor of its own
+    out, grads = _through_python(
+        mg.losses.weighted_means([("mse", xs[0], 0.75, 0.5, 0), ("l1", xs[1], y, 1.25, 1), ("hinge", xs[2], -1.0, 0.3, 2),
+                                  ("mean", xs[3], None, -1.0, 3)]), xs)
+    data = [(_lib.MG_LOSSMODE_MSE, xs[0].detach(), None, 0.75, 0.5, 0), (_lib.MG_LOSSMODE_L1, xs[1].detach(), y, 0.0, 1.25, 1),
+            (_lib.MG_LOSSMODE_HINGE, xs[2].detach(), None, -1.0, 0.3, 2), (_lib.MG_LOSSMODE_MEAN, xs[3].detach(), None, 0.0, -1.0, 3)]
+    ref_out, ref_grads = _launch(mg, data, None, G_OUT, False)
+    assert torch.equal(out, ref_out)
+    for k, (d, r) in enumerate(zip(grads, ref_grads)):
+        assert torch.equal(d, r), "gradient of term %d" % k
+
+
+@pytest.mark.parametrize("n_total", [None, 7])
+def test_2b_totals_are_the_hand_built_tables(mg, n_total):
+    from mixgan_tts_amd import _lib
+    MSE, L1 = _lib.MG_LOSSMODE_MSE, _lib.MG_LOSSMODE_L1
+    gen = torch.Generator().manual_seed(9)
+    B, lam, n_layers = 3, 10.0, 5
+    shapes = [(5, 33), (4, 17), (7, 293), (1, 9)]
+    cm, um = ([torch.randn(2 * B, c, l, generator=gen).cuda().requires_grad_() for c, l in shapes] for _ in range(2))
+    rows = lambda m, lo: m.detach()[lo:lo + B].reshape(-1)  # noqa: E731  (views: the table points into the maps)
+    den = lambda data: [float(a.numel() // B * n_total) for _, a, *_ in data]  # noqa: E731
+    # discriminator: real rows against 1, fake rows against 0, on the last maps
+    tot, d_real, d_fake = mg.losses.d_loss_total_2b(cm[-1], um[-1], B, n_total=n_total)
+    out, grads = _through_python(tot._base, [cm[-1], um[-1]])        # the result vector the three are views of
+    assert torch.equal(torch.stack([tot, d_real, d_fake]).detach().cpu(), out[:3])
+    data = [(MSE, rows(cm[-1], B), None, 1.0, 0.5, 0), (MSE, rows(um[-1], B), None, 1.0, 0.5, 0),
+            (MSE, rows(cm[-1], 0), None, 0.0, 0.5, 1), (MSE, rows(um[-1], 0), None, 0.0, 0.5, 1)]
+    ref_out, ref = _launch(mg, data, den(data) if n_total else None, G_OUT, n_total is not None)
+    assert torch.equal(out, ref_out)
+    for m, real, fake in zip(grads, ref[:2], ref[2:]):
+        assert torch.equal(m, torch.cat([fake, real]).view_as(m))
+    # generator: fake rows of the last maps against 1, fake rows of the others against their real rows
+    maps = cm + um
+    tot, adv, fm = mg.losses.g_adv_fm_total_2b(cm, um, B, lam, n_layers, n_total=n_total)
+    out, grads = _through_python(tot._base, maps)
+    assert torch.equal(torch.stack([tot, adv, fm]).detach().cpu(), out[:3])
+    w = lam * (4.0 / (n_layers + 1)) * 0.5
+    data = [(MSE, rows(cm[-1], 0), None, 1.0, 0.5, 0), (MSE, rows(um[-1], 0), None, 1.0, 0.5, 0)]
+    for j in range(len(shapes) - 1):
+        data += [(L1, rows(cm[j], 0), rows(cm[j], B), 0.0, w, 1), (L1, rows(um[j], 0), rows(um[j], B), 0.0, w, 1)]
+    ref_out, ref = _launch(mg, data, den(data) if n_total else None, G_OUT, n_total is not None)
+    assert torch.equal(out, ref_out)
+    order = [cm[-1], um[-1]] + [m for j in range(len(shapes) - 1) for m in (cm[j], um[j])]     # the terms' maps
+    for m, r in zip(order, ref):
+        d = grads[[id(x) for x in maps].index(id(m))]
+        assert torch.equal(d[:B].reshape(-1), r), "fake rows"
+        assert not d[B:].any(), "the real rows are targets: exactly zero"
+
+
 def _reference(data, den, g):
     """float64: [total, 4 group subtotals, per-term sum / den] and every term's gradient."""
     total, groups, means, grads = 0.0, [0.0] * 4, [], []

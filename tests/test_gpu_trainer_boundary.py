@@ -98,7 +98,8 @@ def test_step_with_two_conditioners_vs_oracle(mg, manifest, tmp_path, paired):
     _tape_trainer(G, tapes[:2])
     cg = conds[1].cuda().requires_grad_()
     out = trainer.step(mel.cuda(), cg, None, pad.cuda(), cond_d=conds[0].cuda())
-    assert G._pair_stash is None
+    assert trainer.last_pair.consumed if paired else trainer.last_pair is None
+    assert not any(getattr(ws, "_mg_busy", False) for ws in G.denoise_fn._ws.values())
     assert G.noise_fn.i == 6 and G.t_fn.i == 2
     # the oracle: D phase on the first conditioner; the G phase sees the discriminator AFTER its update (train.py:146,156)
     ld, _, _ = _oracle_phase(WG, WD, buf, mel, conds[0], pad, tapes[0], True, lam)

@@ -225,7 +225,9 @@ def test_trainer_paired_and_separate_forwards_agree(mg, manifest, tmp_path):
         torch.manual_seed(5)
         outs = [trainer.step(mel.cuda(), cond.cuda(), None, pad.cuda()) for _ in range(2)]
         seen[paired] = (outs, grads)
-        assert G._pair_stash is None                     # consumed by the G-phase forward
+        # the half launched ahead was consumed by the G-phase forward (or never launched), no workspace is left taken
+        assert trainer.last_pair.consumed if paired else trainer.last_pair is None
+        assert not any(getattr(ws, "_mg_busy", False) for ws in G.denoise_fn._ws.values())
     for o1, o2 in zip(seen[True][0], seen[False][0]):
         for k in ("d_loss", "adv_loss", "mel_loss", "fm_loss"):
             a, b = o1[k].item(), o2[k].item()
